@@ -6,8 +6,12 @@ HIP pipeline behind plx_execute_plan, and the download of the (tiny) result.  In
 synthetic (polars_amd/datagen.py: dbgen distributions restated) and already sit in HBM when the
 timed region starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload q1|q3|cfg2|cfg3] [--rows R]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload q1|q3|cfg2|cfg3] [--rows R] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run (no --full) does only what the headline needs: set up the inputs, warm up, time K steps, write the last timed
+step's result to DIR if --dump-outputs is given (dump_outputs), print the line.  --full adds everything below: the spot
+checks of the generated inputs, the CPU baseline, the oracle checks (`verified`), `one_shot_ms`, the secondary workloads.
 
 N > 1: one process per GPU.  --scaling strong (the default at N > 1): the SF100 / 1e9-row configuration in TOTAL, split over the ranks, so the
 N-GPU lines sit on one curve with the N = 1 line (BASELINE: "SF100, 1/2/4/8 GPU"); --scaling weak: every rank holds its own SF100-sized shard (run
@@ -15,7 +19,7 @@ as the extra `..._weak`).  Q1's six-group partials are combined with an all-gath
 of a few hundred bytes (polars_amd/dist.py), no row crosses xGMI; cfg3 / cfg5 pre-aggregate locally and exchange the PARTIAL rows
 by key hash (--mode rows exchanges raw rows instead).  Prints ONE JSON line on rank 0; exits 3 if a result disagreed with the oracle.
 
-Order of work at N = 1: headline (Q1; its input comes from the library's own generator kernel, spot-checked against the
+Order of work at N = 1 with --full: headline (Q1; its input comes from the library's own generator kernel, spot-checked against the
 generator's host twin, with the torch generators as fallback) -> CPU baseline -> secondary workloads (`extras`).  The
 line is complete after the first two; the extras only add to it, and a guard process prints the line as it stands if
 they have not finished PLX_BENCH_DEADLINE_S (420) seconds after the start (run_guarded).  After a workload was timed, the
@@ -40,6 +44,13 @@ CFG2_NULL_PCT = 5
 HASHED_KEY_MULT = 0x9E3779B97F4A7C15 - (1 << 64)      # the odd 64-bit multiplier as an Int64 literal (wrapping multiply = a bijection on the 64-bit keys)
 HASHED_KEY_INV = pow(0x9E3779B97F4A7C15, -1, 1 << 64)   # its inverse mod 2^64: maps result keys back
 WIDE_KEY_MULT2 = 0xC2B2AE3D27D4EB4F - (1 << 64)         # a second odd multiplier: the other key column of the two-column key workload
+FULL = True     # main() sets it from --full; helpers imported by the tests keep their checks
+DUMP_MAX_BYTES = 64_000_000     # --dump-outputs: at most this much in all (a seeded row sample of larger results)
+
+
+def verify_on() -> bool:
+    """the oracle checks of timed results run in --full runs, unless PLX_BENCH_VERIFY=0"""
+    return FULL and os.environ.get("PLX_BENCH_VERIFY", "1") != "0"
 
 
 def parse():
@@ -56,7 +67,11 @@ def parse():
                     "SF100 on 1/2/4/8 GPUs); weak = every rank holds the full single-GPU configuration (SF100 / 1e9 rows per rank)")
     ap.add_argument("--mode", default="auto", choices=["auto", "preagg", "rows"], help="sharded cfg3 / cfg5: what crosses the fabric (dist.sharded_groupby)")
     ap.add_argument("--dry-run", action="store_true", help="sharded workloads only: numpy frames + gloo instead of the library + RCCL (control-flow check without GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the result of the last timed step as DIR/<column>.npy (float64; single-GPU runs)")
+    ap.add_argument("--full", action="store_true", help="also the input spot checks, CPU baseline, oracle checks, one-shot step and secondary workloads")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.dry_run or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs: single-GPU runs only")
     if args.scaling is None:
         args.scaling = "strong" if max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1 else "weak"
     return args
@@ -79,6 +94,8 @@ def check_native_lineitem(pl, df, n: int, seed: int) -> None:
     from polars_amd import datagen
     if df.height != n:
         raise RuntimeError(f"generated {df.height} rows, wanted {n}")
+    if not FULL:
+        return
     blk = min(4096, n)
     for row0 in sorted({0, max(0, n // 2 - 1234), n - blk}):
         got = df.slice(row0, blk)
@@ -99,7 +116,7 @@ def native_uniform_column(pl, name: str, dtype, np_name: str, n: int, seed: int,
     from polars_amd import datagen
     s = datagen.uniform_native(pl, name, dtype, n, seed, stream, lo, hi, scale)
     df = pl.DataFrame([s])
-    for row0, blk in _blocks(n):
+    for row0, blk in (_blocks(n) if FULL else []):
         if not np.array_equal(df.slice(row0, blk)[name].to_numpy(), datagen.uniform_native_host(np_name, row0, blk, seed, stream, lo, hi, scale)):
             raise RuntimeError(f"device generator differs from its host twin in {name} at rows [{row0}, {row0 + blk})")
     return s
@@ -111,6 +128,8 @@ def check_native_q3(pl, O, L, n_orders: int, seed: int) -> None:
     from polars_amd import datagen
     if O.height != n_orders:
         raise RuntimeError(f"generated {O.height} orders, wanted {n_orders}")
+    if not FULL:
+        return
     blk = min(2048, n_orders)
     for order0 in sorted({0, n_orders - blk}):
         wo, wl, _cnt = datagen.orders_lineitem_native_host(order0, blk, n_orders, seed)
@@ -1779,14 +1798,16 @@ def spawn_ranks(args) -> int:
 
 
 def main():
+    global FULL
     args = parse()
+    FULL = args.full
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     rank, ws = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    guard = os.environ.get("PLX_BENCH_GUARD", "1") != "0" and not args.no_extras
+    guard = os.environ.get("PLX_BENCH_GUARD", "1") != "0" and FULL and not args.no_extras
     deadline = float(os.environ.get("PLX_BENCH_DEADLINE_S", "420"))
-    # runs with secondary workloads go through the guard (every rank of an N > 1 run: a rank whose line-printing peer was cut must not
-    # wait in a collective forever); --no-extras runs (rocprofv3 wraps those) do not
+    # runs with secondary workloads (--full) go through the guard (every rank of an N > 1 run: a rank whose line-printing peer was cut must not
+    # wait in a collective forever); plain and --no-extras runs (rocprofv3 wraps those) do not
     if guard:
         sys.exit(run_guarded(lambda emit: run(args, emit), deadline, prints=rank == 0))
     final = {}
@@ -2061,11 +2082,11 @@ def sharded_groupby_line(ctx, args, workload: str, steps: int, warmup: int) -> d
         allc = {c: np.concatenate([e["cols"][c] for e in every]) for c in every[0]["cols"]}
         isum = sum(e["sum"] for e in every)
         verified = verify_sharded_groupby(allc, key_name, "v_sum", second, total_rows, isum if cfg5 else int(round(isum)), [(n, 10 + r) for r in range(ws)], n_keys,
-                                          "UInt32" if cfg5 else "Int64", val_np, val_args, 0.0 if os.environ.get("PLX_BENCH_VERIFY", "1") == "0" else float(os.environ.get("PLX_BENCH_VERIFY_BUDGET_S", "40")))
+                                          "UInt32" if cfg5 else "Int64", val_np, val_args, 0.0 if not verify_on() else float(os.environ.get("PLX_BENCH_VERIFY_BUDGET_S", "40")))
         if verified.get("ok") is False:
             print(f"[bench] VERIFICATION FAILED for the sharded {workload}: {verified}", file=sys.stderr)
         return verified
-    verified = host_check(check) if rank == 0 else None
+    verified = host_check(check) if rank == 0 and FULL else None
     rec_bytes = (4 + 8) if cfg5 else 16
     algo = n * rec_bytes + n_keys * 20 // ws
     how = {"preagg": "local partitioned group-by -> partial rows exchanged by key hash (one grouped all-to-all(v)) -> merge on the owner",
@@ -2155,7 +2176,7 @@ def sharded_q3_line(ctx, args, steps: int, warmup: int, mode=None) -> dict:
         if not ok:
             print(f"[bench] VERIFICATION FAILED for the sharded q3: {verified}", file=sys.stderr)
         return verified
-    verified = host_check(check) if rank == 0 and os.environ.get("PLX_BENCH_VERIFY", "1") != "0" else None
+    verified = host_check(check) if rank == 0 and verify_on() else None
     algo = nl * datagen.Q3_LINEITEM_BYTES_PER_ROW + no * datagen.Q3_ORDERS_BYTES_PER_ROW
     how = {"shuffle": "both sides filtered, then routed by key hash (one grouped all-to-all(v) per input), local fused join -> group-by over the owned keys",
            "broadcast": "filtered build side all-gathered, probe side stays, partial groups routed by key (one small all-to-all(v)) and merged by the owner", "local": "single rank"}[info.get("mode", "local")]
@@ -2208,7 +2229,7 @@ def rowsharded_line(ctx, args, workload: str, steps: int, warmup: int) -> dict:
     verified = None
     if workload == "q1":
         parts = ctx.gather(local["res"])
-        if rank == 0 and os.environ.get("PLX_BENCH_VERIFY", "1") != "0":
+        if rank == 0 and verify_on():
             mine_res = local["res"]
 
             def check():
@@ -2220,7 +2241,7 @@ def rowsharded_line(ctx, args, workload: str, steps: int, warmup: int) -> dict:
                         "combined_equals_merge_of_rank_results": bool(merged_ok), "rank0_shard_vs_oracle": mine,
                         "against": "rank 0's shard: oracle (orc_q1_streaming over the shard's host twin); combined result: merge of the gathered per-rank results"}
             verified = host_check(check)
-    elif rank == 0 and not dry and os.environ.get("PLX_BENCH_VERIFY", "1") != "0":
+    elif rank == 0 and not dry and verify_on():
         last_res = local["res"]
         verified = host_check(lambda: _verify(wl, last_res, float(os.environ.get("PLX_BENCH_VERIFY_BUDGET_S", "40"))))
     line = multi_line_base(ctx, args, steps, warmup, dt, wl.rows * ws, "f64", strong)
@@ -2278,7 +2299,7 @@ def run_multi(args, emit):
         raise RuntimeError(f"the communicator spans {line['comm']['world_size']} ranks, the launcher's environment names {line['comm']['env_world_size']}")
     if ctx.rank == 0:
         emit(line)
-    if not args.no_extras:
+    if FULL and not args.no_extras:
         extras = {}
         line["extras"] = extras
         k2 = max(3, args.steps // 4)
@@ -2329,12 +2350,68 @@ def _verify(wl, res, budget_s: float):
     return v
 
 
+def _as_float64(vals):
+    """A result column (numpy array or list; None = null) as float64: nulls NaN, strings their rank among the column's distinct strings."""
+    import numpy as np
+    try:
+        return np.asarray(vals, dtype=np.float64)
+    except (TypeError, ValueError):
+        pass
+    vals = list(vals)
+    if any(isinstance(v, (str, bytes)) for v in vals):
+        rank = {s: i for i, s in enumerate(sorted({v for v in vals if v is not None}))}
+        vals = [None if v is None else rank[v] for v in vals]
+    return np.array([np.nan if v is None else float(v) for v in vals], dtype=np.float64)
+
+
+def dump_outputs(pl, res, out_dir: str, max_bytes: int = DUMP_MAX_BYTES) -> None:
+    """--dump-outputs: the result of the last timed step as out_dir/<column>.npy, float64.  A result that fits in max_bytes is written whole, its rows
+    in a canonical order (sorted by the columns from left to right: group-by results come in no defined order); a larger one as a fixed, seeded sample
+    of its rows, gathered on the device, in their returned order."""
+    import re
+    import numpy as np
+    if isinstance(res, dict):
+        cols = dict(res)
+    elif hasattr(res, "columns") and hasattr(res, "height"):
+        cols = {c: res[c] for c in res.columns}
+    elif hasattr(res, "to_numpy"):
+        cols = {getattr(res, "name", "") or "result": res if isinstance(res, pl.Series) else np.asarray(res.to_numpy())}
+    else:
+        raise TypeError(f"--dump-outputs: cannot export a step result of type {type(res).__name__}")
+    n = len(next(iter(cols.values()))) if cols else 0
+    sampled = n * len(cols) * 8 > max_bytes
+    if sampled:
+        k = max_bytes // (8 * len(cols))
+        idx = np.unique(np.random.default_rng(0).integers(0, n, k))
+        if any(isinstance(v, pl.Series) for v in cols.values()):
+            sel = pl.Series("idx", idx.astype(np.uint32), dtype=pl.UInt32)
+            cols = {c: v.gather(sel) if isinstance(v, pl.Series) else np.asarray(v)[idx] for c, v in cols.items()}
+        else:
+            cols = {c: np.asarray(v)[idx] for c, v in cols.items()}
+    out = {}
+    for c, v in cols.items():
+        if isinstance(v, pl.Series):
+            v = v.to_list()
+        elif hasattr(v, "to_numpy"):
+            v = v.to_numpy()
+        out[c] = _as_float64(v)
+    if not sampled and out:
+        order = np.lexsort(tuple(reversed(list(out.values()))))
+        out = {c: a[order] for c, a in out.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for c, a in out.items():
+        np.save(os.path.join(out_dir, re.sub(r"[^A-Za-z0-9_.-]", "_", c) + ".npy"), a)
+    print(f"[bench] {len(out)} result arrays ({'a seeded sample of ' if sampled else ''}{n} rows) written to {out_dir}", file=sys.stderr)
+
+
 def run(args, emit):
     """The benchmark proper; emit(line) is called with every improved version of the JSON line (rank 0)."""
     import torch
     rank, local_rank, ws = int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if ws > 1 or args.dry_run or os.environ.get("PLX_BENCH_FORCE_SHARDED") == "1":
         # N > 1, `--dry-run`, or the sharded operators at world size 1 (PLX_BENCH_FORCE_SHARDED=1: a self-exchange through RCCL, the smoke run a one-GPU box allows)
+        if args.dump_outputs:
+            raise RuntimeError("--dump-outputs: single-GPU runs only")
         run_multi(args, emit)
         return
     distributed = False
@@ -2360,6 +2437,8 @@ def run(args, emit):
             pl._ffi.lib().plx_memory_reserve(0)
     wl = make_workload(pl, args.workload, rows, seed=seed, ws=ws)
     dt, stats, res, cold_ms = timed(pl, wl, args.steps, max(args.warmup, 1), distributed)
+    if args.dump_outputs:
+        dump_outputs(pl, res, args.dump_outputs)
     total_rows = wl.rows * ws * args.steps
     line = {
         "metric": "rows/sec + achieved HBM GB/s, TPC-H Q1/Q3 SF100, 1/2/4/8 GPU vs CPU",
@@ -2371,13 +2450,13 @@ def run(args, emit):
         "whole_query_GBps_per_gpu": round(wl.algo_bytes * args.steps / dt / 1e9, 1),
         "cold_first_step_ms": None if cold_ms is None else round(cold_ms, 2),      # first step of the process; EXCLUDES the pool mapping below (pool.map_ms, done at start-up)
         "pool": pool,
-        "one_shot_ms": one_shot_ms(pl, wl),
+        "one_shot_ms": one_shot_ms(pl, wl) if FULL else None,
         "step_ms": getattr(timed, "last_step_ms", None),      # every timed step, in order: a stall of the box shows here, not only in the mean
         **step_spread(getattr(timed, "last_step_ms", None), wl.rows * ws),
         "roofline": roofline(stats, wl, args.steps),
         "kernels": _kernels(stats, 8),
     }
-    want_cpu = rank == 0 and ws == 1 and not args.no_cpu
+    want_cpu = rank == 0 and ws == 1 and FULL and not args.no_cpu
     if rank == 0:
         emit(line, not want_cpu)                 # the headline is safe from here on (a guard cut waits for the CPU baseline)
     if want_cpu:
@@ -2403,9 +2482,9 @@ def run(args, emit):
         except Exception as e:
             line["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"[:300]}
         emit(line, True)
-    elif rank == 0 and ws == 1 and args.workload != "q1" and os.environ.get("PLX_BENCH_VERIFY", "1") != "0":
+    elif rank == 0 and ws == 1 and args.workload != "q1" and verify_on():
         line["verified"] = _verify(wl, res, 60.0)
-    if rank == 0 and not args.no_extras and ws == 1:
+    if rank == 0 and FULL and not args.no_extras and ws == 1:
         extras = {}
         line["extras"] = extras
         k2 = max(3, args.steps // 4)
@@ -2457,7 +2536,7 @@ def run(args, emit):
                             t_dl = time.perf_counter(); r2._download_all(); dls.append((time.perf_counter() - t_dl) * 1e3)
                         extras[w2.name]["result_download_ms"] = round(min(dls), 3)
                         extras[w2.name]["result_download_first_ms"] = round(dls[0], 3)
-                if os.environ.get("PLX_BENCH_VERIFY", "1") != "0":
+                if verify_on():
                     pending_checks.append((w2.name, w2.verify, r2))       # checked after every secondary workload has been timed (below)
                 del w2, r2
             except Exception as e:  # a secondary workload must never take the headline line down
@@ -2480,7 +2559,7 @@ def run(args, emit):
                     "vs_ordered_inputs": (round(d3 / k2 * 1e3 / ordered["ms_per_step"], 2) if ordered.get("ms_per_step") else None),
                     "groups": int(r3.height) if hasattr(r3, "height") else None, "roofline": roofline(s3, w3, k2), "kernels": _kernels(s3, 6),
                     "note": "same query over the SAME rows as tpch_q3_sf100 (the library's generator), both tables in a seeded random row order (device gather)"}
-                if os.environ.get("PLX_BENCH_VERIFY", "1") != "0":
+                if verify_on():
                     pending_checks.append(("tpch_q3_sf100_shuffled_inputs", w3.verify, r3))
                 del w3, r3
             except Exception as e:
@@ -2511,7 +2590,7 @@ def run(args, emit):
                                    "result": "left in HBM (a multi-gigabyte frame: the next operator's input)",
                                    "whole_query_GBps": round(w2.algo_bytes * k2 / d2 / 1e9, 1), "roofline": roofline(s2, w2, k2), "kernels": _kernels(s2, 6)}
                 emit(line)
-                if os.environ.get("PLX_BENCH_VERIFY", "1") != "0":
+                if verify_on():
                     extras[w2.name]["verified"] = _verify(w2, r2, float(os.environ.get("PLX_BENCH_VERIFY_BUDGET_S", "40")))
                 del w2, r2
             except Exception as e:

@@ -148,7 +148,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--rows", "120000"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--rows", "120000"],
                        capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     head, d = bench_lines.split(r.stdout)
@@ -187,7 +187,7 @@ def test_sharded_groupby_bench_dry_run_prints_a_complete_line():
     rows = 200_000
     for wl, kdt in (("cfg3", "Int64"), ("cfg5", "UInt32")):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29541",
-               os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", wl, "--rows", str(rows), "--dry-run", "--scaling", "weak"]
+               os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", wl, "--rows", str(rows), "--dry-run", "--scaling", "weak"]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root, env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
         assert r.returncode == 0, r.stderr[-2000:]
         head, d = bench_lines.split(r.stdout)
@@ -204,7 +204,7 @@ def test_sharded_groupby_bench_dry_run_prints_a_complete_line():
         assert d["verified"]["ok"] is True and all(d["verified"]["checks"].values()) and "oracle" in d["verified"]["against"]
     # few keys per rank (keys 0..1e6 but 2e6 rows would be slow here: force the mode instead): partial rows cross the fabric, not rows; strong scaling label
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29542",
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg3", "--rows", str(rows), "--dry-run", "--mode", "preagg", "--scaling", "strong"]
+           os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg3", "--rows", str(rows), "--dry-run", "--mode", "preagg", "--scaling", "strong"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root, env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
     assert r.returncode == 0, r.stderr[-2000:]
     _, d = bench_lines.split(r.stdout)
@@ -223,7 +223,7 @@ def test_bench_eight_ranks_dry_run_is_quiet_and_complete():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-run", "--steps", "2", "--warmup", "1", "--rows", "120000"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "8", "--dry-run", "--steps", "2", "--warmup", "1", "--rows", "120000"],
                        capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "Traceback" not in r.stderr, r.stderr[-2000:]

@@ -1,5 +1,5 @@
 """The library's lineitem generator kernel against its host twin, and TPC-H Q1 over a generated table against the oracle.
-bench.py performs the same spot check before every headline measurement (and falls back to the torch generators if it
+bench.py --full performs the same spot check before the headline measurement (and falls back to the torch generators if it
 fails), so a defect here cannot corrupt a measurement."""
 import numpy as np
 import pytest

@@ -724,7 +724,7 @@ def test_bench_multi_gpu_default_run_through_rccl_at_world_size_one(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(PLX_BENCH_FORCE_SHARDED="1", PLX_BENCH_EXTRAS_FILE=str(tmp_path / "extras.json"), MASTER_ADDR="127.0.0.1", MASTER_PORT="29631")
     try:
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--rows", "400000"], capture_output=True, text=True, timeout=420, cwd=root, env=env)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--rows", "400000"], capture_output=True, text=True, timeout=420, cwd=root, env=env)
     except subprocess.TimeoutExpired as e:
         err = e.stderr.decode(errors="replace") if isinstance(e.stderr, bytes) else (e.stderr or "")
         pytest.skip("the RCCL run did not finish within 420 s (seen on freshly provisioned boxes: ncclCommInitRank not returning); last lines: " + " | ".join(err.strip().splitlines()[-3:]))
@@ -756,7 +756,7 @@ def test_bench_multi_gpu_default_run_through_rccl_on_every_gpu_of_the_box(tmp_pa
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(PLX_BENCH_EXTRAS_FILE=str(tmp_path / "extras.json"), MASTER_ADDR="127.0.0.1", MASTER_PORT="29641", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--rows", "400000"], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--rows", "400000"], capture_output=True, text=True,
                        timeout=900, cwd=root, env=env)
     assert r.returncode == 0, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
     head, full = bench_lines.split(r.stdout)
