@@ -357,10 +357,28 @@ typedef enum plx_ir_kind {
   PLX_IR_SELECT = 2,  /* input, exprs */
   PLX_IR_HSTACK = 3,  /* input, exprs (with_columns) */
   PLX_IR_GROUPBY = 4, /* input, keys, exprs (aggs), maintain_order */
-  PLX_IR_JOIN = 5,    /* input, input_right, keys (left_on), keys_right (right_on), how, suffix */
+  PLX_IR_JOIN = 5,    /* input, input_right, keys (left_on), keys_right (right_on), how, suffix, maintain_order (plx_join_order) */
   PLX_IR_SORT = 6,    /* input, keys (by), sort_descending[n_keys], sort_nulls_last[n_keys] (IR::Sort; always stable) */
   PLX_IR_SLICE = 7    /* input, slice_offset (negative: from the end), slice_len (IR::Slice); directly above a Sort it becomes top-k */
 } plx_ir_kind;
+
+/* Row order of a PLX_IR_JOIN's output (plx_ir.maintain_order of a join node; JoinArgs::maintain_order / MaintainOrderJoin of the reference).
+ *   NONE        unspecified: whatever the route produces (partition order on the partitioned probes, the other side's order when the
+ *               requested side became the build side, newest row first among duplicate build keys).
+ *   LEFT        output rows are in non-decreasing left row index; the order among the rows of one left row is unspecified.
+ *   LEFT_RIGHT  sorted by (left row index, right row index): a total order, the output is unique.
+ *   RIGHT, RIGHT_LEFT  the mirror image.
+ * PLX_JOIN_LEFT: LEFT and LEFT_RIGHT (an unmatched left row is one output row at its left position, right columns null); RIGHT and
+ * RIGHT_LEFT return PLX_ERR_UNSUPPORTED with a message that names maintain_order (where the rows without a right index would go is not
+ * defined here).  PLX_JOIN_SEMI / PLX_JOIN_ANTI return left order whatever the value.  A value outside 0..4 is PLX_ERR_INVALID; the
+ * option is never silently ignored.  The join feeding a fused join -> group-by is the one exception: its groups are unordered. */
+typedef enum plx_join_order {
+  PLX_JOIN_ORDER_NONE = 0,
+  PLX_JOIN_ORDER_LEFT = 1,
+  PLX_JOIN_ORDER_RIGHT = 2,
+  PLX_JOIN_ORDER_LEFT_RIGHT = 3,
+  PLX_JOIN_ORDER_RIGHT_LEFT = 4
+} plx_join_order;
 
 typedef struct plx_ir {
   int32_t kind; /* plx_ir_kind */
@@ -375,7 +393,7 @@ typedef struct plx_ir {
   const int32_t* keys_right;
   int32_t n_keys_right;
   int32_t how; /* plx_join_how */
-  int32_t maintain_order;
+  int32_t maintain_order; /* PLX_IR_GROUPBY / PLX_IR_SORT: 0 / 1; PLX_IR_JOIN: plx_join_order */
   const char* suffix; /* join suffix, NULL = "_right" */
   const uint8_t* sort_descending; /* PLX_IR_SORT: n_keys flags, NULL = ascending */
   const uint8_t* sort_nulls_last; /* PLX_IR_SORT: n_keys flags, NULL = nulls first */

@@ -26,6 +26,7 @@ ADD, SUB, MUL, TRUE_DIV, FLOOR_DIV, MOD = range(6)
 AND, OR, XOR = range(3)
 AGG_SUM, AGG_MEAN, AGG_MIN, AGG_MAX, AGG_COUNT, AGG_LEN, AGG_FIRST = range(7)
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = range(4)
+JOIN_ORDER_NONE, JOIN_ORDER_LEFT, JOIN_ORDER_RIGHT, JOIN_ORDER_LEFT_RIGHT, JOIN_ORDER_RIGHT_LEFT = range(5)   # plx_join_order
 AE_COLUMN, AE_LITERAL, AE_BINARY, AE_CAST, AE_AGG, AE_LEN, AE_ALIAS, AE_NOT, AE_IS_NULL, AE_IS_NOT_NULL, AE_FILL_NULL = range(11)
 (OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_PLUS, OP_MINUS, OP_MULTIPLY, OP_TRUE_DIVIDE,
  OP_FLOOR_DIVIDE, OP_MODULUS, OP_AND, OP_OR, OP_XOR) = range(15)

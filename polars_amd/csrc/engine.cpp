@@ -48,6 +48,12 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
     for (int j = 0; j < ir[i].n_keys; j++) n.keys.push_back(ir[i].keys[j]);
     for (int j = 0; j < ir[i].n_keys_right; j++) n.keys_right.push_back(ir[i].keys_right[j]);
     n.how = ir[i].how; n.maintain_order = ir[i].maintain_order;
+    if (n.kind == PLX_IR_JOIN) {
+      // plx_join_order: never silently ignored
+      PLX_REQUIRE(n.maintain_order >= PLX_JOIN_ORDER_NONE && n.maintain_order <= PLX_JOIN_ORDER_RIGHT_LEFT, PLX_ERR_INVALID, "join: maintain_order outside 0..4 (plx_join_order)");
+      PLX_REQUIRE(!(n.how == PLX_JOIN_LEFT && (n.maintain_order == PLX_JOIN_ORDER_RIGHT || n.maintain_order == PLX_JOIN_ORDER_RIGHT_LEFT)), PLX_ERR_UNSUPPORTED,
+                  std::string("left join with maintain_order=") + join::join_order_name(n.maintain_order) + ": only maintain_order none / left / left_right are on this path for a left join");
+    }
     if (ir[i].suffix) n.suffix = ir[i].suffix;
     if (n.kind == PLX_IR_SORT) {
       for (int j = 0; j < ir[i].n_keys; j++) {
@@ -2320,6 +2326,14 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
   bool done_direct = false, multi = B->height > 0 && B->cols[bki]->repeats_as_build_key;
   ColumnPtr pidx, bidx;
   std::string cand_how, pd, table_how;
+  bool cand_in_row_order = true;            // false: the candidates are in partition order (partitioned probes) and were not put back
+  // candidates of a partitioned probe go back into row order when the requested order can use it (join::order_pairs then has little or nothing to do)
+  auto partitioned_candidates = [&](ColumnPtr& c) {
+    if (!join::join_order_needs_probe_order(jn.maintain_order, build_right)) { cand_in_row_order = false; return; }
+    std::string rd;
+    join::restore_candidate_order(c, &rd);
+    cand_how += " -> " + rd;
+  };
   const int pmode = partitioned_probe_mode();
   int64_t kmn = 0, kmx = 0;
   if (!(plan.flags & PLX_PLAN_NO_DIRECT_JOIN) && !multi && B->height > 0 && kdt != PLX_U64 && ops::int_range(B->cols[bki], &kmn, &kmx)) {
@@ -2349,7 +2363,7 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
           if (pmode == 2 || (pmode == 1 && P->height >= ((int64_t)1 << 24) && range >= ((uint64_t)1 << 28) && nb * 8 <= range)) {
             if (pk->order_state == 0) pk->order_state = k::sample_sortedness(pk) >= 0.9 ? 1 : 2;
             std::string ppd;
-            if ((pmode == 2 || pk->order_state == 2) && k::partitioned_probe_hits(cs.shape, cs.args, dt, nb, find_static_shape(cs.shape), &cand, &ppd)) cand_how = ppd;
+            if ((pmode == 2 || pk->order_state == 2) && k::partitioned_probe_hits(cs.shape, cs.args, dt, nb, find_static_shape(cs.shape), &cand, &ppd)) { cand_how = ppd; partitioned_candidates(cand); }
             else cand = nullptr;
           }
           if (!cand) {
@@ -2448,7 +2462,7 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
   ColumnPtr cand;
   if (!left_join && (pmode == 2 || (pmode == 1 && P->height >= ((int64_t)1 << 24) && (cap + 1) * 16 > ((uint64_t)64 << 20) && nb * 16 <= (uint64_t)P->height))) {
     std::string pd;
-    if (k::partitioned_hash_probe_hits(cs.shape, cs.args, t, nb, find_static_shape(cs.shape), &cand, &pd)) cand_how = pd;
+    if (k::partitioned_hash_probe_hits(cs.shape, cs.args, t, nb, find_static_shape(cs.shape), &cand, &pd)) { cand_how = pd; partitioned_candidates(cand); }
     else cand = nullptr;
   }
   if (!cand && !ppreds.empty()) {
@@ -2465,6 +2479,13 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
   PLX_HIP(hipStreamSynchronize(stream()));
   table_how = "hash table cap=2^" + std::to_string(log2_cap) + (build_how.empty() ? "" : " [" + build_how + "]") + (multi ? " multi-value (row chains)" : " unique-keys");
   }  // hash-table pipeline
+  // ---- the order the join was asked to keep (plx_join_order): the pair list is ordered, the gathers below then produce the frame in that order
+  if (jn.maintain_order != PLX_JOIN_ORDER_NONE) {
+    join::PairProps props; props.probe_ordered = cand_in_row_order; props.runs_ordered = !multi;
+    std::string od;
+    join::order_pairs(jn.maintain_order, build_right, props, pidx, bidx, &od);
+    pd += ", " + od;
+  }
   // ---- payload: one multi-column gather per side
   const ColumnPtr& lidx = build_right ? pidx : bidx;
   const ColumnPtr& ridx = build_right ? bidx : pidx;
@@ -2607,8 +2628,17 @@ static FramePtr exec_join(Plan& plan, const IRN& n) {
   }
   ColumnPtr li, ri;
   std::string d;
-  join::join_indices(n.how, lk, rk, li, ri, &d);
+  bool dup_build_keys = false;
+  join::join_indices(n.how, lk, rk, li, ri, &d, &dup_build_keys);
   d = packed_desc + d;
+  if (n.maintain_order != PLX_JOIN_ORDER_NONE && n.how != PLX_JOIN_SEMI && n.how != PLX_JOIN_ANTI) {
+    // join_indices emits at scanned offsets: probe order; its chains (duplicate build keys) are newest first.  It builds on the right unless the left side is not the larger one of an inner join.
+    const bool probe_is_left = n.how == PLX_JOIN_LEFT || left->height > right->height;
+    join::PairProps props; props.probe_ordered = true; props.runs_ordered = !dup_build_keys;
+    std::string od;
+    join::order_pairs(n.maintain_order, probe_is_left, props, probe_is_left ? li : ri, probe_is_left ? ri : li, &od);
+    d += ", " + od;
+  }
   if (n.how == PLX_JOIN_SEMI || n.how == PLX_JOIN_ANTI) {
     // left columns only, left order (single_keys_semi_anti.rs; _finish_join is not involved)
     plan.desc += "Join{" + d + ", gather x" + std::to_string(left->cols.size()) + "}; ";

@@ -11,8 +11,9 @@
 namespace plx {
 namespace join {
 
-// (left_idx, right_idx) as PLX_U32 columns; LEFT join: right_idx nullable.
-void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc);
+// (left_idx, right_idx) as PLX_U32 columns; LEFT join: right_idx nullable.  Pairs come out in probe order (the probe side is the left one unless an inner join's
+// left side is not the larger one); *dup_build_keys (may be null; inner / left) = the build side repeats a key, so the pairs of one probe row are in chain order.
+void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys = nullptr);
 
 // Pairs of an inner / left join from a build table the fused build scan filled (fused::JoinAggTable: unique keys, or chains of rows per key) over a candidate
 // list of probe rows (`cand`: PLX_U32, null = every row of probe_key).  Pair order = candidate order; a left join keeps every candidate (build_idx nullable).
@@ -21,6 +22,19 @@ void join_pairs(int how, const ColumnPtr& probe_key, const ColumnPtr& cand, cons
 // the same against a direct-address build table (unique build keys over a dense range: bitmap + rank, fused::DirectJoinTable) and its slot -> build row map
 void join_pairs_direct(int how, const ColumnPtr& probe_key, const ColumnPtr& cand, const fused::DirectJoinTable& dt, const uint32_t* slot_row, ColumnPtr& probe_idx, ColumnPtr& build_idx,
                        std::string* desc);
+
+// ---- the order of the pair list (kernels_join_order.hip; plx_ir.maintain_order of a PLX_IR_JOIN node, plx_join_order) ----
+// What the producer of a pair list guarantees: probe_ordered = probe index non-decreasing (join_indices; join_pairs over a candidate list in row order);
+// runs_ordered = inside one probe row the build index increases (unique build keys; not chains).
+struct PairProps { bool probe_ordered = false, runs_ordered = false; };
+// Puts (probe_idx, build_idx) into `order` (plx_join_order; NONE: untouched, *desc left empty).  probe_is_left: the probe side is the join's left input.  A left join's
+// nullable build_idx keeps its nulls (kNoRow -> validity is rebuilt when rows moved).  *desc = "order=<name>: <what was done>".
+void order_pairs(int order, bool probe_is_left, PairProps props, ColumnPtr& probe_idx, ColumnPtr& build_idx, std::string* desc);
+// A candidate list that is in partition order (k::partitioned_probe_hits / k::partitioned_hash_probe_hits) back into row order: key-only radix of the u32 row ids.
+void restore_candidate_order(ColumnPtr& cand, std::string* desc);
+// does `order` need the pair list in probe order to take a cheap branch of order_pairs (primary = probe side, or a secondary order is asked)?
+bool join_order_needs_probe_order(int order, bool probe_is_left);
+const char* join_order_name(int order);
 
 // HashPartitioner (polars-utils/src/hashing.rs:72-121): rows grouped by partition.
 void hash_partition(const ColumnPtr& key, int n_partitions, uint64_t seed, ColumnPtr& perm, int64_t* counts_out);

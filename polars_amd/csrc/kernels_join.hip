@@ -134,7 +134,8 @@ __global__ __launch_bounds__(kBlock) void join_emit_kernel(KeyCol probe, Table t
 static KeyCol key_col(const ColumnPtr& c) { KeyCol kc; kc.values = c->data(); kc.validity = c->valid_words(); kc.dtype = c->dtype; kc.n = c->len; return kc; }
 static int ceil_log2(uint64_t x) { int b = 0; while ((1ull << b) < x) b++; return b; }
 
-void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc) {
+void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys) {
+  if (dup_build_keys) *dup_build_keys = false;
   PLX_REQUIRE(left_key->dtype == right_key->dtype, PLX_ERR_INVALID,
               std::string("join keys have different dtypes (") + dtype_name(left_key->dtype) + ", " + dtype_name(right_key->dtype) + ")");
   PLX_REQUIRE(how == PLX_JOIN_INNER || how == PLX_JOIN_LEFT || how == PLX_JOIN_SEMI || how == PLX_JOIN_ANTI, PLX_ERR_UNSUPPORTED, "join type outside the hot path");
@@ -198,9 +199,10 @@ void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key
     bidx->validity = ok->values; bidx->null_count = -1;
     if (column_null_count(bidx) == 0) { bidx->validity = nullptr; bidx->null_count = 0; }
   }
-  if (desc) {
+  if (desc || dup_build_keys) {
     uint32_t f = 0; d2h_sync(&f, flags->ptr, 4);
-    *desc = std::string("hash_join[build=") + (left_join ? "right" : (swapped ? "left" : "right")) + " rows=" + std::to_string(build->len) + " cap=2^" + std::to_string(log2_cap) +
+    if (dup_build_keys) *dup_build_keys = f != 0;
+    if (desc) *desc = std::string("hash_join[build=") + (left_join ? "right" : (swapped ? "left" : "right")) + " rows=" + std::to_string(build->len) + " cap=2^" + std::to_string(log2_cap) +
             (f ? " dup-keys" : " unique-keys") + ", probe rows=" + std::to_string(np) + ", pairs=" + std::to_string(total) + "]";
   }
   if (left_join || !swapped) { left_idx = pidx; right_idx = bidx; }

@@ -120,11 +120,13 @@ __global__ __launch_bounds__(kBlock) void radix_count_kernel(const uint64_t* __r
 constexpr int kIPT = 4;                          // keys per thread and ranking round
 constexpr int kGroups = kIPT * kWaves;           // (item, wave) pairs of a round, in input order
 static_assert(kItems % kIPT == 0, "a tile is a whole number of rounds");
+// kPayload = false: key-only instantiation (sort_keys_u64: the whole record is the 64-bit code -- 8 B read + 8 B written per key and pass, 34 KB of LDS, no index staging)
+template <bool kPayload>
 __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(const uint64_t* __restrict__ enc_in, const uint32_t* __restrict__ idx_in, int64_t n, int shift,
                                                                const uint64_t* __restrict__ offsets, uint32_t nblocks, uint64_t* __restrict__ enc_out,
                                                                uint32_t* __restrict__ idx_out) {
   __shared__ uint64_t s_enc[kTile];              // the tile, sorted by digit (32 KB)
-  __shared__ uint32_t s_idx[kTile];              // 16 KB
+  __shared__ uint32_t s_idx[kPayload ? kTile : 1];   // 16 KB
   __shared__ uint64_t gbase[256];                // global slot of the digit's first key of this tile minus its local start
   __shared__ unsigned int hist[256];             // tile histogram, then the running local position of every digit value
   __shared__ unsigned int round_base[256];       // hist[] as it was at the start of the round
@@ -132,7 +134,7 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(const uint64_t* _
   __shared__ uint16_t pre[kGroups][256];         // exclusive prefix of cnt over the (item, wave) pairs (<= kIPT * kBlock)
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t base = (int64_t)blockIdx.x * kTile;
-  uint64_t e[kItems]; uint32_t idx[kItems];
+  uint64_t e[kItems]; uint32_t idx[kPayload ? kItems : 1];
   hist[tid] = 0;
 #pragma unroll
   for (int q = 0; q < kGroups; q++) cnt[q][tid] = 0;
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(const uint64_t* _
   for (int k = 0; k < kItems; k++) {
     const int64_t i = base + (int64_t)k * kBlock + tid;
     e[k] = i < n ? enc_in[i] : 0ull;
-    idx[k] = i < n ? (idx_in ? idx_in[i] : (uint32_t)i) : 0u;
+    if constexpr (kPayload) idx[k] = i < n ? (idx_in ? idx_in[i] : (uint32_t)i) : 0u;
   }
   __syncthreads();
 #pragma unroll
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(const uint64_t* _
       if (!valid[j]) continue;
       const uint32_t pos = round_base[d[j]] + pre[j * kWaves + wave][d[j]] + rank[j];
       s_enc[pos] = e[r * kIPT + j];
-      s_idx[pos] = idx[r * kIPT + j];
+      if constexpr (kPayload) s_idx[pos] = idx[r * kIPT + j];
     }
     // no third barrier: the next round's leaders write cnt (already zeroed); pre / round_base are rewritten only after the next
     // round's first barrier, which every lane reaches after the reads above
@@ -206,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(const uint64_t* _
     const uint64_t ev = s_enc[p];
     const uint64_t out = gbase[(int)((ev >> shift) & 255)] + (uint64_t)p;
     enc_out[out] = ev;
-    idx_out[out] = s_idx[p];
+    if constexpr (kPayload) idx_out[out] = s_idx[p];
   }
 }
 
@@ -282,6 +284,7 @@ static KeyCol key_col(const ColumnPtr& c) { KeyCol kc; kc.values = c->data(); kc
 
 struct Work {
   int64_t m = 0;                 // rows being sorted
+  bool keys_only = false;        // sort_keys_u64: enc[] is the whole record, no permutation travels with it
   Buf enc[2], idx[2];            // ping-pong buffers
   int cur = 0;                   // idx[cur] holds the current permutation (when have_perm)
   bool have_perm = false;        // false: identity
@@ -306,9 +309,18 @@ static void radix_pass(Work& w, int shift) {
     PLX_HIP(hipGetLastError());
   }
   k::exclusive_scan_u32(w.block_hist->as<uint32_t>(), w.offsets->as<uint64_t>(), (int64_t)w.nblocks * 256);
+  if (w.keys_only) {
+    ProfileScope ps("sort_radix_scatter_keys", (uint64_t)m * 16, (uint64_t)m);
+    hipLaunchKernelGGL(radix_scatter_kernel<false>, dim3(w.nblocks), dim3(kBlock), 0, stream(), w.enc[w.cur]->as<uint64_t>(), (const uint32_t*)nullptr, m, shift, w.offsets->as<uint64_t>(),
+                       w.nblocks, w.enc[w.cur ^ 1]->as<uint64_t>(), (uint32_t*)nullptr);
+    PLX_HIP(hipGetLastError());
+    w.cur ^= 1;
+    w.passes++;
+    return;
+  }
   {
     ProfileScope ps("sort_radix_scatter", (uint64_t)m * 24, (uint64_t)m);
-    hipLaunchKernelGGL(radix_scatter_kernel, dim3(w.nblocks), dim3(kBlock), 0, stream(), w.enc[w.cur]->as<uint64_t>(),
+    hipLaunchKernelGGL(radix_scatter_kernel<true>, dim3(w.nblocks), dim3(kBlock), 0, stream(), w.enc[w.cur]->as<uint64_t>(),
                        w.have_perm ? w.idx[w.cur]->as<uint32_t>() : (const uint32_t*)nullptr, m, shift, w.offsets->as<uint64_t>(), w.nblocks,
                        w.enc[w.cur ^ 1]->as<uint64_t>(), w.idx[w.cur ^ 1]->as<uint32_t>());
     PLX_HIP(hipGetLastError());
@@ -318,14 +330,14 @@ static void radix_pass(Work& w, int shift) {
   w.passes++;
 }
 
-// stable sort of the current permutation by the digits of enc[cur] on which rows differ (max_digits least significant digits)
-static void sort_encoded(Work& w, int max_digits) {
+// stable sort of the current permutation by the digits of enc[cur] on which rows differ (digits first_digit .. max_digits - 1, least significant first)
+static void sort_encoded(Work& w, int max_digits, int first_digit = 0) {
   PLX_HIP(hipMemsetAsync(w.hist->ptr, 0, 8 * 256 * sizeof(unsigned int), stream()));
   hipLaunchKernelGGL(digit_hist_kernel, dim3(k::grid_for(w.m, kBlock * 8, 4)), dim3(kBlock), 0, stream(), w.enc[w.cur]->as<uint64_t>(), w.m, w.hist->as<unsigned int>());
   PLX_HIP(hipGetLastError());
   std::vector<unsigned int> h(8 * 256);
   d2h_sync(h.data(), w.hist->ptr, h.size() * sizeof(unsigned int));
-  for (int d = 0; d < max_digits; d++) {
+  for (int d = first_digit; d < max_digits; d++) {
     bool uniform = false;
     for (int v = 0; v < 256; v++) if ((int64_t)h[d * 256 + v] == w.m) { uniform = true; break; }
     if (uniform) { w.skipped++; continue; }
@@ -358,6 +370,26 @@ static void init_work(Work& w, int64_t m, Buf initial_perm) {
   w.hist = dev_alloc(8 * 256 * sizeof(unsigned int));
   w.block_hist = dev_alloc((size_t)w.nblocks * 256 * sizeof(unsigned int));
   w.offsets = dev_alloc(((size_t)w.nblocks * 256 + 1) * sizeof(uint64_t));
+}
+
+// Key-only stable LSD radix of m 64-bit codes on their digits first_digit .. 7 (sort.hpp): the count / scan / scatter pass of the arg-sort without the permutation.
+Buf sort_keys_u64(Buf keys, int64_t m, int first_digit, int* passes, int* skipped) {
+  PLX_REQUIRE(first_digit >= 0 && first_digit < 8, PLX_ERR_INVALID, "sort_keys_u64: first digit outside 0..7");
+  PLX_REQUIRE(m >= 0 && m < 0xffffffffll, PLX_ERR_UNSUPPORTED, "sort_keys_u64: more keys than u32 IdxSize");
+  if (passes) *passes = 0;
+  if (skipped) *skipped = 0;
+  if (m <= 1) return keys;
+  Work w;
+  w.m = m; w.keys_only = true;
+  w.enc[0] = keys; w.enc[1] = dev_alloc((size_t)m * 8);
+  w.nblocks = (uint32_t)((m + kTile - 1) / kTile);
+  w.hist = dev_alloc(8 * 256 * sizeof(unsigned int));
+  w.block_hist = dev_alloc((size_t)w.nblocks * 256 * sizeof(unsigned int));
+  w.offsets = dev_alloc(((size_t)w.nblocks * 256 + 1) * sizeof(uint64_t));
+  sort_encoded(w, 8, first_digit);
+  if (passes) *passes = w.passes;
+  if (skipped) *skipped = w.skipped;
+  return w.enc[w.cur];
 }
 
 static ColumnPtr make_idx(int64_t n) {

@@ -23,5 +23,10 @@ struct SortKey {
 // PLX_U32 row indices of the first `limit` rows (limit < 0: all rows) of the stable sort by `keys`.
 ColumnPtr sort_indices(const std::vector<SortKey>& keys, int64_t limit, std::string* desc);
 
+// Key-only stable LSD radix sort of m 64-bit codes (a device buffer of m * 8 bytes) by their digits first_digit .. 7, least significant first (first_digit = 4:
+// by the high 32 bits only, rows with equal high halves keep their input order).  Digits on which every key agrees cost no pass.  Returns the buffer that holds the
+// sorted codes (`keys` itself or a scratch buffer of the same size; the other one is released); *passes / *skipped (may be null) = digit passes run / skipped.
+Buf sort_keys_u64(Buf keys, int64_t m, int first_digit, int* passes, int* skipped);
+
 }  // namespace sort
 }  // namespace plx

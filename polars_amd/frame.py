@@ -633,8 +633,8 @@ class DataFrame:
     def group_by(self, *keys, maintain_order: bool = False) -> "GroupBy":
         return GroupBy(self.lazy(), keys, maintain_order, eager=True)
 
-    def join(self, other: "DataFrame", on=None, how: str = "inner", left_on=None, right_on=None, suffix: str = "_right") -> "DataFrame":
-        return self.lazy().join(other.lazy(), on=on, how=how, left_on=left_on, right_on=right_on, suffix=suffix).collect()
+    def join(self, other: "DataFrame", on=None, how: str = "inner", left_on=None, right_on=None, suffix: str = "_right", maintain_order: str = "none") -> "DataFrame":
+        return self.lazy().join(other.lazy(), on=on, how=how, left_on=left_on, right_on=right_on, suffix=suffix, maintain_order=maintain_order).collect()
 
     def sort(self, by, *more_by, descending=False, nulls_last=False, maintain_order: bool = False) -> "DataFrame":
         return self.lazy().sort(by, *more_by, descending=descending, nulls_last=nulls_last, maintain_order=maintain_order).collect()
@@ -777,11 +777,15 @@ class LazyFrame:
     def group_by(self, *keys, maintain_order: bool = False) -> "GroupBy":
         return GroupBy(self, keys, maintain_order)
 
-    def join(self, other: "LazyFrame", on=None, how: str = "inner", left_on=None, right_on=None, suffix: str = "_right") -> "LazyFrame":
+    def join(self, other: "LazyFrame", on=None, how: str = "inner", left_on=None, right_on=None, suffix: str = "_right", maintain_order: str = "none") -> "LazyFrame":
+        """maintain_order (polars JoinArgs.maintain_order): "none" (unspecified row order), "left" (left row order), "left_right" (left, then right row
+        order: a total order), "right", "right_left".  A left join takes none / left / left_right; semi / anti joins return left order whatever is asked."""
+        if maintain_order not in P.JOIN_ORDERS:
+            raise ValueError(f"maintain_order must be one of {list(P.JOIN_ORDERS)}, got {maintain_order!r}")
         if on is not None:
             left_on = right_on = on
         lo, ro = _as_exprs([left_on]), _as_exprs([right_on])
-        return LazyFrame(P.Node("join", left=self._node, right=other._node, left_on=lo, right_on=ro, how=how, suffix=suffix))
+        return LazyFrame(P.Node("join", left=self._node, right=other._node, left_on=lo, right_on=ro, how=how, suffix=suffix, maintain_order=maintain_order))
 
     def sort(self, by, *more_by, descending=False, nulls_last=False, maintain_order: bool = False) -> "LazyFrame":
         """LazyFrame.sort (py-polars lazyframe/frame.py sort): `descending` / `nulls_last` are one flag or one per key.
@@ -896,6 +900,7 @@ class LazyFrame:
         row groups left by statistics / slice / shard -- known before anything is read, no GPU needed)."""
         from . import io as _io
         lines = [F.last_plan()] if F._lib is not None and F.last_plan() else []
+        lines += P.describe_join_orders(self._node)
         if _io.has_file_scan(self._node):
             self._lower()
             lines += _io.describe_scans(self._node)

@@ -27,6 +27,22 @@ class Node:
         self.__dict__.update(kw)
 
 
+# JoinArgs.maintain_order -> plx_join_order (include/polars_amd.h)
+JOIN_ORDERS = {"none": F.JOIN_ORDER_NONE, "left": F.JOIN_ORDER_LEFT, "right": F.JOIN_ORDER_RIGHT, "left_right": F.JOIN_ORDER_LEFT_RIGHT, "right_left": F.JOIN_ORDER_RIGHT_LEFT}
+
+
+def describe_join_orders(node: Node) -> List[str]:
+    """One line per join under `node` that was asked to keep a row order (LazyFrame.explain)."""
+    out: List[str] = []
+    for attr in ("input", "left", "right"):
+        child = getattr(node, attr, None)
+        if isinstance(child, Node):
+            out += describe_join_orders(child)
+    if node.kind == "join" and getattr(node, "maintain_order", "none") != "none":
+        out.append(f"Join[how={node.how}, maintain_order={node.maintain_order}]")
+    return out
+
+
 def sum_dtype(dt: T.DataType) -> T.DataType:
     # sum_output_dtype, crates/polars-core/src/chunked_array/ops/aggregate/mod.rs:55-64
     if dt == T.Boolean:
@@ -317,15 +333,16 @@ class Lowering:
                 lk.append(ai)
                 rk.append(bi)
             how = {"inner": F.JOIN_INNER, "left": F.JOIN_LEFT, "semi": F.JOIN_SEMI, "anti": F.JOIN_ANTI}[n.how]
+            order = JOIN_ORDERS[getattr(n, "maintain_order", "none")]
             if n.how in ("semi", "anti"):   # left columns only (single_keys_semi_anti.rs)
-                return push(kind=F.IR_JOIN, input=li, input_right=ri, keys=lk, keys_right=rk, how=how, suffix=n.suffix), dict(ls)
+                return push(kind=F.IR_JOIN, input=li, input_right=ri, keys=lk, keys_right=rk, how=how, suffix=n.suffix, maintain_order=order), dict(ls)
             out_schema = dict(ls)
             right_key_names = {b.name for a, b in zip(n.left_on, n.right_on) if b.kind == "col" and a.kind == "col"}
             for name, dt in rs.items():
                 if name in right_key_names:
                     continue
                 out_schema[name + n.suffix if name in out_schema else name] = dt
-            return push(kind=F.IR_JOIN, input=li, input_right=ri, keys=lk, keys_right=rk, how=how, suffix=n.suffix), out_schema
+            return push(kind=F.IR_JOIN, input=li, input_right=ri, keys=lk, keys_right=rk, how=how, suffix=n.suffix, maintain_order=order), out_schema
         if k == "sort":
             inp, schema = self.lower_node(n.input)
             keys = [self.lower_expr(e, schema)[0] for e in n.by]
