@@ -1324,6 +1324,18 @@ static void dump_compiled(ProgramDump* dump, const char* kind, const Plan& plan,
                           const std::vector<FinalSpec>& specs, const std::vector<int>& out_exprs, int len_idx, int first_idx, bool maintain_order) {
   if (dump) dump->json = compiled_json(kind, plan, c, kp, agg_nodes, specs, out_exprs, len_idx, first_idx, maintain_order);
 }
+// the plain column behind any aliases of expression `e`, or null when `e` is anything else
+static const AE* plain_column(const Plan& plan, int e) {
+  const AE* x = &plan.ae[e];
+  while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs];
+  return x->kind == PLX_AE_COLUMN ? x : nullptr;
+}
+// conjunction of the predicates `preds` lowered into `c`: its node, or -1 when there is none
+static int and_predicates(Compiler& c, const std::vector<int>& preds) {
+  int p = -1;
+  for (int pe : preds) { int n = c.lower(pe); if (c.nodes[n].ty != 'b') throw Unsupported("predicate is not boolean"); p = p < 0 ? n : c.mk(OP_AND, p, n, 'b'); }
+  return p;
+}
 
 // Select(aggregations) over [Filter]* over `src`
 static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& preds, const FramePtr& src, FramePtr& out, Shape* shape_out, int* sid_out,
@@ -1333,9 +1345,7 @@ static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& pr
   std::vector<int> agg_nodes;
   std::vector<FinalSpec> specs;
   try {
-    int p = -1;
-    for (int pe : preds) { int n = c.lower(pe); if (c.nodes[n].ty != 'b') throw Unsupported("predicate is not boolean"); p = p < 0 ? n : c.mk(OP_AND, p, n, 'b'); }
-    c.pred = p;
+    c.pred = and_predicates(c, preds);
     for (int e : node.exprs) collect_aggs(plan, e, agg_nodes);
     for (int a : agg_nodes) specs.push_back(c.lower_agg(a));
     c.finish();
@@ -1377,9 +1387,7 @@ static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& p
   KeyPlan kp;
   int len_idx = -1, first_idx = -1;
   try {
-    int p = -1;
-    for (int pe : preds) { int n = c.lower(pe); if (c.nodes[n].ty != 'b') throw Unsupported("predicate is not boolean"); p = p < 0 ? n : c.mk(OP_AND, p, n, 'b'); }
-    c.pred = p;
+    c.pred = and_predicates(c, preds);
     kp = lower_keys(c, node.keys);
     len_idx = c.add_agg(AGG_LEN, -1);
     for (int e : node.exprs) collect_aggs(plan, e, agg_nodes);
@@ -1471,9 +1479,8 @@ static int resolve_join_side(const Plan& plan, int node, std::set<std::string> u
   if (plan.ir[n].kind != PLX_IR_JOIN) return no("join inputs are not filtered scans");
   const IRN& j = plan.ir[n];
   if (j.how != PLX_JOIN_INNER || j.keys.size() != 1 || j.keys_right.size() != 1) return no("nested join is not a single-key inner join");
-  auto plain = [&](int e) -> const AE* { const AE* x = &plan.ae[e]; while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs]; return x->kind == PLX_AE_COLUMN ? x : nullptr; };
-  const AE* ka = plain(j.keys[0]);
-  const AE* kb = plain(j.keys_right[0]);
+  const AE* ka = plain_column(plan, j.keys[0]);
+  const AE* kb = plain_column(plan, j.keys_right[0]);
   if (!ka || !kb) return no("nested join keys are expressions");
   std::vector<int> ap, bp;
   const int a = peel_filters(plan, j.input, ap), b = peel_filters(plan, j.input_right, bp);
@@ -1505,6 +1512,238 @@ static bool semi_key_range(const SemiFilter& sf, int64_t* mn, int64_t* mx) {
   return true;
 }
 
+// ------------------------------------------------ the stages the fused join pipelines share ----
+// fused_join_groupby, fused_join_frame and fused_semi_anti_frame (below) resolve their sides, name the joined columns and build their tables here.  The
+// structs that hold a table own its device buffers: the table's raw pointers live exactly as long as the struct.
+namespace {
+
+// PLX_JOIN_TRACE=1 (debugging aid): every stage of the hash-table pipeline announced on stderr behind a stream synchronisation -- a stage that hangs is the last one named
+static const bool jtrace = getenv("PLX_JOIN_TRACE") && getenv("PLX_JOIN_TRACE")[0] == '1';
+#define JTRACE(...) do { if (jtrace) { PLX_HIP(hipStreamSynchronize(stream())); fprintf(stderr, "[plx join] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
+
+// The inputs of a join on one plain integer key pair, as written (L, R) and as run (B = build side, P = probe side).
+struct JoinSides {
+  FramePtr L, R, B, P;
+  int lki = -1, rki = -1, bki = -1, pki = -1;      // the key column's index in each frame
+  int kdt = 0;                                     // its dtype (the same on both sides)
+  bool build_right = false;
+  std::vector<int> bpreds, ppreds;                 // the predicates of the build / probe side
+};
+// false + *why: the pipelines do not take this pair of inputs
+static bool resolve_join_sides(JoinSides& s, const FramePtr& L, const FramePtr& R, const AE* lkx, const AE* rkx, bool left_join, const std::vector<int>& lpreds, const std::vector<int>& rpreds,
+                               const char** why) {
+  s.L = L; s.R = R;
+  s.lki = L->find(lkx->name); s.rki = R->find(rkx->name);
+  if (s.lki < 0 || s.rki < 0) { *why = "join key column not found"; return false; }
+  s.kdt = L->cols[s.lki]->dtype;
+  if (s.kdt != R->cols[s.rki]->dtype || !dtype_is_int(s.kdt)) { *why = "join key is not an integer column pair of one dtype"; return false; }
+  if (L->height >= 0xffffffffll || R->height >= 0xffffffffll) { *why = "side exceeds u32 row indices"; return false; }
+  s.build_right = left_join || L->height > R->height;   // det_hash_prone_order (hash_join/mod.rs:41-50): probe = the longer relation; a left join probes with its left table (single_keys_left.rs)
+  s.B = s.build_right ? R : L; s.P = s.build_right ? L : R;
+  s.bki = s.build_right ? s.rki : s.lki; s.pki = s.build_right ? s.lki : s.rki;
+  s.bpreds = s.build_right ? rpreds : lpreds; s.ppreds = s.build_right ? lpreds : rpreds;
+  return true;
+}
+
+// Columns of the joined frame (_finish_join, general.rs:17-49): left columns, then right columns except the coalesced right key; a right name that clashes gets the suffix.
+struct JoinedCol { std::string name; int side; int idx; };     // side 0 = left, 1 = right; idx = the column's index in that side's frame
+static bool joined_columns(const Frame& L, const Frame& R, int rki, const std::string& suffix, std::vector<JoinedCol>& outs, const char** why) {
+  std::set<std::string> seen;
+  for (size_t i = 0; i < L.names.size(); i++) { outs.push_back({L.names[i], 0, (int)i}); seen.insert(L.names[i]); }
+  for (size_t i = 0; i < R.names.size(); i++) {
+    if ((int)i == rki) continue;
+    std::string name = R.names[i];
+    if (seen.count(name)) name += suffix;
+    if (seen.count(name)) { *why = "duplicate output column name"; return false; }
+    seen.insert(name);
+    outs.push_back({name, 1, (int)i});
+  }
+  return true;
+}
+
+// Membership bitmap over the key range [kmin, kmin + range): one fused scan of a side sets bit (key - kmin) of every row that passes its predicate and counts those rows
+// (BitmapBuildSink); the other side's program tests it with OP_BITLOOKUP.
+struct MemberBitmap {
+  Buf bits, rows_dev;
+  int64_t kmin = 0;
+  uint64_t range = 1;
+  // Can a bitmap cover the keys [mn, mx] of a side of `height` rows?  At most 2^34 keys and 256 per row (+ 4096).  !have (an empty side, no statistics): one bit that nobody sets.
+  bool cover(bool have, int64_t mn, int64_t mx, int64_t height) {
+    const unsigned __int128 range128 = have ? (unsigned __int128)((__int128)mx - (__int128)mn) + 1 : 1;
+    if (range128 > ((unsigned __int128)1 << 34) || (have && range128 > (unsigned __int128)height * 256 + 4096)) return false;
+    kmin = mn; range = (uint64_t)range128;
+    return true;
+  }
+  // the empty bitmap; given the side's program (its key = the key column) also the scan that fills it
+  void build(const Compiler* c) {
+    bits = dev_alloc_zero(sizeof(uint64_t) * (size_t)(range / 64 + 2)); rows_dev = dev_alloc_zero(8);
+    if (!c) return;
+    BitmapBuild bb; bb.bits = bits->as<unsigned long long>(); bb.count = rows_dev->as<unsigned long long>(); bb.kmin = kmin; bb.range = range;
+    k::fused_bitmap_build(c->shape, c->args, bb, find_static_shape(c->shape));
+  }
+  uint64_t rows_in() const { uint64_t n = 0; d2h_sync(&n, rows_dev->ptr, 8); return n; }       // (synchronises)
+  Lut lut() const { return Lut{bits->as<unsigned long long>(), range}; }
+};
+
+// Direct-address table for build keys with a small range (cached column statistics): a bitmap over the key range + a rank per word + the {key, row} pairs the build scan
+// appended, by ordinal.  Needs no count pass.  The caller sets dt.opts before try_build and dt.acc after it.
+struct DirectBuild {
+  enum Result { kNotEligible, kBuilt, kDuplicateKeys };
+  Buf bits, rank, okey, orow, used;
+  Buf meta;                      // [0] ordinal counter, [2..3] flags, [4..5] pairs appended (u64)
+  DirectJoinTable dt{};
+  uint64_t range = 0, ord_cap = 0;
+  uint64_t nb = 0;               // build rows that passed = slots (unique keys)
+  int64_t n_ord = 0;             // ordinals the build scan handed out (live pairs and the unused rest of every wave's last chunk)
+  Result try_build(const Plan& plan, const Compiler& cb, const Frame& B, int bki, bool known_dups) {
+    int64_t kmn = 0, kmx = 0;
+    if ((plan.flags & PLX_PLAN_NO_DIRECT_JOIN) || known_dups || B.height <= 0 || B.cols[bki]->dtype == PLX_U64 || !ops::int_range(B.cols[bki], &kmn, &kmx)) return kNotEligible;
+    const unsigned __int128 range128 = (unsigned __int128)((__int128)kmx - (__int128)kmn) + 1;
+    // pair list capacity: every build row may pass + one ordinal chunk (1024, kOrdChunk) per wave
+    ord_cap = (uint64_t)B.height + (uint64_t)k::scan_waves(B.height) * 1024 + 1024;
+    if (range128 > ((unsigned __int128)1 << 34) || range128 > (unsigned __int128)B.height * 256 || ord_cap >= 0xfffffff0ull) return kNotEligible;
+    range = (uint64_t)range128;
+    const size_t n_blocks = (size_t)(range / 512 + 1), n_words = n_blocks * 8;
+    bits = dev_alloc_zero(sizeof(uint64_t) * n_words); rank = dev_alloc(sizeof(uint32_t) * n_words);
+    okey = dev_alloc(sizeof(uint64_t) * ord_cap); orow = dev_alloc(sizeof(uint32_t) * ord_cap); used = dev_alloc_zero(sizeof(uint32_t) * (ord_cap / 1024 + 2));
+    meta = dev_alloc_zero(32);
+    dt.bits = bits->as<unsigned long long>(); dt.rank = rank->as<unsigned int>(); dt.ord_key = okey->as<unsigned long long>(); dt.ord_row = orow->as<unsigned int>();
+    dt.chunk_used = used->as<unsigned int>(); dt.counter = meta->as<unsigned int>(); dt.flags = meta->as<unsigned int>() + 2; dt.acc = nullptr; dt.kmin = kmn; dt.range = range; dt.n_ord = (unsigned int)ord_cap;
+    k::fused_direct_build(cb.shape, cb.args, dt, find_static_shape(cb.shape));
+    // every wave closes its last chunk when it finishes, so chunk_used is final once the build scan is: the rank launch counts
+    // the pairs over the whole reserved capacity (the ordinal counter itself is only read back with the rank's sync)
+    uint64_t pairs = 0;
+    nb = k::direct_rank(dt, rank->as<uint32_t>(), (int64_t)ord_cap, meta->as<uint64_t>() + 2, &pairs);   // synchronises: flags and the ordinal counter are final too
+    uint32_t m4[4] = {0, 0, 0, 0};
+    d2h_sync(m4, meta->ptr, 16);
+    PLX_REQUIRE(!m4[3], PLX_ERR_INVALID, "direct join build: ordinal overflow");
+    if (pairs != nb) return kDuplicateKeys;                        // two pairs shared a bit: the hash-table pipeline runs such keys (chains of rows)
+    n_ord = (int64_t)std::min<uint64_t>(m4[0], ord_cap);
+    return kBuilt;
+  }
+};
+
+// Hash table of the build side: 16-byte {key, row} slots filled by the build scan `cb` (its predicate fused; k::fused_join_build, or window by window from LDS:
+// k::partitioned_join_build), chains of rows per key (`links`) when the build keys repeat.
+struct HashBuildOptions {
+  int min_log2_cap;          // smallest table (the plan text prints cap=2^N)
+  bool start_chained;        // the build keys are known to repeat: chains from the first attempt
+  bool chains_allowed;       // false: run() gives up on duplicate build keys
+  bool want_cells;           // a windowed build also lists its keys and rows by key number (k::JoinCells)
+  const char* plain_how;     // build_how of a build that was not windowed
+};
+struct HashBuild {
+  Buf keys, flags, links;
+  JoinAggTable t{};
+  k::JoinCells cells;
+  int log2_cap = 4;
+  uint64_t cap = 0;
+  uint64_t nb = 0;           // build rows in the table
+  bool multi = false;        // multi-value mode (chains)
+  std::string build_how;
+  // `cnt` counts the rows `cb` inserts.  false: the build keys repeat and chains are not allowed (the column remembers that its keys repeat: repeats_as_build_key).
+  bool run(const Compiler& cnt, const Compiler& cb, const Frame& B, int bki, const HashBuildOptions& o) {
+    // Size of the build table.  The number of build rows that pass the build side's predicate is a by-product of the build scan itself (JoinBuildSink counts what
+    // it inserts), so a large build side is sized from a strided sample of the count program (4 blocks of 2^18 rows, + 25 %) instead of a counting pass over the
+    // whole side; if the sample misjudged (table more than 0.7 full, or a probe sequence overflowed) the table is rebuilt once from the exact count.
+    auto exact_count = [&]() -> uint64_t { std::vector<uint64_t> host(kMaxAggs, 0); k::fused_regagg(cnt.shape, cnt.args, find_static_shape(cnt.shape), host.data()); return host[0]; };
+    bool sized_by_sample = false;
+    if (B.height > 0) {
+      static const bool no_sample = getenv("PLX_JOIN_COUNT_SAMPLE") && getenv("PLX_JOIN_COUNT_SAMPLE")[0] == '0';
+      if (B.height >= ((int64_t)1 << 24) && !no_sample) {
+        constexpr int kCountBlocks = 4;                  // every block is a launch + a host round trip (~40 us)
+        const int64_t per = (int64_t)1 << 18, stride = (B.height / kCountBlocks) & ~(int64_t)127;
+        uint64_t hits = 0, seen = 0;
+        for (int b = 0; b < kCountBlocks; b++) {
+          const int64_t row0 = (int64_t)b * stride, rows_b = std::min<int64_t>(per, B.height - row0);
+          if (rows_b <= 0) continue;
+          std::vector<uint64_t> host(kMaxAggs, 0);
+          k::fused_regagg(cnt.shape, offset_args(cnt.shape, cnt.args, row0, rows_b), -1, host.data());
+          hits += host[0]; seen += (uint64_t)rows_b;
+        }
+        nb = (uint64_t)((double)hits / (double)std::max<uint64_t>(seen, 1) * (double)B.height * 1.25) + 4096;
+        sized_by_sample = true;
+      } else nb = exact_count();
+    }
+    const ColumnPtr& bkey = B.cols[bki];
+    if (o.start_chained) { bkey->repeats_as_build_key = true; if (!o.chains_allowed) return false; multi = true; }
+    bool resized = false, pbuild_off = false;
+    for (int attempt = 0; attempt < 4; attempt++) {
+      if (multi && !links) links = dev_alloc(sizeof(uint64_t) * (size_t)std::max<int64_t>(B.height, 1));
+      // (the sampled count already carries 25 %: x1.6 keeps the load at or below ~0.6 without doubling a table that x2 would push over the next power of two)
+      log2_cap = std::max(o.min_log2_cap, ceil_log2_u64((uint64_t)((double)std::max<uint64_t>(nb, 1) * (sized_by_sample ? 1.6 : 2.0))));
+      cap = 1ull << log2_cap;
+      keys = dev_alloc(sizeof(uint64_t) * 2 * (cap + 1)); flags = dev_alloc_zero(32);       // {key, row} slots: kEmptyKey and kNoRow32 are both all-ones
+      t.slots = keys->as<unsigned long long>(); t.flags = flags->as<unsigned int>(); t.acc = nullptr;
+      t.count = flags->as<unsigned long long>() + 1; t.log2_cap = (uint32_t)log2_cap;
+      t.links = multi ? links->as<unsigned long long>() : nullptr;
+      JTRACE("build attempt %d multi=%d cap=2^%d nb=%llu", attempt, (int)multi, log2_cap, (unsigned long long)nb);
+      // a large build side with (so far) unique keys: partitioned, the table filled window by window from LDS -- no device atomic per row (k::partitioned_join_build)
+      t.log2_window = 0;
+      build_how = o.plain_how;
+      bool pbuilt = false;
+      if (!multi && !pbuild_off && partitioned_build_wanted(B.height, log2_cap)) {
+        t.log2_window = kJoinWindowLog2;
+        std::string bd;
+        pbuilt = k::partitioned_join_build(cb.shape, cb.args, find_static_shape(cb.shape), t, o.want_cells ? &cells : nullptr, &bd);
+        if (pbuilt) build_how = bd; else t.log2_window = 0;
+      }
+      if (!pbuilt) {
+        PLX_HIP(hipMemsetAsync(keys->ptr, 0xff, sizeof(uint64_t) * 2 * (cap + 1), stream()));
+        k::fused_join_build(cb.shape, cb.args, t, find_static_shape(cb.shape));
+      }
+      JTRACE("build done");
+      uint64_t fl64[2] = {0, 0};
+      d2h_sync(fl64, flags->ptr, 16);
+      const uint32_t dup = (uint32_t)fl64[0], ovf = (uint32_t)(fl64[0] >> 32);
+      if (dup) {                                       // (raised by a build without links only: JoinBuildSink)
+        bkey->repeats_as_build_key = true;
+        if (!o.chains_allowed) return false;
+        multi = true;                                  // build once more, chaining the rows of a key (the table's size stays: it was planned for the rows, not the keys)
+        continue;
+      }
+      // the sample misjudged (on whichever attempt: the multi-value rebuild keeps the sampled size): once more, from the exact count.  (A table sized from an exact count
+      // is at most half full: only a sampled size can be over 0.7.)
+      if (!resized && (ovf || (sized_by_sample && fl64[1] * 10 > cap * 7))) {
+        nb = ovf ? exact_count() : fl64[1];
+        sized_by_sample = false; resized = true;
+        continue;
+      }
+      if (ovf && pbuilt) { pbuild_off = true; continue; }                             // a window filled up although the table is sized right (keys that crowd one window): the plain build probes the whole table
+      PLX_REQUIRE(!ovf, PLX_ERR_OOM, "join build: probe sequence overflow");
+      nb = fl64[1];                                                                   // exact from here on
+      break;
+    }
+    return true;
+  }
+};
+
+// Which probes are partitioned first (PLX_PROBE_PARTITIONED: 0 = none, 2 = all).  Direct-address table: worth it when the bitmap is far larger than an L2 (4 MB), few
+// rows can match and the probe keys come in no order (sampled once per column).
+static bool partition_direct_probe(int pmode, const Frame& P, int pki, uint64_t range, uint64_t nb) {
+  if (!(pmode == 2 || (pmode == 1 && P.height >= ((int64_t)1 << 24) && range >= ((uint64_t)1 << 28) && nb * 8 <= range))) return false;
+  const ColumnPtr& pk = P.cols[pki];
+  if (pk->order_state == 0) pk->order_state = k::sample_sortedness(pk) >= 0.9 ? 1 : 2;
+  return pmode == 2 || pk->order_state == 2;
+}
+// Hash table: a table beyond the caches (64 MB) probed by a much longer relation.
+static bool partition_hash_probe(int pmode, const Frame& P, uint64_t cap, uint64_t nb) {
+  return pmode == 2 || (pmode == 1 && P.height >= ((int64_t)1 << 24) && (cap + 1) * 16 > ((uint64_t)64 << 20) && nb * 16 <= (uint64_t)P.height);
+}
+// Runs the probe program `cp` over the candidate rows `hits` only: its input columns gathered at them, `launch(args)` is the probe kernel.  Returns the gathered columns:
+// they live until the caller has synchronised the stream.
+template <class Launch> static std::vector<ColumnPtr> probe_gathered(const Compiler& cp, const ColumnPtr& hits, Launch&& launch) {
+  Args a2 = cp.args;
+  a2.n_rows = hits->len;
+  std::vector<ColumnPtr> srcs;
+  for (int i = 0; i < cp.shape.n_inputs; i++) srcs.push_back(cp.cols[cp.input_cols[i]]);
+  std::vector<ColumnPtr> keep = ops::gather_columns(srcs, hits);
+  for (int i = 0; i < cp.shape.n_inputs; i++) { a2.in[i].values = keep[i]->data(); a2.in[i].validity = cp.shape.in_nullable[i] ? keep[i]->valid_words() : nullptr; }
+  launch(a2);
+  return keep;
+}
+}  // namespace
+
 static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::string* why, std::vector<Shape>* shapes_out = nullptr, bool compile_only = false) {
   auto no = [&](const char* m) { if (why) *why = m; return false; };
   if (gb.input < 0 || plan.ir[gb.input].kind != PLX_IR_JOIN) return no("input is not a join");
@@ -1516,9 +1755,8 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   // build-side group columns.  Needs a build key range a bitmap can cover; otherwise the per-node path runs the join.
   const bool left_join = jn.how == PLX_JOIN_LEFT;
   if (gb.maintain_order) return no("maintain_order");
-  auto plain = [&](int e) -> const AE* { const AE* x = &plan.ae[e]; while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs]; return x->kind == PLX_AE_COLUMN ? x : nullptr; };
-  const AE* lkx = plain(jn.keys[0]);
-  const AE* rkx = plain(jn.keys_right[0]);
+  const AE* lkx = plain_column(plan, jn.keys[0]);
+  const AE* rkx = plain_column(plan, jn.keys_right[0]);
   if (!lkx || !rkx) return no("join keys are expressions");
   std::vector<int> lpreds, rpreds;
   std::vector<SemiFilter> lsemis, rsemis;
@@ -1531,42 +1769,30 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   const int rsrc = resolve_join_side(plan, jn.input_right, used, rpreds, rsemis, why);
   if (rsrc < 0) return false;
   if (lsemis.size() + rsemis.size() > (size_t)kMaxLuts) return no("more nested filter joins than lookup bitmaps");
-  FramePtr L = get_frame(plan.ir[lsrc].frame), R = get_frame(plan.ir[rsrc].frame);
-  const int lki = L->find(lkx->name), rki = R->find(rkx->name);
-  if (lki < 0 || rki < 0) return no("join key column not found");
-  const int kdt = L->cols[lki]->dtype;
-  if (kdt != R->cols[rki]->dtype || !dtype_is_int(kdt)) return no("join key is not an integer column pair of one dtype");
-  if (L->height >= 0xffffffffll || R->height >= 0xffffffffll) return no("side exceeds u32 row indices");
-  const bool build_right = left_join || L->height > R->height;   // det_hash_prone_order: probe = the longer relation; a left join probes with its left table (single_keys_left.rs)
-  const FramePtr& B = build_right ? R : L;
-  const FramePtr& P = build_right ? L : R;
-  const int bki = build_right ? rki : lki, pki = build_right ? lki : rki;
-  const std::vector<int>& bpreds = build_right ? rpreds : lpreds;
-  const std::vector<int>& ppreds = build_right ? lpreds : rpreds;
+  JoinSides sides;
+  const char* bad = nullptr;
+  if (!resolve_join_sides(sides, get_frame(plan.ir[lsrc].frame), get_frame(plan.ir[rsrc].frame), lkx, rkx, left_join, lpreds, rpreds, &bad)) return no(bad);
+  const FramePtr &B = sides.B, &P = sides.P;
+  const int lki = sides.lki, bki = sides.bki, pki = sides.pki, kdt = sides.kdt;
+  const bool build_right = sides.build_right;
+  const std::vector<int> &bpreds = sides.bpreds, &ppreds = sides.ppreds;
   const std::vector<SemiFilter>& bsemis = build_right ? rsemis : lsemis;
   const std::vector<SemiFilter>& psemis = build_right ? lsemis : rsemis;
-  // joined-frame naming (_finish_join, general.rs:17-49): left columns, then right columns except the coalesced right key
-  struct Src { int side; int idx; };   // side 0 = left, 1 = right
-  std::map<std::string, Src> joined;
-  for (size_t i = 0; i < L->names.size(); i++) joined[L->names[i]] = {0, (int)i};
-  for (size_t i = 0; i < R->names.size(); i++) {
-    if ((int)i == rki) continue;
-    std::string name = R->names[i];
-    if (joined.count(name)) name += jn.suffix;
-    if (joined.count(name)) return no("duplicate output column name");
-    joined[name] = {1, (int)i};
-  }
+  std::vector<JoinedCol> jcols;
+  if (!joined_columns(*sides.L, *sides.R, sides.rki, jn.suffix, jcols, &bad)) return no(bad);
+  std::map<std::string, const JoinedCol*> joined;      // by name
+  for (const JoinedCol& jc : jcols) joined[jc.name] = &jc;
   const int build_side = build_right ? 1 : 0;
   // group keys
   struct GKey { bool is_join_key; int build_col; int expr; int dtype; };
   std::vector<GKey> gkeys;
   bool has_join_key = false;
   for (int e : gb.keys) {
-    const AE* x = plain(e);
+    const AE* x = plain_column(plan, e);
     if (!x) return no("group key is an expression");
     auto it = joined.find(x->name);
     if (it == joined.end()) fail(PLX_ERR_NOT_FOUND, "column not found: " + x->name);
-    const Src sc = it->second;
+    const JoinedCol& sc = *it->second;
     const bool is_key = (sc.side == 0 && sc.idx == lki);   // the coalesced key column carries the left name
     if (is_key) { has_join_key = true; gkeys.push_back({true, -1, e, kdt}); }
     else if (sc.side == build_side) gkeys.push_back({false, sc.idx, e, B->cols[sc.idx]->dtype});
@@ -1575,7 +1801,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   if (!has_join_key) return no("group keys do not include the join key");
   // aggregates: probe-side columns only, resolved through the joined names
   Frame pview; pview.height = P->height;
-  for (auto& kv : joined) if (kv.second.side != build_side) { pview.names.push_back(kv.first); pview.cols.push_back(P->cols[kv.second.idx]); }
+  for (auto& kv : joined) if (kv.second->side != build_side) { pview.names.push_back(kv.first); pview.cols.push_back(P->cols[kv.second->idx]); }
   if (!build_right) { pview.names.push_back(lkx->name); pview.cols.push_back(P->cols[pki]); }  // coalesced key: probe values == build values on matches
   std::function<bool(int)> probe_only = [&](int e) -> bool {
     if (e < 0) return true;
@@ -1592,17 +1818,15 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   KeyPlan akp;
   std::vector<FinalSpec> aspecs;
   int a_len_idx = -1;
-  int64_t a_kmn = 0, a_kmx = 0;
-  uint64_t a_range = 0;
+  MemberBitmap unmatched_keys;                                  // left join: the build keys that pass the build side's predicate
   if (left_join) {
     if (psemis.size() + 1 > (size_t)kMaxLuts) return no("left join: no lookup bitmap left for the membership test");
     if (kdt == PLX_U64) return no("left join on UInt64 keys");
+    int64_t a_kmn = 0, a_kmx = 0;
     bool have = false;                                          // (a placeholder column -- compile-only callers -- has its declared range or none)
     if (B->height > 0 && B->cols[bki]->values) have = ops::int_range(B->cols[bki], &a_kmn, &a_kmx);
     else if (B->height > 0 && B->cols[bki]->range_state == 1) { a_kmn = B->cols[bki]->range_min; a_kmx = B->cols[bki]->range_max; have = true; }
-    const unsigned __int128 range128 = have ? (unsigned __int128)((__int128)a_kmx - (__int128)a_kmn) + 1 : 1;
-    if (range128 > ((unsigned __int128)1 << 34) || (have && range128 > (unsigned __int128)B->height * 256 + 4096)) return no("left join: build key range too wide for the membership bitmap");
-    a_range = (uint64_t)range128;
+    if (!unmatched_keys.cover(have, a_kmn, a_kmx, B->height)) return no("left join: build key range too wide for the membership bitmap");
   }
   std::vector<std::unique_ptr<Compiler>> csemi;      // one program per semi filter: build-side filters first, then probe-side
   std::vector<int> agg_nodes; std::vector<FinalSpec> specs;
@@ -1610,8 +1834,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   try {
     // conjunction of the side's predicates and of the membership tests of its semi filters (lookup bitmap i = args.lut[lut0 + i])
     auto and_preds = [&](Compiler& c, const std::vector<int>& preds, const std::vector<SemiFilter>& semis, int lut0) {
-      int p = -1;
-      for (int pe : preds) { int n = c.lower(pe); if (c.nodes[n].ty != 'b') throw Unsupported("predicate is not boolean"); p = p < 0 ? n : c.mk(OP_AND, p, n, 'b'); }
+      int p = and_predicates(c, preds);
       for (size_t i = 0; i < semis.size(); i++) {
         int64_t mn = 0, mx = 0;
         if (!semi_key_range(semis[i], &mn, &mx)) mn = mx = 0;      // empty filter side: the bitmap is empty, nothing matches
@@ -1646,7 +1869,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
       ca.df = &pview;
       int p = and_preds(ca, ppreds, psemis, 0);                                  // (its own lookup numbering: the probe side's semi filters, then the membership bitmap)
       const int kn = ca.load(pki);
-      const int member = ca.ifnull(ca.bit_lookup(p < 0 ? kn : ca.mask_valid(kn, p), (int)psemis.size(), a_kmn), 0);      // a null key is among nobody's keys
+      const int member = ca.ifnull(ca.bit_lookup(p < 0 ? kn : ca.mask_valid(kn, p), (int)psemis.size(), unmatched_keys.kmin), 0);      // a null key is among nobody's keys
       const int unmatched = ca.mk(OP_NOT, member, member, 'b');
       ca.pred = p < 0 ? unmatched : ca.mk(OP_AND, p, unmatched, 'b');
       int jk_expr = -1;
@@ -1690,7 +1913,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
       }
       o << "]";
       // a left join's unmatched rows: a group-by program over the probe side whose predicate ends in NOT member(key) -- lookup bitmap `lut` = the build keys that pass the build program
-      if (left_join) o << ",\"unmatched\":{\"lut\":" << psemis.size() << ",\"kmin\":\"" << a_kmn << "\",\"range\":\"" << a_range << "\",\"program\":"
+      if (left_join) o << ",\"unmatched\":{\"lut\":" << psemis.size() << ",\"kmin\":\"" << unmatched_keys.kmin << "\",\"range\":\"" << unmatched_keys.range << "\",\"program\":"
                        << compiled_json("group_by", plan, ca, &akp, agg_nodes, aspecs, gb.exprs, a_len_idx, -1, false) << "}";
       o << "}";
       t_program_dump->json = o.str();
@@ -1700,7 +1923,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   // ---- run
   // semi filters first: one fused scan of each filter side -> membership bitmap; its set bits must equal the rows that passed
   // (unique filter keys), otherwise the nested join multiplies rows and the per-node path has to run it
-  std::vector<Buf> lut_bits;
+  std::vector<MemberBitmap> semi_bits(csemi.size());
   {
     size_t ci = 0;
     for (int side = 0; side < 2; side++) {
@@ -1709,23 +1932,17 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
         const SemiFilter& sf = sv[i];
         int64_t mn = 0, mx = 0;
         const bool have = sf.F->height > 0 && semi_key_range(sf, &mn, &mx);
-        const unsigned __int128 range128 = have ? (unsigned __int128)((__int128)mx - (__int128)mn) + 1 : 1;
-        if (range128 > ((unsigned __int128)1 << 34) || (have && range128 > (unsigned __int128)sf.F->height * 256 + 4096)) return no("nested filter join: key range too wide for a bitmap");
-        const uint64_t range = (uint64_t)range128;
-        Buf bits = dev_alloc_zero(sizeof(uint64_t) * (size_t)(range / 64 + 2)), rows_dev = dev_alloc_zero(8);
+        MemberBitmap& mb = semi_bits[ci];
+        if (!mb.cover(have, mn, mx, sf.F->height)) return no("nested filter join: key range too wide for a bitmap");
+        mb.build(have ? csemi[ci].get() : nullptr);
         if (have) {
-          BitmapBuild bb; bb.bits = bits->as<unsigned long long>(); bb.count = rows_dev->as<unsigned long long>(); bb.kmin = mn; bb.range = range;
-          Compiler& cf = *csemi[ci];
-          k::fused_bitmap_build(cf.shape, cf.args, bb, find_static_shape(cf.shape));
-          uint64_t rows_in = 0;
-          d2h_sync(&rows_in, rows_dev->ptr, 8);
-          if ((uint64_t)k::bitmap_popcount(bits->as<uint64_t>(), (int64_t)range) != rows_in) return no("nested filter join: the filter side's keys are not unique");
-          plan.desc += "SemiFilter{" + sf.F->names[sf.fkey] + " -> bitmap range=" + std::to_string(range) + " rows=" + std::to_string(rows_in) + "/" + std::to_string(sf.F->height) + "}; ";
+          const uint64_t rows_in = mb.rows_in();
+          if ((uint64_t)k::bitmap_popcount(mb.bits->as<uint64_t>(), (int64_t)mb.range) != rows_in) return no("nested filter join: the filter side's keys are not unique");
+          plan.desc += "SemiFilter{" + sf.F->names[sf.fkey] + " -> bitmap range=" + std::to_string(mb.range) + " rows=" + std::to_string(rows_in) + "/" + std::to_string(sf.F->height) + "}; ";
         }
-        const Lut lut{bits->as<unsigned long long>(), range};
+        const Lut lut = mb.lut();
         const int li = side == 0 ? (int)i : (int)(bsemis.size() + i);
         if (side == 0) { cnt.args.lut[li] = lut; cb.args.lut[li] = lut; } else { cp.args.lut[li] = lut; cs.args.lut[li] = lut; if (left_join) ca.args.lut[i] = lut; }
-        lut_bits.push_back(bits);
       }
     }
   }
@@ -1751,31 +1968,15 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   int64_t G = 0;
   bool done = false;
   // -- direct-address table when the build key range is small (cached column statistics); needs no count pass
-  int64_t kmn = 0, kmx = 0;
-  if (!(plan.flags & PLX_PLAN_NO_DIRECT_JOIN) && !known_dups && B->height > 0 && kdt != PLX_U64 && ops::int_range(B->cols[bki], &kmn, &kmx)) {
-    const unsigned __int128 range128 = (unsigned __int128)((__int128)kmx - (__int128)kmn) + 1;
-    // pair list capacity: every build row may pass + one ordinal chunk (1024, kOrdChunk) per wave
-    const uint64_t ord_cap = (uint64_t)B->height + (uint64_t)k::scan_waves(B->height) * 1024 + 1024;
-    if (range128 <= ((unsigned __int128)1 << 34) && range128 <= (unsigned __int128)B->height * 256 && ord_cap < 0xfffffff0ull) {
-      const uint64_t range = (uint64_t)range128;
-      const size_t n_blocks = (size_t)(range / 512 + 1), n_words = n_blocks * 8;
-      Buf bits = dev_alloc_zero(sizeof(uint64_t) * n_words), rank = dev_alloc(sizeof(uint32_t) * n_words);
-      Buf okey = dev_alloc(sizeof(uint64_t) * ord_cap), orow = dev_alloc(sizeof(uint32_t) * ord_cap), used = dev_alloc_zero(sizeof(uint32_t) * (ord_cap / 1024 + 2));
-      Buf meta = dev_alloc_zero(32);   // [0] ordinal counter, [2..3] flags, [4..5] pairs appended (u64)
-      DirectJoinTable dt{}; dt.bits = bits->as<unsigned long long>(); dt.rank = rank->as<unsigned int>(); dt.ord_key = okey->as<unsigned long long>(); dt.ord_row = orow->as<unsigned int>();
-      dt.chunk_used = used->as<unsigned int>(); dt.counter = meta->as<unsigned int>(); dt.flags = meta->as<unsigned int>() + 2; dt.acc = nullptr; dt.kmin = kmn; dt.range = range; dt.n_ord = (unsigned int)ord_cap;
-      dt.opts = probe_late_loads() ? kDirectLateLoads : 0u;
-      k::fused_direct_build(cb.shape, cb.args, dt, find_static_shape(cb.shape));
-      // every wave closes its last chunk when it finishes, so chunk_used is final once the build scan is: the rank launch counts
-      // the pairs over the whole reserved capacity (the ordinal counter itself is only read back with the rank's sync)
-      uint64_t pairs = 0;
-      nb = k::direct_rank(dt, rank->as<uint32_t>(), (int64_t)ord_cap, meta->as<uint64_t>() + 2, &pairs);   // synchronises: flags and the ordinal counter are final too
-      uint32_t m4[4] = {0, 0, 0, 0};
-      d2h_sync(m4, meta->ptr, 16);
-      PLX_REQUIRE(!m4[3], PLX_ERR_INVALID, "direct join build: ordinal overflow");
-      if (pairs != nb) known_dups = true;                          // two pairs shared a bit: duplicate build keys -- the hash-table pipeline below runs them in multi-value mode
-      else {
-      const uint32_t n_used = m4[0];
+  {
+    DirectBuild direct;
+    direct.dt.opts = probe_late_loads() ? kDirectLateLoads : 0u;
+    const DirectBuild::Result built = direct.try_build(plan, cb, *B, bki, known_dups);
+    if (built == DirectBuild::kDuplicateKeys) known_dups = true;   // the hash-table pipeline below runs them in multi-value mode
+    else if (built == DirectBuild::kBuilt) {
+      DirectJoinTable& dt = direct.dt;
+      const uint64_t range = direct.range;
+      nb = direct.nb;
       const int64_t n_slots = (int64_t)nb, s1 = std::max<int64_t>(n_slots, 1);
       Buf acc2 = dev_alloc(sizeof(uint64_t) * (size_t)s1 * cp.shape.n_aggs);
       k::init_agg_cells(acc2->as<uint64_t>(), s1, cp.shape);   // LEN = 0: build rows no probe row matched never show up
@@ -1786,21 +1987,12 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
       std::string probe_how = "probe_agg";
       bool probed = false;
       Buf touch;
-      const int pmode = partitioned_probe_mode();
-      if (pmode == 2 || (pmode == 1 && P->height >= ((int64_t)1 << 24) && range >= ((uint64_t)1 << 28) && nb * 8 <= range)) {
-        const ColumnPtr& pk = P->cols[pki];
-        if (pk->order_state == 0) pk->order_state = k::sample_sortedness(pk) >= 0.9 ? 1 : 2;
+      if (partition_direct_probe(partitioned_probe_mode(), *P, pki, range, nb)) {
         ColumnPtr hits;
         std::string pd;
-        if ((pmode == 2 || pk->order_state == 2) && k::partitioned_probe_hits(cs.shape, cs.args, dt, nb, find_static_shape(cs.shape), &hits, &pd)) {
+        if (k::partitioned_probe_hits(cs.shape, cs.args, dt, nb, find_static_shape(cs.shape), &hits, &pd)) {
           if (hits->len > 0) {
-            Args a2 = cp.args;
-            a2.n_rows = hits->len;
-            std::vector<ColumnPtr> srcs;
-            for (int i = 0; i < cp.shape.n_inputs; i++) srcs.push_back(cp.cols[cp.input_cols[i]]);
-            std::vector<ColumnPtr> keep = ops::gather_columns(srcs, hits);
-            for (int i = 0; i < cp.shape.n_inputs; i++) { a2.in[i].values = keep[i]->data(); a2.in[i].validity = cp.shape.in_nullable[i] ? keep[i]->valid_words() : nullptr; }
-            k::fused_direct_probe_agg(cp.shape, a2, dt, probe_static_id);
+            std::vector<ColumnPtr> keep = probe_gathered(cp, hits, [&](const Args& a2) { k::fused_direct_probe_agg(cp.shape, a2, dt, probe_static_id); });
             // the pair-list compaction below looks every build pair up in bitmap, rank and LEN cells -- random lines for a shuffled build side.  Only keys
             // among the candidates can have been matched: a 2^26-bit filter of their hashes (8 MB: cache-resident) lets the compaction skip the rest
             const int key_in = slot_input(cp.shape, cp.shape.key);
@@ -1822,95 +2014,23 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
       r.packed_keys = dev_alloc(sizeof(uint64_t) * (size_t)s1);
       r.acc = dev_alloc(sizeof(uint64_t) * (size_t)s1 * r.n_aggs);
       rows->values = dev_alloc(values_bytes(PLX_U32, s1));
-      G = n_slots ? k::direct_agg_compact(dt, (int64_t)std::min<uint64_t>(n_used, ord_cap), r.n_aggs, len_idx, r.packed_keys->as<uint64_t>(), rows->values->as<uint32_t>(), r.acc->as<uint64_t>()) : 0;
+      G = n_slots ? k::direct_agg_compact(dt, direct.n_ord, r.n_aggs, len_idx, r.packed_keys->as<uint64_t>(), rows->values->as<uint32_t>(), r.acc->as<uint64_t>()) : 0;
       r.n_groups = G;
       rows->len = G;
       plan.desc += std::string("FusedJoinGroupBy{build=") + (build_right ? "right" : "left") + " rows=" + std::to_string(nb) + "/" + std::to_string(B->height) + " direct-address table range=" +
                    std::to_string(range) + " (bitmap + rank) unique-keys, probe rows=" + std::to_string(P->height) + ", fused_scan[" + jit::program_mode(probe_static_id, cp.args.n_rows) + "]+" + probe_how + ", aggs=" +
                    std::to_string(r.n_aggs) + ", groups=" + std::to_string(G) + "}; ";
       done = true;
-      }  // unique build keys
-    }
+    }  // unique build keys
   }
-  // Size of the build table.  The number of build rows that pass the build side's predicate is a by-product of the build scan itself (JoinBuildSink counts what
-  // it inserts), so a large build side is sized from a strided sample of the count program (4 blocks of 2^18 rows, + 25 %) instead of a counting pass over the
-  // whole side; if the sample misjudged (table more than 0.7 full, or a probe sequence overflowed) the table is rebuilt once from the exact count.
-  auto exact_count = [&]() -> uint64_t { std::vector<uint64_t> host(kMaxAggs, 0); k::fused_regagg(cnt.shape, cnt.args, find_static_shape(cnt.shape), host.data()); return host[0]; };
-  bool sized_by_sample = false;
-  if (!done && B->height > 0) {
-    static const bool no_sample = getenv("PLX_JOIN_COUNT_SAMPLE") && getenv("PLX_JOIN_COUNT_SAMPLE")[0] == '0';
-    if (B->height >= ((int64_t)1 << 24) && !no_sample) {
-      constexpr int kCountBlocks = 4;                  // every block is a launch + a host round trip (~40 us)
-      const int64_t per = (int64_t)1 << 18, stride = (B->height / kCountBlocks) & ~(int64_t)127;
-      uint64_t hits = 0, seen = 0;
-      for (int b = 0; b < kCountBlocks; b++) {
-        const int64_t row0 = (int64_t)b * stride, rows_b = std::min<int64_t>(per, B->height - row0);
-        if (rows_b <= 0) continue;
-        std::vector<uint64_t> host(kMaxAggs, 0);
-        k::fused_regagg(cnt.shape, offset_args(cnt.shape, cnt.args, row0, rows_b), -1, host.data());
-        hits += host[0]; seen += (uint64_t)rows_b;
-      }
-      nb = (uint64_t)((double)hits / (double)std::max<uint64_t>(seen, 1) * (double)B->height * 1.25) + 4096;
-      sized_by_sample = true;
-    } else nb = exact_count();
-  }
-  // PLX_JOIN_TRACE=1 (debugging aid): every stage of the hash-table pipeline announced on stderr behind a stream synchronisation -- a stage that hangs is the last one named
-  static const bool jtrace = getenv("PLX_JOIN_TRACE") && getenv("PLX_JOIN_TRACE")[0] == '1';
-#define JTRACE(...) do { if (jtrace) { PLX_HIP(hipStreamSynchronize(stream())); fprintf(stderr, "[plx join] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
   if (!done) {
-  Buf keys, flags, acc, links;
-  JoinAggTable t{};
-  int log2_cap = 4;
-  uint64_t cap = 0;
-  std::string build_how;
-  bool pbuild_off = false;
-  k::JoinCells jcells;
-  if (known_dups) { B->cols[bki]->repeats_as_build_key = true; if (!multi_ok) return no("build keys are not unique (and a build-side group column is not integer-typed)"); multi = true; }
-  bool resized = false;
-  for (int attempt = 0; attempt < 4; attempt++) {
-    if (multi && !links) links = dev_alloc(sizeof(uint64_t) * (size_t)std::max<int64_t>(B->height, 1));
-    // (the sampled count already carries 25 %: x1.6 keeps the load at or below ~0.6 without doubling a table that x2 would push over the next power of two)
-    log2_cap = std::max(4, ceil_log2_u64((uint64_t)((double)std::max<uint64_t>(nb, 1) * (sized_by_sample ? 1.6 : 2.0))));
-    cap = 1ull << log2_cap;
-    keys = dev_alloc(sizeof(uint64_t) * 2 * (cap + 1)); flags = dev_alloc_zero(32);       // {key, row} slots: kEmptyKey and kNoRow32 are both all-ones
-    t.slots = keys->as<unsigned long long>(); t.flags = flags->as<unsigned int>(); t.acc = nullptr;
-    t.count = flags->as<unsigned long long>() + 1; t.log2_cap = (uint32_t)log2_cap;
-    t.links = multi ? links->as<unsigned long long>() : nullptr;
-    JTRACE("build attempt %d multi=%d cap=2^%d nb=%llu", attempt, (int)multi, log2_cap, (unsigned long long)nb);
-    // a large build side with (so far) unique keys: partitioned, the table filled window by window from LDS -- no device atomic per row (k::partitioned_join_build)
-    t.log2_window = 0;
-    build_how = "join_build";
-    bool pbuilt = false;
-    if (!multi && !pbuild_off && partitioned_build_wanted(B->height, log2_cap)) {
-      t.log2_window = kJoinWindowLog2;
-      std::string bd;
-      pbuilt = k::partitioned_join_build(cb.shape, cb.args, find_static_shape(cb.shape), t, &jcells, &bd);
-      if (pbuilt) build_how = bd; else t.log2_window = 0;
-    }
-    if (!pbuilt) {
-      PLX_HIP(hipMemsetAsync(keys->ptr, 0xff, sizeof(uint64_t) * 2 * (cap + 1), stream()));
-      k::fused_join_build(cb.shape, cb.args, t, find_static_shape(cb.shape));
-    }
-    JTRACE("build done");
-    uint64_t fl64[2] = {0, 0};
-    d2h_sync(fl64, flags->ptr, 16);
-    const uint32_t dup = (uint32_t)fl64[0], ovf = (uint32_t)(fl64[0] >> 32);
-    if (dup) {
-      if (!multi_ok) return no("build keys are not unique (and a build-side group column is not integer-typed)");
-      B->cols[bki]->repeats_as_build_key = true;
-      multi = true;                                  // build once more, chaining the rows of a key (the table's size stays: it was planned for the rows, not the keys)
-      continue;
-    }
-    if (!resized && (ovf || (sized_by_sample && fl64[1] * 10 > cap * 7))) {      // the sample misjudged (on whichever attempt: the multi-value rebuild keeps the sampled size): once more, from the exact count
-      nb = ovf ? exact_count() : fl64[1];
-      sized_by_sample = false; resized = true;
-      continue;
-    }
-    if (ovf && pbuilt) { pbuild_off = true; continue; }                             // a window filled up although the table is sized right (keys that crowd one window): the plain build probes the whole table
-    PLX_REQUIRE(!ovf, PLX_ERR_OOM, "join build: probe sequence overflow");
-    nb = fl64[1];                                                                   // exact from here on
-    break;
-  }
+  HashBuild hb;
+  if (!hb.run(cnt, cb, *B, bki, HashBuildOptions{4, known_dups, multi_ok, true, "join_build"})) return no("build keys are not unique (and a build-side group column is not integer-typed)");
+  JoinAggTable& t = hb.t;
+  const k::JoinCells& jcells = hb.cells;
+  const uint64_t cap = hb.cap;
+  nb = hb.nb; multi = hb.multi;
+  Buf acc;
   if (multi) {
     Buf cflags = dev_alloc_zero(8);
     constexpr unsigned int kMaxChain = 1024;
@@ -1934,25 +2054,16 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   // filter in LDS); the hash probe below then runs over the surviving candidates only and compares whole keys.
   std::string hprobe_how = "probe_agg";
   bool hprobed = false;
-  {
-    const int pmode = partitioned_probe_mode();
-    if (pmode == 2 || (pmode == 1 && P->height >= ((int64_t)1 << 24) && (cap + 1) * 16 > ((uint64_t)64 << 20) && nb * 16 <= (uint64_t)P->height)) {
-      ColumnPtr hits;
-      std::string pd;
-      if (k::partitioned_hash_probe_hits(cs.shape, cs.args, t, nb, find_static_shape(cs.shape), &hits, &pd)) {
-        if (hits->len > 0) {
-          Args a2 = cp.args;
-          a2.n_rows = hits->len;
-          std::vector<ColumnPtr> srcs;
-          for (int i = 0; i < cp.shape.n_inputs; i++) srcs.push_back(cp.cols[cp.input_cols[i]]);
-          std::vector<ColumnPtr> keep = ops::gather_columns(srcs, hits);
-          for (int i = 0; i < cp.shape.n_inputs; i++) { a2.in[i].values = keep[i]->data(); a2.in[i].validity = cp.shape.in_nullable[i] ? keep[i]->valid_words() : nullptr; }
-          k::fused_probe_agg(cp.shape, a2, t, probe_static_id);
-          PLX_HIP(hipStreamSynchronize(stream()));       // the gathered columns live until the kernels have read them
-        }
-        hprobe_how = pd + "+gather+probe_agg";
-        hprobed = true;
+  if (partition_hash_probe(partitioned_probe_mode(), *P, cap, nb)) {
+    ColumnPtr hits;
+    std::string pd;
+    if (k::partitioned_hash_probe_hits(cs.shape, cs.args, t, nb, find_static_shape(cs.shape), &hits, &pd)) {
+      if (hits->len > 0) {
+        std::vector<ColumnPtr> keep = probe_gathered(cp, hits, [&](const Args& a2) { k::fused_probe_agg(cp.shape, a2, t, probe_static_id); });
+        PLX_HIP(hipStreamSynchronize(stream()));       // the gathered columns live until the kernels have read them
       }
+      hprobe_how = pd + "+gather+probe_agg";
+      hprobed = true;
     }
   }
   JTRACE("probe (partitioned: %d)", (int)hprobed);
@@ -1974,7 +2085,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   PLX_REQUIRE(multi || G <= g1, PLX_ERR_INVALID, "join: more groups than build rows");
   r.n_groups = G;
   rows->len = G;
-  plan.desc += std::string("FusedJoinGroupBy{build=") + (build_right ? "right" : "left") + " rows=" + std::to_string(nb) + "/" + std::to_string(B->height) + " hash table cap=2^" + std::to_string(log2_cap) + " [" + build_how + "]" +
+  plan.desc += std::string("FusedJoinGroupBy{build=") + (build_right ? "right" : "left") + " rows=" + std::to_string(nb) + "/" + std::to_string(B->height) + " hash table cap=2^" + std::to_string(hb.log2_cap) + " [" + hb.build_how + "]" +
                (multi ? " multi-value (row chains, a group = a build row; " + std::to_string(merged_rows) + " rows share another row's group), probe rows=" : " unique-keys, probe rows=") + std::to_string(P->height) + ", fused_scan[" + jit::program_mode(probe_static_id, cp.args.n_rows) + "]+" + hprobe_how + ", aggs=" + std::to_string(r.n_aggs) + ", groups=" + std::to_string(G) + "}; ";
   }  // hash-table path
   // ---- output frame: keys, then aggregates
@@ -2001,12 +2112,8 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   }
   if (left_join) {
     // the unmatched left rows: membership bitmap of the build keys that pass the build side's predicate, then a fused group-by over the left table
-    Buf bits = dev_alloc_zero(sizeof(uint64_t) * (size_t)(a_range / 64 + 2)), rows_dev = dev_alloc_zero(8);
-    if (B->height > 0) {
-      BitmapBuild bb; bb.bits = bits->as<unsigned long long>(); bb.count = rows_dev->as<unsigned long long>(); bb.kmin = a_kmn; bb.range = a_range;
-      k::fused_bitmap_build(cb.shape, cb.args, bb, find_static_shape(cb.shape));
-    }
-    ca.args.lut[psemis.size()] = Lut{bits->as<unsigned long long>(), a_range};
+    unmatched_keys.build(B->height > 0 ? &cb : nullptr);
+    ca.args.lut[psemis.size()] = unmatched_keys.lut();
     FusedAggResult ar;
     std::string ad;
     try {
@@ -2020,7 +2127,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
       plan.desc += "AssumedBoundsViolated{exact statistics, second run}; ";
       return fused_join_groupby(plan, gb, out, why, shapes_out, compile_only);
     }
-    plan.desc += "LeftJoinUnmatched{membership bitmap range=" + std::to_string(a_range) + ", " + akp.note + "FusedFilterGroupBy{" + ad + ", groups=" + std::to_string(ar.n_groups) + "}}; ";
+    plan.desc += "LeftJoinUnmatched{membership bitmap range=" + std::to_string(unmatched_keys.range) + ", " + akp.note + "FusedFilterGroupBy{" + ad + ", groups=" + std::to_string(ar.n_groups) + "}}; ";
     const int64_t U = ar.n_groups;
     auto tail = std::make_shared<Frame>();
     tail->height = U;
@@ -2068,8 +2175,7 @@ static bool fused_filter_frame(Plan& plan, const std::vector<int>& preds, const 
                                const MemberTest* member = nullptr) {
   Compiler c(plan, *src);
   try {
-    int p = -1;
-    for (int pe : preds) { int n = c.lower(pe); if (c.nodes[n].ty != 'b') throw Unsupported("predicate is not boolean"); p = p < 0 ? n : c.mk(OP_AND, p, n, 'b'); }
+    int p = and_predicates(c, preds);
     if (member) {
       const int kn = c.load(member->key_col);
       int m = c.ifnull(c.bit_lookup(p < 0 ? kn : c.mask_valid(kn, p), 0, member->kmin), 0);      // (rows the predicates already rejected do not look the bitmap up: OP_MASKV)
@@ -2262,9 +2368,8 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
   if (mode == 0) return no("disabled (PLX_JOIN_MATERIALISE=0)");
   if ((jn.how != PLX_JOIN_INNER && jn.how != PLX_JOIN_LEFT) || jn.keys.size() != 1 || jn.keys_right.size() != 1) return no("not a single-key inner or left join");
   const bool left_join = jn.how == PLX_JOIN_LEFT;
-  auto plain = [&](int e) -> const AE* { const AE* x = &plan.ae[e]; while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs]; return x->kind == PLX_AE_COLUMN ? x : nullptr; };
-  const AE* lkx = plain(jn.keys[0]);
-  const AE* rkx = plain(jn.keys_right[0]);
+  const AE* lkx = plain_column(plan, jn.keys[0]);
+  const AE* rkx = plain_column(plan, jn.keys_right[0]);
   if (!lkx || !rkx) return no("join keys are expressions");
   std::vector<int> lpreds, rpreds;
   const int lsrc = peel_filters(plan, jn.input, lpreds), rsrc = peel_filters(plan, jn.input_right, rpreds);
@@ -2273,48 +2378,26 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
   if (mode == 1 && height_of(lsrc) >= 0 && height_of(rsrc) >= 0 && std::max(height_of(lsrc), height_of(rsrc)) < ((int64_t)1 << 24)) return no("small inputs");
   FramePtr L = exec_node(plan, lsrc), R = exec_node(plan, rsrc);
   plan.memo[lsrc] = L; plan.memo[rsrc] = R;
-  const int lki = L->find(lkx->name), rki = R->find(rkx->name);
-  if (lki < 0 || rki < 0) return no("join key column not found");
-  const int kdt = L->cols[lki]->dtype;
-  if (kdt != R->cols[rki]->dtype || !dtype_is_int(kdt)) return no("join key is not an integer column pair of one dtype");
-  if (L->height >= 0xffffffffll || R->height >= 0xffffffffll) return no("side exceeds u32 row indices");
-  const bool build_right = left_join || L->height > R->height;       // det_hash_prone_order (hash_join/mod.rs:41-50); a left join probes with its left table
-  const FramePtr& B = build_right ? R : L;
-  const FramePtr& P = build_right ? L : R;
+  JoinSides sides;
+  const char* bad = nullptr;
+  if (!resolve_join_sides(sides, L, R, lkx, rkx, left_join, lpreds, rpreds, &bad)) return no(bad);
+  const FramePtr &B = sides.B, &P = sides.P;
+  const int bki = sides.bki, pki = sides.pki;
+  const bool build_right = sides.build_right;
+  const std::vector<int> &bpreds = sides.bpreds, &ppreds = sides.ppreds;
   if (mode == 1 && P->height < ((int64_t)1 << 24)) return no("small inputs");
-  const int bki = build_right ? rki : lki, pki = build_right ? lki : rki;
-  const std::vector<int>& bpreds = build_right ? rpreds : lpreds;
-  const std::vector<int>& ppreds = build_right ? lpreds : rpreds;
-  // output columns (_finish_join, general.rs:17-49): left columns, then right columns except the coalesced right key; clashes get the suffix
-  struct OutCol { std::string name; int side; int idx; };     // side 0 = left, 1 = right
-  std::vector<OutCol> outs;
-  {
-    std::set<std::string> seen;
-    for (size_t i = 0; i < L->names.size(); i++) { outs.push_back({L->names[i], 0, (int)i}); seen.insert(L->names[i]); }
-    for (size_t i = 0; i < R->names.size(); i++) {
-      if ((int)i == rki) continue;
-      std::string name = R->names[i];
-      if (seen.count(name)) name += jn.suffix;
-      if (seen.count(name)) return no("duplicate output column name");
-      seen.insert(name);
-      outs.push_back({name, 1, (int)i});
-    }
-  }
+  std::vector<JoinedCol> outs;
+  if (!joined_columns(*L, *R, sides.rki, jn.suffix, outs, &bad)) return no(bad);
   Compiler cnt(plan, *B), cb(plan, *B), cs(plan, *P);
   try {
-    auto and_preds = [&](Compiler& c, const std::vector<int>& preds) {
-      int p = -1;
-      for (int pe : preds) { int n = c.lower(pe); if (c.nodes[n].ty != 'b') throw Unsupported("predicate is not boolean"); p = p < 0 ? n : c.mk(OP_AND, p, n, 'b'); }
-      return p;
-    };
-    cnt.pred = and_preds(cnt, bpreds);
+    cnt.pred = and_predicates(cnt, bpreds);
     const int bk_cnt = cnt.load(bki);
     cnt.add_agg(cnt.nodes[bk_cnt].nullable ? AGG_COUNT : AGG_LEN, cnt.nodes[bk_cnt].nullable ? bk_cnt : -1);
     cnt.finish();
-    cb.pred = and_preds(cb, bpreds);
+    cb.pred = and_predicates(cb, bpreds);
     cb.key = cb.load(bki);
     cb.finish();
-    cs.pred = and_preds(cs, ppreds);
+    cs.pred = and_predicates(cs, ppreds);
     cs.key = cs.load(pki);
     cs.add_agg(AGG_FIRST_ROW, -1);
     cs.finish();
@@ -2335,132 +2418,66 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
     cand_how += " -> " + rd;
   };
   const int pmode = partitioned_probe_mode();
-  int64_t kmn = 0, kmx = 0;
-  if (!(plan.flags & PLX_PLAN_NO_DIRECT_JOIN) && !multi && B->height > 0 && kdt != PLX_U64 && ops::int_range(B->cols[bki], &kmn, &kmx)) {
-    const unsigned __int128 range128 = (unsigned __int128)((__int128)kmx - (__int128)kmn) + 1;
-    const uint64_t ord_cap = (uint64_t)B->height + (uint64_t)k::scan_waves(B->height) * 1024 + 1024;
-    if (range128 <= ((unsigned __int128)1 << 34) && range128 <= (unsigned __int128)B->height * 256 && ord_cap < 0xfffffff0ull) {
-      const uint64_t range = (uint64_t)range128;
-      const size_t n_words = (size_t)(range / 512 + 1) * 8;
-      Buf bits = dev_alloc_zero(sizeof(uint64_t) * n_words), rank = dev_alloc(sizeof(uint32_t) * n_words);
-      Buf okey = dev_alloc(sizeof(uint64_t) * ord_cap), orow = dev_alloc(sizeof(uint32_t) * ord_cap), used = dev_alloc_zero(sizeof(uint32_t) * (ord_cap / 1024 + 2));
-      Buf meta = dev_alloc_zero(32);
-      DirectJoinTable dt{}; dt.bits = bits->as<unsigned long long>(); dt.rank = rank->as<unsigned int>(); dt.ord_key = okey->as<unsigned long long>(); dt.ord_row = orow->as<unsigned int>();
-      dt.chunk_used = used->as<unsigned int>(); dt.counter = meta->as<unsigned int>(); dt.flags = meta->as<unsigned int>() + 2; dt.acc = nullptr; dt.kmin = kmn; dt.range = range; dt.n_ord = (unsigned int)ord_cap;
-      k::fused_direct_build(cb.shape, cb.args, dt, find_static_shape(cb.shape));
-      uint64_t pairs = 0;
-      nb = k::direct_rank(dt, rank->as<uint32_t>(), (int64_t)ord_cap, meta->as<uint64_t>() + 2, &pairs);
-      uint32_t m4[4] = {0, 0, 0, 0};
-      d2h_sync(m4, meta->ptr, 16);
-      PLX_REQUIRE(!m4[3], PLX_ERR_INVALID, "direct join build: ordinal overflow");
-      if (pairs != nb) { multi = true; B->cols[bki]->repeats_as_build_key = true; }
-      else {
-        Buf slot_row = dev_alloc(sizeof(uint32_t) * (size_t)std::max<uint64_t>(nb, 1));
-        k::direct_slot_rows(dt, (int64_t)std::min<uint64_t>(m4[0], ord_cap), slot_row->as<uint32_t>());
-        ColumnPtr cand;
-        if (!left_join) {
-          const ColumnPtr& pk = P->cols[pki];
-          if (pmode == 2 || (pmode == 1 && P->height >= ((int64_t)1 << 24) && range >= ((uint64_t)1 << 28) && nb * 8 <= range)) {
-            if (pk->order_state == 0) pk->order_state = k::sample_sortedness(pk) >= 0.9 ? 1 : 2;
-            std::string ppd;
-            if ((pmode == 2 || pk->order_state == 2) && k::partitioned_probe_hits(cs.shape, cs.args, dt, nb, find_static_shape(cs.shape), &cand, &ppd)) { cand_how = ppd; partitioned_candidates(cand); }
-            else cand = nullptr;
+  {
+    DirectBuild direct;
+    const DirectBuild::Result built = direct.try_build(plan, cb, *B, bki, multi);
+    if (built == DirectBuild::kDuplicateKeys) multi = true;
+    else if (built == DirectBuild::kBuilt) {
+      const DirectJoinTable& dt = direct.dt;
+      const uint64_t range = direct.range;
+      nb = direct.nb;
+      Buf slot_row = dev_alloc(sizeof(uint32_t) * (size_t)std::max<uint64_t>(nb, 1));
+      k::direct_slot_rows(dt, direct.n_ord, slot_row->as<uint32_t>());
+      ColumnPtr cand;
+      if (!left_join) {
+        if (partition_direct_probe(pmode, *P, pki, range, nb)) {
+          std::string ppd;
+          if (k::partitioned_probe_hits(cs.shape, cs.args, dt, nb, find_static_shape(cs.shape), &cand, &ppd)) { cand_how = ppd; partitioned_candidates(cand); }
+          else cand = nullptr;
+        }
+        if (!cand) {
+          // the probe scan itself: predicate + bitmap test per row, ballots out; the hit rows' indices from the ballots (every one of them matches)
+          const int64_t np = P->height, n_wt = (np + 127) / 128;
+          cand = std::make_shared<Column>();
+          cand->dtype = PLX_U32; cand->null_count = 0; cand->len = 0; cand->values = dev_alloc(8);
+          if (np > 0) {
+            Buf ballots = dev_alloc(sizeof(uint64_t) * 2 * (size_t)n_wt), counts = dev_alloc(sizeof(uint32_t) * (size_t)n_wt);
+            const int sid = find_static_shape(cs.shape);
+            k::fused_direct_hits(cs.shape, cs.args, dt, BallotOut{ballots->as<unsigned long long>(), counts->as<unsigned int>()}, sid);
+            const k::Selection sel = k::selection_finish(ballots, counts, np);
+            cand->len = sel.n_out;
+            cand->values = dev_alloc(values_bytes(PLX_U32, std::max<int64_t>(sel.n_out, 1)));
+            k::compact_by_ballots(sel, k::CompactCols{}, cand->values->as<uint32_t>());
+            PLX_HIP(hipStreamSynchronize(stream()));
+            cand_how = std::string("fused_scan[") + jit::program_mode(sid, np) + "]+direct hits (ballots -> row ids)";
           }
-          if (!cand) {
-            // the probe scan itself: predicate + bitmap test per row, ballots out; the hit rows' indices from the ballots (every one of them matches)
-            const int64_t np = P->height, n_wt = (np + 127) / 128;
-            cand = std::make_shared<Column>();
-            cand->dtype = PLX_U32; cand->null_count = 0; cand->len = 0; cand->values = dev_alloc(8);
-            if (np > 0) {
-              Buf ballots = dev_alloc(sizeof(uint64_t) * 2 * (size_t)n_wt), counts = dev_alloc(sizeof(uint32_t) * (size_t)n_wt);
-              const int sid = find_static_shape(cs.shape);
-              k::fused_direct_hits(cs.shape, cs.args, dt, BallotOut{ballots->as<unsigned long long>(), counts->as<unsigned int>()}, sid);
-              const k::Selection sel = k::selection_finish(ballots, counts, np);
-              cand->len = sel.n_out;
-              cand->values = dev_alloc(values_bytes(PLX_U32, std::max<int64_t>(sel.n_out, 1)));
-              k::compact_by_ballots(sel, k::CompactCols{}, cand->values->as<uint32_t>());
-              PLX_HIP(hipStreamSynchronize(stream()));
-              cand_how = std::string("fused_scan[") + jit::program_mode(sid, np) + "]+direct hits (ballots -> row ids)";
-            }
-          }
-        } else if (!ppreds.empty()) {
-          FramePtr none; std::string fwhy;
-          const size_t mark = plan.desc.size();
-          if (!fused_filter_frame(plan, ppreds, P, none, &fwhy, &cand, true)) { if (why) *why = "probe-side predicate: " + fwhy; return false; }
-          cand_how = "probe rows by " + plan.desc.substr(mark);
-          plan.desc.resize(mark);
-          while (!cand_how.empty() && (cand_how.back() == ' ' || cand_how.back() == ';')) cand_how.pop_back();
-        } else cand_how = "every probe row";
-        join::join_pairs_direct(jn.how, P->cols[pki], cand, dt, slot_row->as<uint32_t>(), pidx, bidx, &pd);
-        PLX_HIP(hipStreamSynchronize(stream()));
-        table_how = "direct-address table range=" + std::to_string(range) + " (bitmap + rank + slot rows) unique-keys";
-        done_direct = true;
-      }
+        }
+      } else if (!ppreds.empty()) {
+        FramePtr none; std::string fwhy;
+        const size_t mark = plan.desc.size();
+        if (!fused_filter_frame(plan, ppreds, P, none, &fwhy, &cand, true)) { if (why) *why = "probe-side predicate: " + fwhy; return false; }
+        cand_how = "probe rows by " + plan.desc.substr(mark);
+        plan.desc.resize(mark);
+        while (!cand_how.empty() && (cand_how.back() == ' ' || cand_how.back() == ';')) cand_how.pop_back();
+      } else cand_how = "every probe row";
+      join::join_pairs_direct(jn.how, P->cols[pki], cand, dt, slot_row->as<uint32_t>(), pidx, bidx, &pd);
+      PLX_HIP(hipStreamSynchronize(stream()));
+      table_how = "direct-address table range=" + std::to_string(range) + " (bitmap + rank + slot rows) unique-keys";
+      done_direct = true;
     }
   }
   if (build_rows_out && done_direct) *build_rows_out = nb;
   if (build_side_out) *build_side_out = build_right ? 1 : 0;
   if (!done_direct) {
-  // ---- build (the hash-table pipeline of fused_join_groupby: sized from a strided sample of the count program, rebuilt once if the sample misjudged; duplicate keys -> chains)
-  auto exact_count = [&]() -> uint64_t { std::vector<uint64_t> host(kMaxAggs, 0); k::fused_regagg(cnt.shape, cnt.args, find_static_shape(cnt.shape), host.data()); return host[0]; };
-  bool sized_by_sample = false;
-  if (B->height > 0) {
-    if (B->height >= ((int64_t)1 << 24)) {
-      constexpr int kCountBlocks = 4;
-      const int64_t per = (int64_t)1 << 18, stride = (B->height / kCountBlocks) & ~(int64_t)127;
-      uint64_t hits = 0, seen = 0;
-      for (int b = 0; b < kCountBlocks; b++) {
-        const int64_t row0 = (int64_t)b * stride, rows_b = std::min<int64_t>(per, B->height - row0);
-        if (rows_b <= 0) continue;
-        std::vector<uint64_t> host(kMaxAggs, 0);
-        k::fused_regagg(cnt.shape, offset_args(cnt.shape, cnt.args, row0, rows_b), -1, host.data());
-        hits += host[0]; seen += (uint64_t)rows_b;
-      }
-      nb = (uint64_t)((double)hits / (double)std::max<uint64_t>(seen, 1) * (double)B->height * 1.25) + 4096;
-      sized_by_sample = true;
-    } else nb = exact_count();
-  }
-  Buf keys, flags, links;
-  JoinAggTable t{};
-  int log2_cap = 4;
-  uint64_t cap = 0;
-  bool resized = false, pbuild_off = false;
-  std::string build_how;
-  for (int attempt = 0; attempt < 4; attempt++) {
-    if (multi && !links) links = dev_alloc(sizeof(uint64_t) * (size_t)std::max<int64_t>(B->height, 1));
-    log2_cap = std::max(8, ceil_log2_u64((uint64_t)((double)std::max<uint64_t>(nb, 1) * (sized_by_sample ? 1.6 : 2.0))));
-    cap = 1ull << log2_cap;
-    keys = dev_alloc(sizeof(uint64_t) * 2 * (cap + 1)); flags = dev_alloc_zero(32);
-    t.slots = keys->as<unsigned long long>(); t.flags = flags->as<unsigned int>(); t.acc = nullptr;
-    t.count = flags->as<unsigned long long>() + 1; t.log2_cap = (uint32_t)log2_cap;
-    t.links = multi ? links->as<unsigned long long>() : nullptr;
-    // (as in fused_join_groupby: a large build side with unique keys is binned into the table's windows and filled from LDS)
-    t.log2_window = 0;
-    build_how.clear();
-    bool pbuilt = false;
-    if (!multi && !pbuild_off && partitioned_build_wanted(B->height, log2_cap)) {
-      t.log2_window = kJoinWindowLog2;
-      pbuilt = k::partitioned_join_build(cb.shape, cb.args, find_static_shape(cb.shape), t, nullptr, &build_how);
-      if (!pbuilt) t.log2_window = 0;
-    }
-    if (!pbuilt) {
-      PLX_HIP(hipMemsetAsync(keys->ptr, 0xff, sizeof(uint64_t) * 2 * (cap + 1), stream()));
-      k::fused_join_build(cb.shape, cb.args, t, find_static_shape(cb.shape));
-    }
-    uint64_t fl64[2] = {0, 0};
-    d2h_sync(fl64, flags->ptr, 16);
-    const uint32_t dup = (uint32_t)fl64[0], ovf = (uint32_t)(fl64[0] >> 32);
-    if (dup && !multi) { B->cols[bki]->repeats_as_build_key = true; multi = true; continue; }      // build once more, chaining the rows of a key
-    if (!resized && (ovf || fl64[1] * 10 > cap * 7)) { nb = ovf ? exact_count() : fl64[1]; sized_by_sample = false; resized = true; continue; }      // the sample misjudged: once more, from the exact count
-    if (ovf && pbuilt) { pbuild_off = true; continue; }
-    PLX_REQUIRE(!ovf, PLX_ERR_OOM, "join build: probe sequence overflow");
-    nb = fl64[1];
-    break;
-  }
+  // ---- build (sized from a strided sample of the count program, rebuilt once if the sample misjudged; duplicate keys -> chains)
+  HashBuild hb;
+  hb.run(cnt, cb, *B, bki, HashBuildOptions{8, multi, true, false, ""});
+  const JoinAggTable& t = hb.t;
+  nb = hb.nb; multi = hb.multi;
   if (build_rows_out) *build_rows_out = nb;
   // ---- candidates
   ColumnPtr cand;
-  if (!left_join && (pmode == 2 || (pmode == 1 && P->height >= ((int64_t)1 << 24) && (cap + 1) * 16 > ((uint64_t)64 << 20) && nb * 16 <= (uint64_t)P->height))) {
+  if (!left_join && partition_hash_probe(pmode, *P, hb.cap, nb)) {
     std::string pd;
     if (k::partitioned_hash_probe_hits(cs.shape, cs.args, t, nb, find_static_shape(cs.shape), &cand, &pd)) { cand_how = pd; partitioned_candidates(cand); }
     else cand = nullptr;
@@ -2477,7 +2494,7 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
   // ---- pairs
   join::join_pairs(jn.how, P->cols[pki], cand, t, pidx, bidx, &pd);
   PLX_HIP(hipStreamSynchronize(stream()));
-  table_how = "hash table cap=2^" + std::to_string(log2_cap) + (build_how.empty() ? "" : " [" + build_how + "]") + (multi ? " multi-value (row chains)" : " unique-keys");
+  table_how = "hash table cap=2^" + std::to_string(hb.log2_cap) + (hb.build_how.empty() ? "" : " [" + hb.build_how + "]") + (multi ? " multi-value (row chains)" : " unique-keys");
   }  // hash-table pipeline
   // ---- the order the join was asked to keep (plx_join_order): the pair list is ordered, the gathers below then produce the frame in that order
   if (jn.maintain_order != PLX_JOIN_ORDER_NONE) {
@@ -2525,9 +2542,8 @@ static bool fused_semi_anti_frame(Plan& plan, const IRN& jn, FramePtr& out, std:
   auto no = [&](const char* m) { if (why) *why = m; return false; };
   if (join_materialise_mode() == 0) return no("disabled (PLX_JOIN_MATERIALISE=0)");
   if ((jn.how != PLX_JOIN_SEMI && jn.how != PLX_JOIN_ANTI) || jn.keys.size() != 1 || jn.keys_right.size() != 1) return no("not a single-key semi or anti join");
-  auto plain = [&](int e) -> const AE* { const AE* x = &plan.ae[e]; while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs]; return x->kind == PLX_AE_COLUMN ? x : nullptr; };
-  const AE* lkx = plain(jn.keys[0]);
-  const AE* rkx = plain(jn.keys_right[0]);
+  const AE* lkx = plain_column(plan, jn.keys[0]);
+  const AE* rkx = plain_column(plan, jn.keys_right[0]);
   if (!lkx || !rkx) return no("join keys are expressions");
   std::vector<int> lpreds, rpreds;
   const int lsrc = peel_filters(plan, jn.input, lpreds), rsrc = peel_filters(plan, jn.input_right, rpreds);
@@ -2539,25 +2555,21 @@ static bool fused_semi_anti_frame(Plan& plan, const IRN& jn, FramePtr& out, std:
   if (kdt != R->cols[rki]->dtype || !dtype_is_int(kdt) || kdt == PLX_U64) return no("join key is not a signed / narrow integer column pair of one dtype");
   int64_t mn = 0, mx = 0;
   const bool have = R->height > 0 && R->cols[rki]->values && ops::int_range(R->cols[rki], &mn, &mx);
-  const unsigned __int128 range128 = have ? (unsigned __int128)((__int128)mx - (__int128)mn) + 1 : 1;
-  if (range128 > ((unsigned __int128)1 << 34) || (have && range128 > (unsigned __int128)R->height * 256 + 4096)) return no("right key range too wide for a membership bitmap");
-  const uint64_t range = (uint64_t)range128;
-  Buf bits = dev_alloc_zero(sizeof(uint64_t) * (size_t)(range / 64 + 2)), rows_dev = dev_alloc_zero(8);
+  MemberBitmap members;
+  if (!members.cover(have, mn, mx, R->height)) return no("right key range too wide for a membership bitmap");
+  const uint64_t range = members.range;
   uint64_t rows_in = 0;
   if (have) {
     Compiler cb(plan, *R);
     try {
-      int p = -1;
-      for (int pe : rpreds) { int n = cb.lower(pe); if (cb.nodes[n].ty != 'b') throw Unsupported("predicate is not boolean"); p = p < 0 ? n : cb.mk(OP_AND, p, n, 'b'); }
-      cb.pred = p;
+      cb.pred = and_predicates(cb, rpreds);
       cb.key = cb.load(rki);
       cb.finish();
     } catch (const Unsupported& u) { if (why) *why = "right side: " + u.why; return false; }
-    BitmapBuild bb; bb.bits = bits->as<unsigned long long>(); bb.count = rows_dev->as<unsigned long long>(); bb.kmin = mn; bb.range = range;
-    k::fused_bitmap_build(cb.shape, cb.args, bb, find_static_shape(cb.shape));
-    d2h_sync(&rows_in, rows_dev->ptr, 8);
-  }
-  const MemberTest mt{lki, bits->as<unsigned long long>(), mn, range, jn.how == PLX_JOIN_ANTI};
+    members.build(&cb);
+    rows_in = members.rows_in();
+  } else members.build(nullptr);
+  const MemberTest mt{lki, members.bits->as<unsigned long long>(), mn, range, jn.how == PLX_JOIN_ANTI};
   const size_t mark = plan.desc.size();
   std::string fwhy;
   if (!fused_filter_frame(plan, lpreds, L, out, &fwhy, nullptr, false, &mt)) { if (why) *why = "left side: " + fwhy; return false; }
@@ -2655,11 +2667,8 @@ static FramePtr exec_join(Plan& plan, const IRN& n) {
   for (size_t i = 0; i < left->cols.size(); i++) { out->names.push_back(left->names[i]); out->cols.push_back(ops::gather(left->cols[i], li)); }
   std::vector<std::string> coalesced;   // right key columns merged into the left key (both sides plain columns)
   for (size_t j = 0; j < n.keys.size(); j++) {
-    const AE* rkx = &plan.ae[n.keys_right[j]];
-    while (rkx->kind == PLX_AE_ALIAS) rkx = &plan.ae[rkx->lhs];
-    const AE* lkx = &plan.ae[n.keys[j]];
-    while (lkx->kind == PLX_AE_ALIAS) lkx = &plan.ae[lkx->lhs];
-    if (rkx->kind == PLX_AE_COLUMN && lkx->kind == PLX_AE_COLUMN) coalesced.push_back(rkx->name);
+    const AE* rkx = plain_column(plan, n.keys_right[j]);
+    if (rkx && plain_column(plan, n.keys[j])) coalesced.push_back(rkx->name);
   }
   for (size_t i = 0; i < right->cols.size(); i++) {
     if (std::find(coalesced.begin(), coalesced.end(), right->names[i]) != coalesced.end()) continue;  // coalesced key
@@ -2774,12 +2783,10 @@ static FramePtr exec_node(Plan& plan, int node_id) {
             const IRN& jn = plan.ir[n.input];
             FramePtr bf = exec_node(plan, peel_filters_node(plan, build_side ? jn.input_right : jn.input));
             bool of_build = !n.keys.empty();
+            const AE* lk = plain_column(plan, jn.keys[0]);      // (a plain column: fused_join_frame took the join)
             for (int e : n.keys) {
-              const AE* x = &plan.ae[e];
-              while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs];
-              const AE* lk = &plan.ae[jn.keys[0]];
-              while (lk->kind == PLX_AE_ALIAS) lk = &plan.ae[lk->lhs];
-              of_build = of_build && x->kind == PLX_AE_COLUMN && (x->name == lk->name || bf->find(x->name) >= 0 || (x->name.size() > jn.suffix.size() && bf->find(x->name.substr(0, x->name.size() - jn.suffix.size())) >= 0));
+              const AE* x = plain_column(plan, e);
+              of_build = of_build && x && (x->name == lk->name || bf->find(x->name) >= 0 || (x->name.size() > jn.suffix.size() && bf->find(x->name.substr(0, x->name.size() - jn.suffix.size())) >= 0));
             }
             plan.group_hint = of_build ? (double)std::max<uint64_t>(build_rows, 1) : 0.0;
           }
@@ -2833,9 +2840,7 @@ bool describe_filter_fusion(Plan& plan, int root, Shape* shape, std::string* why
   FramePtr src = get_frame(plan.ir[src_node].frame);
   Compiler c(plan, *src);
   try {
-    int p = -1;
-    for (int pe : preds) { int nn = c.lower(pe); if (c.nodes[nn].ty != 'b') throw Unsupported("predicate is not boolean"); p = p < 0 ? nn : c.mk(OP_AND, p, nn, 'b'); }
-    c.pred = p;
+    c.pred = and_predicates(c, preds);
     c.finish();
   } catch (const Unsupported& u) { if (why_not) *why_not = u.why; return false; }
   if (shape) *shape = c.shape;
