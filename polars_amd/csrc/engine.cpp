@@ -629,6 +629,12 @@ static bool assume_range(const ColumnPtr& col) {
   return true;
 }
 static bool learn_dense_ranges() { const char* e = getenv("PLX_LEARN_DENSE_RANGE"); return !(e && e[0] == '0'); }   // (measurement / tests: 0 = the first run plans without a range pass)
+// the plain column behind any aliases of expression `e`, or null when `e` is anything else
+static const AE* plain_column(const Plan& plan, int e) {
+  const AE* x = &plan.ae[e];
+  while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs];
+  return x->kind == PLX_AE_COLUMN ? x : nullptr;
+}
 static KeyPlan lower_keys(Compiler& c, const std::vector<int>& key_exprs) {
   KeyPlan kp;
   const Plan& plan = c.plan;
@@ -643,10 +649,9 @@ static KeyPlan lower_keys(Compiler& c, const std::vector<int>& key_exprs) {
     knodes[i] = c.lower(e);
     info[i].nullable = c.nodes[knodes[i]].nullable;
     part.nullable = info[i].nullable;
-    const AE* x = &plan.ae[e];
-    while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs];
+    const AE* x = plain_column(plan, e);
     if (part.dtype == PLX_BOOL) { info[i].have_range = true; info[i].mn = 0; info[i].mx = 1; }
-    else if (dtype_is_int(part.dtype) && x->kind == PLX_AE_COLUMN) {
+    else if (dtype_is_int(part.dtype) && x) {
       ColumnPtr col = c.df->cols[c.df->find(x->name)];
       bool cheap = dtype_width(part.dtype) <= 2 || nk > 1 || col->range_state != 0;
       // A single wide key whose range nobody has looked at yet: the range pass over it costs 8 B / row (1.5 ms per 1e9 rows) -- worth it exactly when the keys are
@@ -959,9 +964,8 @@ static uint64_t key_program_signature(const Shape& sh, const Args& args) {
 // the frame column a single-column group key reads directly, when the query has no predicate (then the sample depends on nothing else)
 static ColumnPtr plain_key_column(const Compiler& c, const KeyPlan& kp) {
   if (c.shape.pred != kNone || kp.parts.size() != 1) return nullptr;
-  const AE* x = &c.plan.ae[kp.parts[0].expr];
-  while (x->kind == PLX_AE_ALIAS) x = &c.plan.ae[x->lhs];
-  if (x->kind != PLX_AE_COLUMN) return nullptr;
+  const AE* x = plain_column(c.plan, kp.parts[0].expr);
+  if (!x) return nullptr;
   const int ci = c.df->find(x->name);
   return ci >= 0 && c.df->cols[ci]->len == c.args.n_rows ? c.df->cols[ci] : nullptr;
 }
@@ -992,217 +996,224 @@ static int64_t sample_keys_cached(const ColumnPtr& key_col, const Shape& sh, con
   return d;
 }
 
-static void run_fused_groupby(Compiler& c, const KeyPlan& kp, int len_idx, FusedAggResult& res, std::string& desc) {
-  const Shape& sh = c.shape;
-  const Args& args = c.args;
-  const int static_id = find_static_shape(sh);
-  const int64_t n = args.n_rows;
-  res.n_aggs = sh.n_aggs;
-  if (n == 0) { res.n_groups = 0; res.acc = dev_alloc(8); res.packed_keys = dev_alloc(8); return; }
-  if (kp.packed && kp.total_bits <= 12 && k::lds_agg_copies(1 << kp.total_bits, sh.n_aggs) > 0) {
-    const int G = 1 << kp.total_bits;
-    Buf cells = dev_alloc(sizeof(uint64_t) * (size_t)G * sh.n_aggs);
-    Buf oob = untrusted_key_bounds(c) ? dev_alloc_zero(8) : nullptr;      // key bounds nobody measured: the sink reports a group id outside the table
-    k::fused_lds_agg(sh, args, G, static_id, cells->as<uint64_t>(), oob ? oob->as<unsigned int>() : nullptr);
-    desc += std::string("fused_scan[") + jit::program_mode(static_id, args.n_rows) + "]+lds_table(G=" + std::to_string(G) + ",copies=" + std::to_string(k::lds_agg_copies(G, sh.n_aggs)) + ")";
-    compact_into(nullptr, cells->as<uint64_t>(), G, -1, sh.n_aggs, len_idx, res);
-    check_oob_flag(oob);
-    res.key_valid = nullptr;  // packed keys carry their own null codes
-    return;
-  }
-  // large inputs over many (packed) group ids: per-row atomics on the dense HBM table are bound by the device atomic
-  // rate just like the hash table -> partition + LDS aggregation on the packed id (kernels_partition.hip)
-  if (kp.packed && kp.total_bits > 12 && !(c.plan.flags & PLX_PLAN_NO_PARTITION) && n >= ((int64_t)1 << 24)) {
-    const double est = std::min((double)((uint64_t)1 << std::min(kp.total_bits, 40)), (double)n);
-    if (part_version() == 2) {
-      // second generation: direct-address LDS tables over the dense id when they fit (hash tables otherwise); a strided sample
-      // finds the heavy hitters, which are aggregated in the scatter pass instead of being scattered
-      std::vector<uint64_t> hot;
-      double est2 = est;
-      if (hot_keys_enabled() || kp.total_bits > 25) {
-        const int64_t S = kPartSampleRows;
-        double g_est = 1e18;
-        const int64_t d = sample_keys_cached(plain_key_column(c, kp), sh, args, static_id, len_idx, S, hot_keys_enabled() ? &hot : nullptr, &g_est, desc);
-        if (d >= 0) est2 = std::min(est, std::min(g_est, (double)n) * 1.3);
-        desc += "sample(distinct=" + std::to_string(d) + ",hot=" + std::to_string(hot.size()) + ")+";
-      }
-      if (c.plan.group_hint > 0) { est2 = std::min(est, c.plan.group_hint * 1.02 + 64.0); desc += "groups<=" + std::to_string((int64_t)c.plan.group_hint) + "(plan)+"; }
-      PartPlan2 p2;
-      k::SrcRange ranges[kMaxSrc];
-      source_ranges(c, ranges);
-      // (too many id bits for direct-address tables -> hash partitions of the packed id: its range is [0, 2^total_bits) by construction -- when the bounds behind the
-      // packing were measured, not guessed -- so ids of < 48 bits travel as 48-bit offsets, two rows a record: fused::kPackPair)
-      k::SrcRange id_rng;
-      if (kp.total_bits < 48 && !untrusted_key_bounds(c)) { id_rng.known = true; id_rng.mn = 0; id_rng.mx = (int64_t)(((uint64_t)1 << kp.total_bits) - 1); }
-      if (k::partition_plan2(sh, est2, kp.total_bits, len_idx, n, (int)hot.size(), &p2, ranges, &id_rng)) {
-        std::string pd;
-        Buf ok, okv, oacc;
-        const int64_t g = k::partitioned_agg2(sh, args, p2, static_id, hot, &ok, &okv, &oacc, &pd);
-        if (g >= 0) {
-          if (p2.check_src) mark_sources_verified(c);
-          res.n_groups = g; res.n_aggs = sh.n_aggs; res.packed_keys = ok; res.key_valid = nullptr; res.acc = oacc;   // packed ids carry their own null codes
-          desc += std::string("fused_scan[") + jit::program_mode(static_id, args.n_rows) + "]+" + pd;
-          return;
-        }
-        desc += g == -2 ? "v2-unavailable+" : "lds-overflow+";
-      }
-    }
-    PartitionPlan pp;
-    if (part_version() == 1 && k::partition_plan(sh, est, false, &pp)) {
-      std::string pd;
-      Buf ok, okv, oacc;
-      const int64_t g = k::partitioned_agg(sh, args, pp, static_id, &ok, &okv, &oacc, &pd);
-      if (g >= 0) {
-        res.n_groups = g; res.n_aggs = sh.n_aggs; res.packed_keys = ok; res.key_valid = nullptr; res.acc = oacc;   // packed ids carry their own null codes
-        desc += std::string("fused_scan[") + jit::program_mode(static_id, args.n_rows) + "]+" + pd;
-        return;
-      }
-      desc += "lds-overflow+";
-    }
-  }
-  if (kp.packed && kp.total_bits <= 28 && ((size_t)sh.n_aggs << (kp.total_bits + 3)) <= (size_t(8) << 30)) {
-    const int64_t G = (int64_t)1 << kp.total_bits;
-    Buf cells = dev_alloc(sizeof(uint64_t) * (size_t)(G + 1) * sh.n_aggs);
-    k::init_agg_cells(cells->as<uint64_t>(), G + 1, sh);
-    Buf oob = untrusted_key_bounds(c) ? dev_alloc_zero(8) : nullptr;
-    DenseTable t; t.acc = cells->as<unsigned long long>(); t.key_min = 0; t.n_groups = G; t.oob = oob ? oob->as<unsigned int>() : nullptr;
-    k::fused_dense_agg(sh, args, t, static_id);
-    desc += std::string("fused_scan[") + jit::program_mode(static_id, args.n_rows) + "]+dense_hbm_table(G=" + std::to_string(G) + ")";
-    compact_into(nullptr, cells->as<uint64_t>(), G, -1, sh.n_aggs, len_idx, res);
-    check_oob_flag(oob);
-    res.key_valid = nullptr;
-    return;
-  }
-  // hash table: size from a sampled distinct-count estimate, grow x4 on overflow
-  int log2_cap;
-  const int64_t S = (int64_t)1 << 22;
-  if (n <= 2 * S) log2_cap = std::max(10, ceil_log2_u64((uint64_t)n * 2));
-  else {
-    Args sa = args; sa.n_rows = S;
-    FusedAggResult tmp;
-    std::vector<uint64_t> hot;
-    const bool may_partition = !(c.plan.flags & PLX_PLAN_NO_PARTITION) && n >= ((int64_t)1 << 24);
-    const bool strided = may_partition && !kp.wide && part_version() == 2;
-    const int64_t Sd = strided || kp.wide ? kPartSampleRows : S;
-    double g_est = -1.0;
-    int64_t d = kp.wide ? run_wide_agg(sh, args, 21, kp.wide_nullable, tmp, true, kSampleBlocks, Sd)
-                        : (strided ? sample_keys_cached(plain_key_column(c, kp), sh, args, static_id, len_idx, Sd, hot_keys_enabled() ? &hot : nullptr, &g_est, desc)
-                                   : run_hash_agg(sh, sa, static_id, 23, len_idx, tmp, true));
-    double G = d < 0 ? 1e18 : (g_est >= 0.0 ? g_est : estimate_groups((double)d, (double)Sd));
-    G = std::min(G, (double)n);
-    const bool hinted = c.plan.group_hint > 0;
-    if (hinted) { G = std::min(c.plan.group_hint, (double)n); desc += "groups<=" + std::to_string((int64_t)c.plan.group_hint) + "(plan)+"; }
-    log2_cap = std::max(12, ceil_log2_u64((uint64_t)(G * 2.0) + 1));
-    desc += "sample(distinct=" + std::to_string(d) + "/" + std::to_string(Sd) + ")+";
-    // many rows, many groups: per-row global atomics are bound by the ~24 G/s device atomic rate; partition the
-    // rows and aggregate each partition in LDS instead (kernels_partition.hip)
-    // a wide (multi-column, unpackable) key takes the same partitioned path: records carry one word per key column, partitions come from the hash of the
-    // words + null mask, the LDS tables compare word by word (the reference row-encodes such keys: crates/polars-row, hash_keys.rs:334 RowEncodedKeys)
-    if (kp.wide && may_partition && part_version() == 2 && G >= 4096.0) {
-      k::SrcRange ranges[kMaxSrc];
-      source_ranges(c, ranges);
-      double plan_for = hinted ? G * 1.02 + 64.0 : G * 1.3;
-      for (int attempt = 0; attempt < 3; attempt++) {
-        PartPlan2 p2;
-        if (!k::partition_plan2(sh, plan_for, -1, len_idx, n, 0, &p2, ranges)) break;
-        std::string pd;
-        Buf ok, okv, oacc;
-        int64_t stride = 0;
-        const int64_t g = k::partitioned_agg2(sh, args, p2, static_id, {}, &ok, &okv, &oacc, &pd, nullptr, &stride);
-        if (g >= 0) {
-          if (p2.check_src) mark_sources_verified(c);
-          res.n_groups = g; res.n_aggs = sh.n_aggs; res.wide_words = ok; res.wide_valid = okv; res.wide_stride = stride; res.acc = oacc;
-          desc += std::string("fused_scan[") + jit::program_mode(static_id, args.n_rows) + "]+" + pd;
-          return;
-        }
-        if (g == -2) { desc += "v2-unavailable+"; break; }
-        desc += "lds-overflow(P=" + std::to_string(1u << p2.log2_parts) + ")+";
-        if (p2.log2_parts >= 9) break;
-        // a table filled up: the sample undercounted (clustered keys).  One more attempt at the LARGEST plan (512 partitions); if that overflows too the HBM table takes over --
-        // never a ladder of full scatter + aggregate passes over all rows
-        plan_for = std::max(plan_for * 2.0, (double)((uint64_t)p2.n_slots << 9) * 0.8);
-      }
-    }
-    if (!kp.wide && !(c.plan.flags & PLX_PLAN_NO_PARTITION) && G >= 4096.0 && n >= ((int64_t)1 << 24)) {
-      bool any_null = c.key >= 0 && c.nodes[c.key].nullable;
-      for (auto& a : c.aggs) if (a.second >= 0 && c.nodes[a.second].nullable) any_null = true;
-      if (part_version() == 2) {
-        k::SrcRange ranges[kMaxSrc];
-        source_ranges(c, ranges);
-        // A raw signed-integer key column scanned without a predicate: the scatter pass also records the exact key range, which is
-        // cached on the column like any other statistic -- the NEXT group-by / join on it can plan dense (direct-address) tables.
-        ColumnPtr stat_col;
-        if (sh.pred == kNone && kp.parts.size() == 1 && dtype_is_int(kp.parts[0].dtype) && kp.parts[0].dtype != PLX_U64) {
-          const AE* x = &c.plan.ae[kp.parts[0].expr];
-          while (x->kind == PLX_AE_ALIAS) x = &c.plan.ae[x->lhs];
-          if (x->kind == PLX_AE_COLUMN) { const int ci = c.df->find(x->name); if (ci >= 0 && c.df->cols[ci]->range_state == 0 && c.df->cols[ci]->len == n) stat_col = c.df->cols[ci]; }
-        }
-        // ... and once the exact range of such a key is known (learned that way, or computed): 64-bit keys spanning < 2^48 travel as 48-bit offsets, two rows a record
-        // (fused::kPackPair in hash mode; only ranges the library computed itself: a declared or assumed range is never used unchecked)
-        k::SrcRange key_rng;
-        if (kp.parts.size() == 1 && dtype_is_int(kp.parts[0].dtype) && kp.parts[0].dtype != PLX_U64) {
-          const AE* x = &c.plan.ae[kp.parts[0].expr];
-          while (x->kind == PLX_AE_ALIAS) x = &c.plan.ae[x->lhs];
-          if (x->kind == PLX_AE_COLUMN) {
-            const int ci = c.df->find(x->name);
-            if (ci >= 0 && c.df->cols[ci]->range_state == 1 && c.df->cols[ci]->range_trusted) { key_rng.known = true; key_rng.mn = c.df->cols[ci]->range_min; key_rng.mx = c.df->cols[ci]->range_max; }
-          }
-        }
-        // How many groups to plan for.  The estimate assumes equally likely keys; heavy hitters in the sample mean a heavy TAIL too, and a tail the sample
-        // undercounts badly (zipf 1.1 over 1e6 keys: 1.5e5 distinct keys in 2^20 sampled rows, 1e6 in 1e9 rows): with skew the tables are planned for 4 x the
-        // estimate.  A table that fills up anyway is reported by the aggregation pass; the plan is then doubled (more partitions) and the pass repeated -- never
-        // the per-row HBM-table path, which a skewed input turns into seconds of same-address atomics.
-        double plan_for = hinted ? G * 1.02 + 64.0 : (!hot.empty() && G < 1e17) ? G * 4.0 : G * 1.3;      // (a bound from the plan is not an estimate: no safety factor)
-        for (int attempt = 0; attempt < 3; attempt++) {
-          PartPlan2 p2;
-          if (!k::partition_plan2(sh, plan_for, -1, len_idx, n, (int)hot.size(), &p2, ranges, &key_rng)) {
-            if (attempt == 0 && !hot.empty() && k::partition_plan2(sh, G * 1.3, -1, len_idx, n, (int)hot.size(), &p2, ranges, &key_rng)) { /* 4 x does not fit 512 partitions: the plain estimate does */ }
-            else break;
-          }
-          std::string pd;
-          Buf ok, okv, oacc;
-          int64_t key_range[2] = {1, 0};
-          const int64_t g = k::partitioned_agg2(sh, args, p2, static_id, hot, &ok, &okv, &oacc, &pd, stat_col ? key_range : nullptr);
-          if (g >= 0) {
-            if (stat_col && key_range[0] <= key_range[1]) { stat_col->range_state = 1; stat_col->range_min = key_range[0]; stat_col->range_max = key_range[1]; stat_col->range_trusted = true; pd += "+key_range_learned"; }
-            if (p2.check_src) mark_sources_verified(c);
-            res.n_groups = g; res.n_aggs = sh.n_aggs; res.packed_keys = ok; res.key_valid = okv; res.acc = oacc;
-            desc += "hot=" + std::to_string(hot.size()) + "+" + std::string("fused_scan[") + jit::program_mode(static_id, args.n_rows) + "]+" + pd;
-            return;
-          }
-          if (g == -2) { desc += "v2-unavailable+"; break; }
-          desc += "lds-overflow(P=" + std::to_string(1u << p2.log2_parts) + ")+";
-          if (p2.log2_parts >= 9) break;
-          plan_for = std::max(plan_for * 2.0, (double)((uint64_t)p2.n_slots << p2.log2_parts) * 1.01);      // beyond what this plan's tables hold at all
-        }
-      }
-      if (part_version() == 1) {
-      PartitionPlan pp;
-      if (k::partition_plan(sh, G * 1.3, any_null, &pp)) {
-        std::string pd;
-        Buf ok, okv, oacc;
-        const int64_t g = k::partitioned_agg(sh, args, pp, static_id, &ok, &okv, &oacc, &pd);
-        if (g >= 0) {
-          res.n_groups = g; res.n_aggs = sh.n_aggs; res.packed_keys = ok; res.key_valid = okv; res.acc = oacc;
-          desc += std::string("fused_scan[") + jit::program_mode(static_id, args.n_rows) + "]+" + pd;
-          return;
-        }
-        desc += "lds-overflow+";
-      }
-      }   // first-generation kernels (PLX_PART_V=1 only)
-    }
-  }
-  for (int attempt = 0; attempt < 8; attempt++) {
-    int64_t g = kp.wide ? run_wide_agg(sh, args, log2_cap, kp.wide_nullable, res, false) : run_hash_agg(sh, args, static_id, log2_cap, len_idx, res, false);
+// ---- the fused group-by driver: run_fused_groupby chooses the route, each route is one function that says whether it produced the result ----
+namespace {
+// what the routes of one run share
+struct GroupByRun {
+  Compiler& c; const KeyPlan& kp; const Shape& sh; const Args& args;      // (sh, args: c.shape, c.args)
+  const int len_idx, static_id;
+  const bool may_partition;      // the plan allows the partitioned routes and the input is large enough for them to pay
+  FusedAggResult& res; std::string& desc;
+};
+// "fused_scan[<mode>]+": how the scan program in front of a sink was obtained
+std::string scan_tag(int static_id, int64_t n_rows) { return std::string("fused_scan[") + jit::program_mode(static_id, n_rows) + "]+"; }
+
+// the table-in-one-kernel routes end alike: compact the cells, then look at the flag the sink raises for a group id outside its table
+void finish_table(GroupByRun& q, const Buf& cells, int64_t G, const Buf& oob) {
+  compact_into(nullptr, cells->as<uint64_t>(), G, -1, q.sh.n_aggs, q.len_idx, q.res);
+  check_oob_flag(oob);
+  q.res.key_valid = nullptr;  // packed keys carry their own null codes
+}
+void lds_table(GroupByRun& q) {
+  const int G = 1 << q.kp.total_bits;
+  Buf cells = dev_alloc(sizeof(uint64_t) * (size_t)G * q.sh.n_aggs);
+  Buf oob = untrusted_key_bounds(q.c) ? dev_alloc_zero(8) : nullptr;      // key bounds nobody measured: the sink reports a group id outside the table
+  k::fused_lds_agg(q.sh, q.args, G, q.static_id, cells->as<uint64_t>(), oob ? oob->as<unsigned int>() : nullptr);
+  q.desc += scan_tag(q.static_id, q.args.n_rows) + "lds_table(G=" + std::to_string(G) + ",copies=" + std::to_string(k::lds_agg_copies(G, q.sh.n_aggs)) + ")";
+  finish_table(q, cells, G, oob);
+}
+void dense_hbm_table(GroupByRun& q) {
+  const int64_t G = (int64_t)1 << q.kp.total_bits;
+  Buf cells = dev_alloc(sizeof(uint64_t) * (size_t)(G + 1) * q.sh.n_aggs);
+  k::init_agg_cells(cells->as<uint64_t>(), G + 1, q.sh);
+  Buf oob = untrusted_key_bounds(q.c) ? dev_alloc_zero(8) : nullptr;
+  DenseTable t; t.acc = cells->as<unsigned long long>(); t.key_min = 0; t.n_groups = G; t.oob = oob ? oob->as<unsigned int>() : nullptr;
+  k::fused_dense_agg(q.sh, q.args, t, q.static_id);
+  q.desc += scan_tag(q.static_id, q.args.n_rows) + "dense_hbm_table(G=" + std::to_string(G) + ")";
+  finish_table(q, cells, G, oob);
+}
+
+// what a partitioned aggregation hands back as group keys
+enum PartKeys { kPackedIds /* carry their own null codes */, kKeysWithValidity, kWideWords };
+void take_partitioned(GroupByRun& q, PartKeys keys, int64_t g, const Buf& ok, const Buf& okv, const Buf& oacc, int64_t stride, const std::string& pd) {
+  FusedAggResult& res = q.res;
+  res.n_groups = g; res.n_aggs = q.sh.n_aggs; res.acc = oacc;
+  if (keys == kWideWords) { res.wide_words = ok; res.wide_valid = okv; res.wide_stride = stride; }
+  else { res.packed_keys = ok; res.key_valid = keys == kKeysWithValidity ? okv : nullptr; }
+  q.desc += scan_tag(q.static_id, q.args.n_rows) + pd;
+}
+// first-generation kernels (PLX_PART_V=1 only)
+bool partitioned_v1(GroupByRun& q, double est_groups, bool any_nullable, PartKeys keys) {
+  PartitionPlan pp;
+  if (!k::partition_plan(q.sh, est_groups, any_nullable, &pp)) return false;
+  std::string pd;
+  Buf ok, okv, oacc;
+  const int64_t g = k::partitioned_agg(q.sh, q.args, pp, q.static_id, &ok, &okv, &oacc, &pd);
+  if (g < 0) { q.desc += "lds-overflow+"; return false; }
+  take_partitioned(q, keys, g, ok, okv, oacc, 0, pd);
+  return true;
+}
+// second generation: what its three call sites differ in
+struct PartTry {
+  double plan_for = 0;                // groups the LDS tables are planned for
+  double fallback = 0;                // > 0: planned for instead, once, when `plan_for` fits no plan on the first attempt
+  int packed_bits = -1;               // > 0: the key is a dense packed id of that many bits
+  std::vector<uint64_t> hot;          // heavy hitters: aggregated in the scatter pass instead of being scattered
+  k::SrcRange ranges[kMaxSrc];        // source_ranges(): filled by the caller, which reads its other statistics after that call
+  k::SrcRange key_rng;                // exact range of the key / the packed id, where known
+  ColumnPtr stat_col;                 // the column that learns its key range from the scatter pass
+  int attempts = 3;                   // a table that fills up is reported by the aggregation pass: the plan grows and the pass is repeated
+  bool grow_to_largest = false;       // growth rule after an overflow, see below
+  PartKeys keys = kPackedIds;
+};
+bool partitioned_v2(GroupByRun& q, PartTry& t) {
+  for (int attempt = 0; attempt < t.attempts; attempt++) {
+    PartPlan2 p2;
+    auto plan = [&](double groups) { return k::partition_plan2(q.sh, groups, t.packed_bits, q.len_idx, q.args.n_rows, (int)t.hot.size(), &p2, t.ranges, &t.key_rng); };
+    if (!plan(t.plan_for) && !(attempt == 0 && t.fallback > 0 && plan(t.fallback))) return false;
+    std::string pd;
+    Buf ok, okv, oacc;
+    int64_t key_range[2] = {1, 0}, stride = 0;
+    const int64_t g = k::partitioned_agg2(q.sh, q.args, p2, q.static_id, t.hot, &ok, &okv, &oacc, &pd, t.stat_col ? key_range : nullptr, &stride);
     if (g >= 0) {
-      desc += std::string("fused_scan[") + jit::program_mode(kp.wide ? -1 : static_id, args.n_rows) + "]+" + (kp.wide ? "wide_hash_hbm_table(words=" + std::to_string(sh.n_keys + (kp.wide_nullable ? 1 : 0)) + ",cap=2^" : "hash_hbm_table(cap=2^") + std::to_string(log2_cap) + ")";
+      if (t.stat_col && key_range[0] <= key_range[1]) { t.stat_col->range_state = 1; t.stat_col->range_min = key_range[0]; t.stat_col->range_max = key_range[1]; t.stat_col->range_trusted = true; pd += "+key_range_learned"; }
+      if (p2.check_src) mark_sources_verified(q.c);
+      if (t.keys == kKeysWithValidity) q.desc += "hot=" + std::to_string(t.hot.size()) + "+";      // (as found: the single-key site alone names its hot list here)
+      take_partitioned(q, t.keys, g, ok, okv, oacc, stride, pd);
+      return true;
+    }
+    if (g == -2) { q.desc += "v2-unavailable+"; return false; }
+    q.desc += t.attempts == 1 ? "lds-overflow+" : "lds-overflow(P=" + std::to_string(1u << p2.log2_parts) + ")+";      // (as found: the one-attempt site does not name its P)
+    if (p2.log2_parts >= 9) return false;
+    // a table filled up: the sample undercounted (clustered keys).  grow_to_largest: one more attempt at the LARGEST plan (512 partitions); if that overflows too the HBM
+    // table takes over -- never a ladder of full scatter + aggregate passes over all rows.  Otherwise: beyond what this plan's tables hold at all.
+    // (as found: 0.8 of the largest plan's slots for wide keys, 1.01 of this plan's slots for a single key)
+    t.plan_for = std::max(t.plan_for * 2.0, t.grow_to_largest ? (double)((uint64_t)p2.n_slots << 9) * 0.8 : (double)((uint64_t)p2.n_slots << p2.log2_parts) * 1.01);
+  }
+  return false;
+}
+
+// large inputs over many (packed) group ids: per-row atomics on the dense HBM table are bound by the device atomic
+// rate just like the hash table -> partition + LDS aggregation on the packed id (kernels_partition.hip)
+bool partitioned_packed_ids(GroupByRun& q) {
+  const int bits = q.kp.total_bits;
+  const int64_t n = q.args.n_rows;
+  const double est = std::min((double)((uint64_t)1 << std::min(bits, 40)), (double)n);
+  if (part_version() != 2) return partitioned_v1(q, est, false, kPackedIds);
+  // second generation: direct-address LDS tables over the dense id when they fit (hash tables otherwise); a strided sample
+  // finds the heavy hitters, which are aggregated in the scatter pass instead of being scattered
+  PartTry t;
+  t.plan_for = est; t.packed_bits = bits; t.attempts = 1;
+  if (hot_keys_enabled() || bits > 25) {
+    double g_est = 1e18;
+    const int64_t d = sample_keys_cached(plain_key_column(q.c, q.kp), q.sh, q.args, q.static_id, q.len_idx, kPartSampleRows, hot_keys_enabled() ? &t.hot : nullptr, &g_est, q.desc);
+    if (d >= 0) t.plan_for = std::min(est, std::min(g_est, (double)n) * 1.3);
+    q.desc += "sample(distinct=" + std::to_string(d) + ",hot=" + std::to_string(t.hot.size()) + ")+";
+  }
+  const double hint = q.c.plan.group_hint;
+  if (hint > 0) { t.plan_for = std::min(est, hint * 1.02 + 64.0); q.desc += "groups<=" + std::to_string((int64_t)hint) + "(plan)+"; }
+  source_ranges(q.c, t.ranges);
+  // (too many id bits for direct-address tables -> hash partitions of the packed id: its range is [0, 2^total_bits) by construction -- when the bounds behind the
+  // packing were measured, not guessed -- so ids of < 48 bits travel as 48-bit offsets, two rows a record: fused::kPackPair)
+  if (bits < 48 && !untrusted_key_bounds(q.c)) { t.key_rng.known = true; t.key_rng.mn = 0; t.key_rng.mx = (int64_t)(((uint64_t)1 << bits) - 1); }
+  return partitioned_v2(q, t);
+}
+
+// hash table: size from a sampled distinct-count estimate.  groups < 0: an input too small to sample (and to partition)
+struct HashSizing { double groups = -1.0; std::vector<uint64_t> hot; int log2_cap = 0; };
+HashSizing size_hash_table(GroupByRun& q) {
+  const KeyPlan& kp = q.kp;
+  const int64_t n = q.args.n_rows;
+  HashSizing hs;
+  const int64_t S = (int64_t)1 << 22;
+  if (n <= 2 * S) { hs.log2_cap = std::max(10, ceil_log2_u64((uint64_t)n * 2)); return hs; }
+  Args sa = q.args; sa.n_rows = S;
+  FusedAggResult tmp;
+  const bool strided = q.may_partition && !kp.wide && part_version() == 2;
+  const int64_t Sd = strided || kp.wide ? kPartSampleRows : S;
+  double g_est = -1.0;
+  int64_t d = kp.wide ? run_wide_agg(q.sh, q.args, 21, kp.wide_nullable, tmp, true, kSampleBlocks, Sd)
+                      : (strided ? sample_keys_cached(plain_key_column(q.c, kp), q.sh, q.args, q.static_id, q.len_idx, Sd, hot_keys_enabled() ? &hs.hot : nullptr, &g_est, q.desc)
+                                 : run_hash_agg(q.sh, sa, q.static_id, 23, q.len_idx, tmp, true));
+  double G = d < 0 ? 1e18 : (g_est >= 0.0 ? g_est : estimate_groups((double)d, (double)Sd));
+  G = std::min(G, (double)n);
+  const double hint = q.c.plan.group_hint;
+  if (hint > 0) { G = std::min(hint, (double)n); q.desc += "groups<=" + std::to_string((int64_t)hint) + "(plan)+"; }
+  hs.groups = G;
+  hs.log2_cap = std::max(12, ceil_log2_u64((uint64_t)(G * 2.0) + 1));
+  q.desc += "sample(distinct=" + std::to_string(d) + "/" + std::to_string(Sd) + ")+";
+  return hs;
+}
+// many rows, many groups: per-row global atomics are bound by the ~24 G/s device atomic rate; partition the
+// rows and aggregate each partition in LDS instead (kernels_partition.hip)
+// a wide (multi-column, unpackable) key takes the same partitioned path: records carry one word per key column, partitions come from the hash of the
+// words + null mask, the LDS tables compare word by word (the reference row-encodes such keys: crates/polars-row, hash_keys.rs:334 RowEncodedKeys)
+bool partitioned_wide_keys(GroupByRun& q, double G) {
+  if (part_version() != 2) return false;
+  PartTry t;
+  source_ranges(q.c, t.ranges);
+  t.plan_for = q.c.plan.group_hint > 0 ? G * 1.02 + 64.0 : G * 1.3;
+  t.grow_to_largest = true; t.keys = kWideWords;
+  return partitioned_v2(q, t);
+}
+bool partitioned_single_key(GroupByRun& q, double G, std::vector<uint64_t>& hot) {
+  Compiler& c = q.c;
+  if (part_version() != 2) {
+    bool any_null = c.key >= 0 && c.nodes[c.key].nullable;
+    for (auto& a : c.aggs) if (a.second >= 0 && c.nodes[a.second].nullable) any_null = true;
+    return partitioned_v1(q, G * 1.3, any_null, kKeysWithValidity);
+  }
+  PartTry t;
+  source_ranges(c, t.ranges);
+  ColumnPtr key_col;      // the frame column behind a single plain signed-integer key
+  const KeyPart* k0 = q.kp.parts.size() == 1 ? &q.kp.parts[0] : nullptr;
+  if (k0 && dtype_is_int(k0->dtype) && k0->dtype != PLX_U64)
+    if (const AE* x = plain_column(c.plan, k0->expr)) { const int ci = c.df->find(x->name); if (ci >= 0) key_col = c.df->cols[ci]; }
+  // A raw signed-integer key column scanned without a predicate: the scatter pass also records the exact key range, which is
+  // cached on the column like any other statistic -- the NEXT group-by / join on it can plan dense (direct-address) tables.
+  if (key_col && q.sh.pred == kNone && key_col->range_state == 0 && key_col->len == q.args.n_rows) t.stat_col = key_col;
+  // ... and once the exact range of such a key is known (learned that way, or computed): 64-bit keys spanning < 2^48 travel as 48-bit offsets, two rows a record
+  // (fused::kPackPair in hash mode; only ranges the library computed itself: a declared or assumed range is never used unchecked)
+  if (key_col && key_col->range_state == 1 && key_col->range_trusted) { t.key_rng.known = true; t.key_rng.mn = key_col->range_min; t.key_rng.mx = key_col->range_max; }
+  // How many groups to plan for.  The estimate assumes equally likely keys; heavy hitters in the sample mean a heavy TAIL too, and a tail the sample
+  // undercounts badly (zipf 1.1 over 1e6 keys: 1.5e5 distinct keys in 2^20 sampled rows, 1e6 in 1e9 rows): with skew the tables are planned for 4 x the
+  // estimate.  A table that fills up anyway is reported by the aggregation pass; the plan is then doubled (more partitions) and the pass repeated -- never
+  // the per-row HBM-table path, which a skewed input turns into seconds of same-address atomics.
+  t.hot = std::move(hot);
+  t.plan_for = c.plan.group_hint > 0 ? G * 1.02 + 64.0 : (!t.hot.empty() && G < 1e17) ? G * 4.0 : G * 1.3;      // (a bound from the plan is not an estimate: no safety factor)
+  if (!t.hot.empty()) t.fallback = G * 1.3;      // 4 x does not fit 512 partitions: the plain estimate does
+  t.keys = kKeysWithValidity;
+  return partitioned_v2(q, t);
+}
+// hash / wide-hash HBM table of 2^log2_cap slots, grown x4 on overflow
+void hash_hbm_table(GroupByRun& q, int log2_cap) {
+  const KeyPlan& kp = q.kp;
+  for (int attempt = 0; attempt < 8; attempt++) {
+    int64_t g = kp.wide ? run_wide_agg(q.sh, q.args, log2_cap, kp.wide_nullable, q.res, false) : run_hash_agg(q.sh, q.args, q.static_id, log2_cap, q.len_idx, q.res, false);
+    if (g >= 0) {
+      q.desc += scan_tag(kp.wide ? -1 : q.static_id, q.args.n_rows) + (kp.wide ? "wide_hash_hbm_table(words=" + std::to_string(q.sh.n_keys + (kp.wide_nullable ? 1 : 0)) + ",cap=2^" : "hash_hbm_table(cap=2^") + std::to_string(log2_cap) + ")";
       return;
     }
     log2_cap += 2;
-    desc += "grow+";
+    q.desc += "grow+";
     PLX_REQUIRE(log2_cap <= 34, PLX_ERR_OOM, "group-by hash table would exceed 2^34 slots");
   }
   fail(PLX_ERR_OOM, "group-by hash table kept overflowing");
+}
+}  // namespace
+
+static void run_fused_groupby(Compiler& c, const KeyPlan& kp, int len_idx, FusedAggResult& res, std::string& desc) {
+  const Shape& sh = c.shape;
+  const int64_t n = c.args.n_rows;
+  res.n_aggs = sh.n_aggs;
+  if (n == 0) { res.n_groups = 0; res.acc = dev_alloc(8); res.packed_keys = dev_alloc(8); return; }
+  GroupByRun q{c, kp, sh, c.args, len_idx, find_static_shape(sh), !(c.plan.flags & PLX_PLAN_NO_PARTITION) && n >= ((int64_t)1 << 24), res, desc};
+  if (kp.packed && kp.total_bits <= 12 && k::lds_agg_copies(1 << kp.total_bits, sh.n_aggs) > 0) return lds_table(q);
+  if (kp.packed && kp.total_bits > 12 && q.may_partition && partitioned_packed_ids(q)) return;
+  if (kp.packed && kp.total_bits <= 28 && ((size_t)sh.n_aggs << (kp.total_bits + 3)) <= (size_t(8) << 30)) return dense_hbm_table(q);
+  HashSizing hs = size_hash_table(q);
+  if (q.may_partition && hs.groups >= 4096.0 && (kp.wide ? partitioned_wide_keys(q, hs.groups) : partitioned_single_key(q, hs.groups, hs.hot))) return;
+  hash_hbm_table(q, hs.log2_cap);
 }
 
 // Output columns are allocated here and filled by ONE finalize_batch launch per query
@@ -1324,12 +1335,6 @@ static void dump_compiled(ProgramDump* dump, const char* kind, const Plan& plan,
                           const std::vector<FinalSpec>& specs, const std::vector<int>& out_exprs, int len_idx, int first_idx, bool maintain_order) {
   if (dump) dump->json = compiled_json(kind, plan, c, kp, agg_nodes, specs, out_exprs, len_idx, first_idx, maintain_order);
 }
-// the plain column behind any aliases of expression `e`, or null when `e` is anything else
-static const AE* plain_column(const Plan& plan, int e) {
-  const AE* x = &plan.ae[e];
-  while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs];
-  return x->kind == PLX_AE_COLUMN ? x : nullptr;
-}
 // conjunction of the predicates `preds` lowered into `c`: its node, or -1 when there is none
 static int and_predicates(Compiler& c, const std::vector<int>& preds) {
   int p = -1;
@@ -1377,6 +1382,12 @@ static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& pr
   return true;
 }
 
+// the columns' bounds that the planner had only ASSUMED (assume_range) are forgotten, and never guessed again; returns whether there was any
+static bool forget_assumed_bounds(const std::vector<ColumnPtr>& cols) {
+  bool guessed = false;
+  for (auto& col : cols) if (col->range_assumed) { col->range_state = 0; col->range_trusted = true; col->range_assumed = false; col->range_verified = false; col->no_assume = true; std::atomic_store(&col->key_sample, std::shared_ptr<void>()); guessed = true; }
+  return guessed;
+}
 // GroupBy(keys, aggregations) over [Filter]* over `src`
 static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& preds, const FramePtr& src, FramePtr& out, Shape* shape_out, int* sid_out,
                           std::string* why, bool compile_only) {
@@ -1405,9 +1416,7 @@ static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& p
   } catch (const Error& e) {
     // a row outside bounds the planner had only ASSUMED (assume_range): forget the guesses, never guess about these columns again, and run the query once more --
     // its statistics now come from exact passes.  (Bounds the caller declared are the caller's promise: that error stands.)
-    bool guessed = false;
-    for (auto& col : c.cols) if (col->range_assumed) { col->range_state = 0; col->range_trusted = true; col->range_assumed = false; col->range_verified = false; col->no_assume = true; std::atomic_store(&col->key_sample, std::shared_ptr<void>()); guessed = true; }
-    if (!guessed || e.code != PLX_ERR_INVALID) throw;
+    if (!forget_assumed_bounds(c.cols) || e.code != PLX_ERR_INVALID) throw;
     plan.desc += "AssumedBoundsViolated{exact statistics, second run}; ";
     return fused_groupby(plan, node, preds, src, out, shape_out, sid_out, why, compile_only);
   }
@@ -2121,9 +2130,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
     } catch (const Error& e) {
       // a row outside bounds the planner had only ASSUMED for the probe key / value columns (lower_keys(ca) and source_ranges run outside fused_groupby's own handler): forget
       // the guesses, never guess about these columns again, and run the whole join once more from exact statistics -- like fused_groupby does
-      bool guessed = false;
-      for (auto& col : ca.cols) if (col->range_assumed) { col->range_state = 0; col->range_trusted = true; col->range_assumed = false; col->range_verified = false; col->no_assume = true; std::atomic_store(&col->key_sample, std::shared_ptr<void>()); guessed = true; }
-      if (!guessed || e.code != PLX_ERR_INVALID) throw;
+      if (!forget_assumed_bounds(ca.cols) || e.code != PLX_ERR_INVALID) throw;
       plan.desc += "AssumedBoundsViolated{exact statistics, second run}; ";
       return fused_join_groupby(plan, gb, out, why, shapes_out, compile_only);
     }
@@ -2449,7 +2456,7 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
             cand->values = dev_alloc(values_bytes(PLX_U32, std::max<int64_t>(sel.n_out, 1)));
             k::compact_by_ballots(sel, k::CompactCols{}, cand->values->as<uint32_t>());
             PLX_HIP(hipStreamSynchronize(stream()));
-            cand_how = std::string("fused_scan[") + jit::program_mode(sid, np) + "]+direct hits (ballots -> row ids)";
+            cand_how = scan_tag(sid, np) + "direct hits (ballots -> row ids)";
           }
         }
       } else if (!ppreds.empty()) {
