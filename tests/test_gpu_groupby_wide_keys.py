@@ -4,6 +4,8 @@ by word (partition2_device.hpp: process_wide).  Checked against numpy / pandas o
 import numpy as np
 import pytest
 
+from groupby_route_inputs import assert_groups_equal, reference, sample_rows
+
 pytestmark = pytest.mark.gpu
 
 
@@ -87,9 +89,8 @@ def test_wide_key_table_overflow_plans_more_partitions(pl, monkeypatch):
     rng = np.random.default_rng(203)
     n, G = 17_000_003, 900_000
     g = rng.integers(0, G, n)
-    per, stride = ((1 << 20) // 8) & ~127, (n // 8) & ~127
-    for b in range(8):
-        g[b * stride: b * stride + per] = rng.integers(0, 5000, per)                           # what the planner samples: ~5000 groups
+    sampled = sample_rows(n)
+    g[sampled] = rng.integers(0, 5000, len(sampled))                                           # what the planner samples: ~5000 groups
     ka = rng.integers(-(1 << 62), 1 << 62, G).astype(np.int64)
     kb = rng.integers(-(1 << 62), 1 << 62, G).astype(np.int64)
     v = rng.integers(0, 100, n).astype(np.int64)
@@ -98,6 +99,8 @@ def test_wide_key_table_overflow_plans_more_partitions(pl, monkeypatch):
     plan = pl.last_plan()
     assert plan.count("lds-overflow(P=") == 1 and "P=512" in plan and "lds_wide_key_table" in plan, plan
     assert out.height == len(np.unique(g)) and int(out["s"].to_numpy().sum()) == int(v.sum()) and int(out["len"].to_numpy().sum()) == n
+    ref = reference([ka[g], kb[g]], [None, None], [("s", "sum", (v, None)), ("len", "len", None)])
+    assert_groups_equal({c: out[c]._download() for c in out.columns}, ref, ["a", "b"])        # every group, not only the totals: the retry put no row into a wrong one
 
 
 def test_wide_keys_with_one_heavy_group(pl):
