@@ -357,7 +357,12 @@ typedef enum plx_ir_kind {
   PLX_IR_SELECT = 2,  /* input, exprs */
   PLX_IR_HSTACK = 3,  /* input, exprs (with_columns) */
   PLX_IR_GROUPBY = 4, /* input, keys, exprs (aggs), maintain_order */
-  PLX_IR_JOIN = 5,    /* input, input_right, keys (left_on), keys_right (right_on), how, suffix, maintain_order (plx_join_order) */
+  PLX_IR_JOIN = 5,    /* input, input_right, keys (left_on), keys_right (right_on), how, suffix, maintain_order (plx_join_order).  Key shapes that are joined:
+                       * 1 key column; 2..8 key columns of integer, Boolean or float dtype, where column j has the same dtype on both sides (more than 8:
+                       * PLX_ERR_UNSUPPORTED naming the limit).  A null in any key part makes the row's key null: it matches nothing.  Floats compare in the
+                       * total order (NaN == NaN, -0 == +0).  The route is visible in the plan description: "packed N key columns into Int64; hash_join[...]"
+                       * when the joint value ranges bit-pack into 63 bits, "wide_hash_join[words=N (why), ...]" / wide_hash_semi_join / wide_hash_anti_join
+                       * otherwise (a table of row ids whose key words are compared column by column: any dtype mix, any value range). */
   PLX_IR_SORT = 6,    /* input, keys (by), sort_descending[n_keys], sort_nulls_last[n_keys] (IR::Sort; always stable) */
   PLX_IR_SLICE = 7    /* input, slice_offset (negative: from the end), slice_len (IR::Slice); directly above a Sort it becomes top-k */
 } plx_ir_kind;

@@ -2368,6 +2368,7 @@ static FramePtr exec_groupby_materialised(Plan& plan, const IRN& n, const FrameP
 // each partition tested against an LDS filter of its region of the table) or -- joins that keep most probe rows, left joins, small tables -- into the one-pass
 // row-id compaction (k::fused_filter); join::join_pairs then looks every CANDIDATE up once and lays the (probe row, build row) pairs out, and the payload columns
 // `want` names (null: all) are gathered at them, several columns per launch.  PLX_JOIN_MATERIALISE: 0 = never, 2 = any size (tests), default from 2^24 probe rows.
+static int join_wide_keys_mode() { const char* e = getenv("PLX_JOIN_WIDE_KEYS"); return e && e[0] == '0' ? 0 : e && e[0] == '2' ? 2 : 1; }   // (read at every join: the tests switch it)
 static int join_materialise_mode() { const char* e = getenv("PLX_JOIN_MATERIALISE"); return e && e[0] == '0' ? 0 : e && e[0] == '2' ? 2 : 1; }
 static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::string>* want, FramePtr& out, std::string* why, uint64_t* build_rows_out = nullptr, int* build_side_out = nullptr) {
   auto no = [&](const char* m) { if (why) *why = m; return false; };
@@ -2602,6 +2603,8 @@ static FramePtr exec_join(Plan& plan, const IRN& n) {
   FramePtr right = exec_node(plan, n.input_right);
   PLX_REQUIRE(!n.keys.empty() && n.keys.size() == n.keys_right.size(), PLX_ERR_INVALID, "join: left_on / right_on length mismatch");
   ColumnPtr lk, rk;
+  std::vector<ColumnPtr> lraw, rraw;   // multi-column keys: the key columns as they are
+  std::string wide_why;                // ... and why they are not packed into one Int64 (empty: they are)
   std::string packed_desc;
   if (n.keys.size() == 1) {
     lk = broadcast(eval(plan, n.keys[0], *left, nullptr), left->height);
@@ -2611,25 +2614,35 @@ static FramePtr exec_join(Plan& plan, const IRN& n) {
     // keys are instead packed into ONE Int64 using the joint value range of both sides:
     //   packed = sum_j (key_j - min_j) * stride_j,  stride_j = prod_{i>j} (max_i - min_i + 1)
     // A null in any key column makes the packed key null, i.e. the row never matches (nulls_equal = false).
+    // Keys that do not pack -- a Float32 / Float64 / UInt64 part, one column beyond 63 bits, a product of the spans beyond 9e18 -- take the wide route instead: a table
+    // of row ids whose key words are compared column by column at the build rows (join::join_indices_wide).  PLX_JOIN_WIDE_KEYS: 2 = every multi-column key, 0 = never.
+    const int wide_mode = join_wide_keys_mode();
     std::vector<ColumnPtr> lks, rks;
     std::vector<int64_t> mins, spans;
+    auto no_pack = [&](const std::string& error, const std::string& why) { PLX_REQUIRE(wide_mode != 0, PLX_ERR_UNSUPPORTED, error); wide_why = why; };
+    if (wide_mode == 2) wide_why = "PLX_JOIN_WIDE_KEYS=2";
     for (size_t j = 0; j < n.keys.size(); j++) {
       ColumnPtr a = broadcast(eval(plan, n.keys[j], *left, nullptr), left->height);
       ColumnPtr b = broadcast(eval(plan, n.keys_right[j], *right, nullptr), right->height);
       PLX_REQUIRE(a->dtype == b->dtype, PLX_ERR_INVALID, "join keys have different dtypes");
-      PLX_REQUIRE(dtype_is_int(a->dtype) || a->dtype == PLX_BOOL, PLX_ERR_UNSUPPORTED, "multi-column join keys must be integer / boolean / dictionary codes on this path");
-      if (a->dtype != PLX_I64) { PLX_REQUIRE(a->dtype != PLX_U64, PLX_ERR_UNSUPPORTED, "multi-column join on UInt64 keys"); a = ops::cast(a, PLX_I64); b = ops::cast(b, PLX_I64); }
+      lraw.push_back(a); rraw.push_back(b);
+      if (!wide_why.empty()) continue;
+      if (!(dtype_is_int(a->dtype) || a->dtype == PLX_BOOL)) { no_pack("multi-column join keys must be integer / boolean / dictionary codes on this path", std::string(a->dtype == PLX_F32 ? "Float32" : a->dtype == PLX_F64 ? "Float64" : dtype_name(a->dtype)) + " key part"); continue; }
+      if (a->dtype == PLX_U64) { no_pack("multi-column join on UInt64 keys", "UInt64 key part"); continue; }
+      if (a->dtype != PLX_I64) { a = ops::cast(a, PLX_I64); b = ops::cast(b, PLX_I64); }
       int64_t amn = 0, amx = 0, bmn = 0, bmx = 0;
       const bool ha = ops::int_range(a, &amn, &amx), hb = ops::int_range(b, &bmn, &bmx);
       int64_t mn = ha ? amn : bmn, mx = ha ? amx : bmx;
       if (ha && hb) { mn = std::min(amn, bmn); mx = std::max(amx, bmx); }
       if (!ha && !hb) { mn = 0; mx = 0; }
-      PLX_REQUIRE((double)mx - (double)mn < 9e18, PLX_ERR_UNSUPPORTED, "multi-column join keys span more than 63 bits");
+      if (!((double)mx - (double)mn < 9e18)) { no_pack("multi-column join keys span more than 63 bits", "key part " + std::to_string(j) + " spans more than 63 bits"); continue; }
       lks.push_back(a); rks.push_back(b); mins.push_back(mn); spans.push_back(mx - mn + 1);
     }
-    double total = 1;
-    for (int64_t sp : spans) total *= (double)sp;
-    PLX_REQUIRE(total < 9.0e18, PLX_ERR_UNSUPPORTED, "multi-column join keys do not pack into 63 bits (needs row encoding)");
+    if (wide_why.empty()) {
+      double total = 1;
+      for (int64_t sp : spans) total *= (double)sp;
+      if (!(total < 9.0e18)) no_pack("multi-column join keys do not pack into 63 bits (needs row encoding)", "key spans do not pack into 63 bits");
+    }
     auto pack = [&](std::vector<ColumnPtr>& ks) {
       ColumnPtr acc;
       int64_t stride = 1;
@@ -2642,13 +2655,19 @@ static FramePtr exec_join(Plan& plan, const IRN& n) {
       }
       return acc;
     };
-    lk = pack(lks); rk = pack(rks);
-    packed_desc = "packed " + std::to_string(n.keys.size()) + " key columns into Int64; ";
+    if (wide_why.empty()) {
+      lk = pack(lks); rk = pack(rks);
+      packed_desc = "packed " + std::to_string(n.keys.size()) + " key columns into Int64; ";
+    }
   }
   ColumnPtr li, ri;
   std::string d;
   bool dup_build_keys = false;
-  join::join_indices(n.how, lk, rk, li, ri, &d, &dup_build_keys);
+  if (!wide_why.empty()) {
+    join::join_indices_wide(n.how, lraw, rraw, li, ri, &d, &dup_build_keys);
+    const size_t at = d.find(", build=");     // "wide_hash_join[words=N, build=...": the reason goes behind the word count
+    if (at != std::string::npos) d.insert(at, " (" + wide_why + ")");
+  } else join::join_indices(n.how, lk, rk, li, ri, &d, &dup_build_keys);
   d = packed_desc + d;
   if (n.maintain_order != PLX_JOIN_ORDER_NONE && n.how != PLX_JOIN_SEMI && n.how != PLX_JOIN_ANTI) {
     // join_indices emits at scanned offsets: probe order; its chains (duplicate build keys) are newest first.  It builds on the right unless the left side is not the larger one of an inner join.

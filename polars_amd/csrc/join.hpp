@@ -1,9 +1,10 @@
-// join.hpp -- hash join on one key column pair (kernels_join.hip).
+// join.hpp -- hash join on one key column pair (kernels_join.hip) or on a key of several columns (kernels_join_wide.hip).
 // Replaces polars-ops/src/frame/join/hash_join/{single_keys.rs:16-167 (build_tables),
 // single_keys_inner.rs:11-149 (probe_inner / hash_join_tuples_inner),
 // single_keys_left.rs:106-195, single_keys_dispatch.rs:234-357,476-553}.
 #pragma once
 #include <string>
+#include <vector>
 
 #include "core.hpp"
 #include "fused.hpp"
@@ -14,6 +15,10 @@ namespace join {
 // (left_idx, right_idx) as PLX_U32 columns; LEFT join: right_idx nullable.  Pairs come out in probe order (the probe side is the left one unless an inner join's
 // left side is not the larger one); *dup_build_keys (may be null; inner / left) = the build side repeats a key, so the pairs of one probe row are in chain order.
 void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys = nullptr);
+// The same contract on a key of 2..8 columns of any integer / Boolean / float dtype (kernels_join_wide.hip; column j has one dtype on both sides, a null in any part makes
+// the row's key null).  The table holds row ids, the key words are compared at the build columns; *desc = "wide_hash_join[words=N, ...]" / wide_hash_semi_join / wide_hash_anti_join.
+void join_indices_wide(int how, const std::vector<ColumnPtr>& left_keys, const std::vector<ColumnPtr>& right_keys, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc,
+                       bool* dup_build_keys = nullptr);
 
 // Pairs of an inner / left join from a build table the fused build scan filled (fused::JoinAggTable: unique keys, or chains of rows per key) over a candidate
 // list of probe rows (`cand`: PLX_U32, null = every row of probe_key).  Pair order = candidate order; a left join keeps every candidate (build_idx nullable).

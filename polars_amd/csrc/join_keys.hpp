@@ -1,0 +1,45 @@
+// join_keys.hpp -- how the join kernels read a key column (device-only header shared by kernels_join.hip and kernels_join_wide.hip).
+// A key is read in its physical dtype and widened to one 64-bit word in registers (no materialised 64-bit key copy); floats are
+// canonicalised (-0 -> +0, one NaN: total_ord.rs:40-48) so that equal keys have equal words.
+#pragma once
+#include "dev.hpp"
+#include "core.hpp"
+
+namespace plx {
+namespace join {
+
+constexpr uint64_t kEmpty = ~0ull;
+constexpr uint32_t kNoRow = 0xffffffffu;
+constexpr uint64_t kRandomOdd = 0x55fbfd6bfc5458e9ull;
+
+struct KeyCol {
+  const void* values;
+  const uint64_t* validity;
+  int dtype;
+  int64_t n;
+};
+
+__device__ __forceinline__ uint64_t load_key(const KeyCol& kc, int64_t i) {
+  switch (kc.dtype) {
+    case PLX_I8: return (uint64_t)(long long)reinterpret_cast<const int8_t*>(kc.values)[i];
+    case PLX_I16: return (uint64_t)(long long)reinterpret_cast<const int16_t*>(kc.values)[i];
+    case PLX_I32: return (uint64_t)(long long)reinterpret_cast<const int32_t*>(kc.values)[i];
+    case PLX_U8: return reinterpret_cast<const uint8_t*>(kc.values)[i];
+    case PLX_U16: return reinterpret_cast<const uint16_t*>(kc.values)[i];
+    case PLX_U32: return reinterpret_cast<const uint32_t*>(kc.values)[i];
+    case PLX_F32: { float f = reinterpret_cast<const float*>(kc.values)[i]; double d = (double)f; return (d != d) ? 0x7ff8000000000000ull : (uint64_t)__double_as_longlong(d + 0.0); }
+    case PLX_F64: { double d = reinterpret_cast<const double*>(kc.values)[i]; return (d != d) ? 0x7ff8000000000000ull : (uint64_t)__double_as_longlong(d + 0.0); }
+    case PLX_BOOL: return (reinterpret_cast<const uint64_t*>(kc.values)[i >> 6] >> (i & 63)) & 1;
+    default: return reinterpret_cast<const uint64_t*>(kc.values)[i];
+  }
+}
+__device__ __forceinline__ bool key_valid(const KeyCol& kc, int64_t i) { return !kc.validity || ((kc.validity[i >> 6] >> (i & 63)) & 1); }
+
+inline KeyCol key_col(const ColumnPtr& c) { KeyCol kc; kc.values = c->data(); kc.validity = c->valid_words(); kc.dtype = c->dtype; kc.n = c->len; return kc; }
+inline int ceil_log2(uint64_t x) { int b = 0; while ((1ull << b) < x) b++; return b; }
+
+// semi / anti: out_probe[offsets[i]] = i for every probe row with counts[i] != 0 (join_emit_kept_kernel, kernels_join.hip), on the current stream
+void emit_kept_rows(const uint32_t* counts, const uint64_t* offsets, int64_t n, uint32_t* out_probe);
+
+}  // namespace join
+}  // namespace plx

@@ -16,6 +16,7 @@
 #include "dev.hpp"
 #include "fused.hpp"
 #include "join.hpp"
+#include "join_keys.hpp"
 #include "kernels.hpp"
 #include "ops.hpp"
 #include "scan.hpp"
@@ -25,33 +26,6 @@ namespace join {
 
 using namespace dev;
 using k::kBlock;
-
-constexpr uint64_t kEmpty = ~0ull;
-constexpr uint32_t kNoRow = 0xffffffffu;
-constexpr uint64_t kRandomOdd = 0x55fbfd6bfc5458e9ull;
-
-struct KeyCol {
-  const void* values;
-  const uint64_t* validity;
-  int dtype;
-  int64_t n;
-};
-
-__device__ __forceinline__ uint64_t load_key(const KeyCol& kc, int64_t i) {
-  switch (kc.dtype) {
-    case PLX_I8: return (uint64_t)(long long)reinterpret_cast<const int8_t*>(kc.values)[i];
-    case PLX_I16: return (uint64_t)(long long)reinterpret_cast<const int16_t*>(kc.values)[i];
-    case PLX_I32: return (uint64_t)(long long)reinterpret_cast<const int32_t*>(kc.values)[i];
-    case PLX_U8: return reinterpret_cast<const uint8_t*>(kc.values)[i];
-    case PLX_U16: return reinterpret_cast<const uint16_t*>(kc.values)[i];
-    case PLX_U32: return reinterpret_cast<const uint32_t*>(kc.values)[i];
-    case PLX_F32: { float f = reinterpret_cast<const float*>(kc.values)[i]; double d = (double)f; return (d != d) ? 0x7ff8000000000000ull : (uint64_t)__double_as_longlong(d + 0.0); }
-    case PLX_F64: { double d = reinterpret_cast<const double*>(kc.values)[i]; return (d != d) ? 0x7ff8000000000000ull : (uint64_t)__double_as_longlong(d + 0.0); }
-    case PLX_BOOL: return (reinterpret_cast<const uint64_t*>(kc.values)[i >> 6] >> (i & 63)) & 1;
-    default: return reinterpret_cast<const uint64_t*>(kc.values)[i];
-  }
-}
-__device__ __forceinline__ bool key_valid(const KeyCol& kc, int64_t i) { return !kc.validity || ((kc.validity[i >> 6] >> (i & 63)) & 1); }
 
 struct Table {
   unsigned long long* keys;  // [cap + 1]; slot cap = the key whose bits equal kEmpty
@@ -131,8 +105,10 @@ __global__ __launch_bounds__(kBlock) void join_emit_kernel(KeyCol probe, Table t
   }
 }
 
-static KeyCol key_col(const ColumnPtr& c) { KeyCol kc; kc.values = c->data(); kc.validity = c->valid_words(); kc.dtype = c->dtype; kc.n = c->len; return kc; }
-static int ceil_log2(uint64_t x) { int b = 0; while ((1ull << b) < x) b++; return b; }
+void emit_kept_rows(const uint32_t* counts, const uint64_t* offsets, int64_t n, uint32_t* out_probe) {
+  hipLaunchKernelGGL(join_emit_kept_kernel, dim3(k::grid_for(n, kBlock * 2)), dim3(kBlock), 0, stream(), counts, offsets, n, out_probe);
+  PLX_HIP(hipGetLastError());
+}
 
 void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys) {
   if (dup_build_keys) *dup_build_keys = false;
@@ -177,8 +153,7 @@ void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key
     ColumnPtr kept = mk_idx((int64_t)total);
     if (total) {
       ProfileScope ps("join_emit_kept", (uint64_t)np * 12 + total * 4, (uint64_t)np);
-      hipLaunchKernelGGL(join_emit_kept_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), counts->as<uint32_t>(), offsets->as<uint64_t>(), np, kept->values->as<uint32_t>());
-      PLX_HIP(hipGetLastError());
+      emit_kept_rows(counts->as<uint32_t>(), offsets->as<uint64_t>(), np, kept->values->as<uint32_t>());
     }
     if (desc) *desc = std::string(how == PLX_JOIN_SEMI ? "hash_semi_join" : "hash_anti_join") + "[build=right rows=" + std::to_string(build->len) + " cap=2^" + std::to_string(log2_cap) +
                       ", probe rows=" + std::to_string(np) + ", kept=" + std::to_string(total) + "]";

@@ -779,7 +779,9 @@ class LazyFrame:
 
     def join(self, other: "LazyFrame", on=None, how: str = "inner", left_on=None, right_on=None, suffix: str = "_right", maintain_order: str = "none") -> "LazyFrame":
         """maintain_order (polars JoinArgs.maintain_order): "none" (unspecified row order), "left" (left row order), "left_right" (left, then right row
-        order: a total order), "right", "right_left".  A left join takes none / left / left_right; semi / anti joins return left order whatever is asked."""
+        order: a total order), "right", "right_left".  A left join takes none / left / left_right; semi / anti joins return left order whatever is asked.
+        Multi-column keys (`on=[...]` or `left_on=[...], right_on=[...]`): 2..8 columns of integer, Boolean or float dtype, column j of one dtype on both sides, any
+        value range; a null in any part makes the row's key null (it matches nothing).  `last_plan()` names the route (packed into one Int64, or `wide_hash_join`)."""
         if maintain_order not in P.JOIN_ORDERS:
             raise ValueError(f"maintain_order must be one of {list(P.JOIN_ORDERS)}, got {maintain_order!r}")
         if on is not None:
