@@ -124,7 +124,11 @@ typedef enum plx_agg_op {
   PLX_AGG_FIRST = 6  /* first row of each group (group_by only; used for key columns) */
 } plx_agg_op;
 
-typedef enum plx_join_how { PLX_JOIN_INNER = 0, PLX_JOIN_LEFT = 1, PLX_JOIN_SEMI = 2, PLX_JOIN_ANTI = 3 } plx_join_how;
+/* Null keys match nothing (nulls_equal is not on this path).  PLX_JOIN_FULL: every pair of the inner join, one row per unmatched left row (null right index) and one
+ * row per unmatched right row (null left index); null-key rows of either side count as unmatched.  PLX_JOIN_RIGHT: the left join with the sides exchanged -- every
+ * right row appears, the left index is nullable.  (The reference tree was not at hand when FULL and RIGHT were added: their contract here and at plx_ir.coalesce /
+ * plx_join_order is the maintainers' reading of polars >= 1.0 and is what the tests pin.) */
+typedef enum plx_join_how { PLX_JOIN_INNER = 0, PLX_JOIN_LEFT = 1, PLX_JOIN_SEMI = 2, PLX_JOIN_ANTI = 3, PLX_JOIN_FULL = 4, PLX_JOIN_RIGHT = 5 } plx_join_how;
 
 /* A 64-bit scalar passed by bit pattern; interpreted according to a plx_dtype. */
 typedef union plx_scalar {
@@ -357,7 +361,7 @@ typedef enum plx_ir_kind {
   PLX_IR_SELECT = 2,  /* input, exprs */
   PLX_IR_HSTACK = 3,  /* input, exprs (with_columns) */
   PLX_IR_GROUPBY = 4, /* input, keys, exprs (aggs), maintain_order */
-  PLX_IR_JOIN = 5,    /* input, input_right, keys (left_on), keys_right (right_on), how, suffix, maintain_order (plx_join_order).  Key shapes that are joined:
+  PLX_IR_JOIN = 5,    /* input, input_right, keys (left_on), keys_right (right_on), how, suffix, maintain_order (plx_join_order), coalesce.  Key shapes that are joined:
                        * 1 key column; 2..8 key columns of integer, Boolean or float dtype, where column j has the same dtype on both sides (more than 8:
                        * PLX_ERR_UNSUPPORTED naming the limit).  A null in any key part makes the row's key null: it matches nothing.  Floats compare in the
                        * total order (NaN == NaN, -0 == +0).  The route is visible in the plan description: "packed N key columns into Int64; hash_join[...]"
@@ -375,7 +379,13 @@ typedef enum plx_ir_kind {
  *   RIGHT, RIGHT_LEFT  the mirror image.
  * PLX_JOIN_LEFT: LEFT and LEFT_RIGHT (an unmatched left row is one output row at its left position, right columns null); RIGHT and
  * RIGHT_LEFT return PLX_ERR_UNSUPPORTED with a message that names maintain_order (where the rows without a right index would go is not
- * defined here).  PLX_JOIN_SEMI / PLX_JOIN_ANTI return left order whatever the value.  A value outside 0..4 is PLX_ERR_INVALID; the
+ * defined here).  PLX_JOIN_RIGHT is the mirror image: NONE, RIGHT and RIGHT_LEFT; LEFT and LEFT_RIGHT return PLX_ERR_UNSUPPORTED with a
+ * message that names maintain_order.
+ * PLX_JOIN_FULL takes all five.  A side's "primary" rows are the rows that carry an index of that side.  LEFT / LEFT_RIGHT: the rows with a
+ * left index come first, in the order defined above; the rows without one (unmatched right rows) follow after all of them, in increasing
+ * right row index -- so LEFT_RIGHT and RIGHT_LEFT stay total orders with a unique output.  RIGHT / RIGHT_LEFT: the mirror image.  The "no
+ * row" sentinel can therefore sit on the primary side of a full join's pair list; the pair list still holds fewer than 2^32 - 1 pairs.
+ * PLX_JOIN_SEMI / PLX_JOIN_ANTI return left order whatever the value.  A value outside 0..4 is PLX_ERR_INVALID; the
  * option is never silently ignored.  The join feeding a fused join -> group-by is the one exception: its groups are unordered. */
 typedef enum plx_join_order {
   PLX_JOIN_ORDER_NONE = 0,
@@ -404,6 +414,16 @@ typedef struct plx_ir {
   const uint8_t* sort_nulls_last; /* PLX_IR_SORT: n_keys flags, NULL = nulls first */
   int64_t slice_offset;           /* PLX_IR_SLICE */
   int64_t slice_len;              /* PLX_IR_SLICE: rows kept (clamped to the input; slice_offsets, polars-core/src/utils/mod.rs:340-358) */
+  int32_t coalesce;               /* PLX_IR_JOIN (JoinArgs::coalesce): 0 = the join kind's default (inner, left and right coalesce; full keeps both keys), 1 = coalesce,
+                                   * 2 = keep both key columns; anything else is PLX_ERR_INVALID at plan import; semi / anti ignore it.  A key pair is "plain" when both key
+                                   * expressions are plain columns; only plain pairs coalesce.  Output columns:
+                                   *   inner / left, coalesce   left columns, then right columns without the plain right keys
+                                   *   full, coalesce           the same, each plain left key column holding the left value where the row has a left index, the right key's otherwise
+                                   *   right, coalesce          left columns without the plain left keys, then all right columns
+                                   *   keep both                all left columns, then all right columns (a key is null where its side has no row)
+                                   * A right name that (still) clashes with a left name gets the suffix: a full join on k yields k and k_right.
+                                   * The coalesced key of a FULL join is built for key columns of 1, 2, 4 or 8 bytes per value; a Boolean key column (a bitmap) coalesced
+                                   * on a full join is PLX_ERR_UNSUPPORTED at execution (keep both keys, or cast the key). */
 } plx_ir;
 
 /* plan flags */

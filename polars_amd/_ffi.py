@@ -25,7 +25,8 @@ EQ, NE, LT, LE, GT, GE = range(6)
 ADD, SUB, MUL, TRUE_DIV, FLOOR_DIV, MOD = range(6)
 AND, OR, XOR = range(3)
 AGG_SUM, AGG_MEAN, AGG_MIN, AGG_MAX, AGG_COUNT, AGG_LEN, AGG_FIRST = range(7)
-JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = range(4)
+JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI, JOIN_FULL, JOIN_RIGHT = range(6)
+JOIN_COALESCE_DEFAULT, JOIN_COALESCE, JOIN_KEEP_BOTH = range(3)          # plx_ir.coalesce
 JOIN_ORDER_NONE, JOIN_ORDER_LEFT, JOIN_ORDER_RIGHT, JOIN_ORDER_LEFT_RIGHT, JOIN_ORDER_RIGHT_LEFT = range(5)   # plx_join_order
 AE_COLUMN, AE_LITERAL, AE_BINARY, AE_CAST, AE_AGG, AE_LEN, AE_ALIAS, AE_NOT, AE_IS_NULL, AE_IS_NOT_NULL, AE_FILL_NULL = range(11)
 (OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_PLUS, OP_MINUS, OP_MULTIPLY, OP_TRUE_DIVIDE,
@@ -79,7 +80,7 @@ class IR(C.Structure):
                 ("keys", C.POINTER(C.c_int32)), ("n_keys", C.c_int32), ("keys_right", C.POINTER(C.c_int32)),
                 ("n_keys_right", C.c_int32), ("how", C.c_int32), ("maintain_order", C.c_int32), ("suffix", C.c_char_p),
                 ("sort_descending", C.POINTER(C.c_uint8)), ("sort_nulls_last", C.POINTER(C.c_uint8)), ("slice_offset", C.c_int64),
-                ("slice_len", C.c_int64)]
+                ("slice_len", C.c_int64), ("coalesce", C.c_int32)]
 
 
 class ProfileRecord(C.Structure):

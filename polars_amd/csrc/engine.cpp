@@ -53,6 +53,11 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       PLX_REQUIRE(n.maintain_order >= PLX_JOIN_ORDER_NONE && n.maintain_order <= PLX_JOIN_ORDER_RIGHT_LEFT, PLX_ERR_INVALID, "join: maintain_order outside 0..4 (plx_join_order)");
       PLX_REQUIRE(!(n.how == PLX_JOIN_LEFT && (n.maintain_order == PLX_JOIN_ORDER_RIGHT || n.maintain_order == PLX_JOIN_ORDER_RIGHT_LEFT)), PLX_ERR_UNSUPPORTED,
                   std::string("left join with maintain_order=") + join::join_order_name(n.maintain_order) + ": only maintain_order none / left / left_right are on this path for a left join");
+      PLX_REQUIRE(!(n.how == PLX_JOIN_RIGHT && (n.maintain_order == PLX_JOIN_ORDER_LEFT || n.maintain_order == PLX_JOIN_ORDER_LEFT_RIGHT)), PLX_ERR_UNSUPPORTED,
+                  std::string("right join with maintain_order=") + join::join_order_name(n.maintain_order) + ": only maintain_order none / right / right_left are on this path for a right join");
+      PLX_REQUIRE(n.how >= PLX_JOIN_INNER && n.how <= PLX_JOIN_RIGHT, PLX_ERR_INVALID, "join: how outside 0..5 (plx_join_how)");
+      n.coalesce = ir[i].coalesce;
+      PLX_REQUIRE(n.coalesce >= 0 && n.coalesce <= 2, PLX_ERR_INVALID, "join: coalesce outside 0..2 (0 = the join kind's default, 1 = coalesce, 2 = keep both key columns)");
     }
     if (ir[i].suffix) n.suffix = ir[i].suffix;
     if (n.kind == PLX_IR_SORT) {
@@ -1481,6 +1486,12 @@ static void collect_columns(const Plan& plan, int e, std::set<std::string>& out)
 // Resolves one input of the outer join to a scan node: [Filter]* Scan, or [Filter]* Join(inner; A, B) with A, B = [Filter]* Scan
 // where one of A / B is a pure filter with respect to `used` (the column names referenced above).  Appends the payload side's
 // predicates to `preds` and the filter to `semis`; returns the payload scan node or -1 (why set).
+// Full and right joins, and joins that keep both key columns (coalesce = 2), are served by the per-node route at every size: the reason the fused pipelines give (null: none).
+static const char* join_takes_per_node_route(const IRN& jn) {
+  if (jn.how == PLX_JOIN_FULL || jn.how == PLX_JOIN_RIGHT) return "full and right joins take the per-node route";
+  if (jn.coalesce == 2) return "coalesce=false (both key columns kept) takes the per-node route";
+  return nullptr;
+}
 static int resolve_join_side(const Plan& plan, int node, std::set<std::string> used, std::vector<int>& preds, std::vector<SemiFilter>& semis, std::string* why) {
   auto no = [&](const char* m) { if (why) *why = m; return -1; };
   const int n = peel_filters(plan, node, preds);
@@ -1488,6 +1499,7 @@ static int resolve_join_side(const Plan& plan, int node, std::set<std::string> u
   if (plan.ir[n].kind != PLX_IR_JOIN) return no("join inputs are not filtered scans");
   const IRN& j = plan.ir[n];
   if (j.how != PLX_JOIN_INNER || j.keys.size() != 1 || j.keys_right.size() != 1) return no("nested join is not a single-key inner join");
+  if (j.coalesce == 2) return no("nested join keeps both key columns (coalesce=false)");
   const AE* ka = plain_column(plan, j.keys[0]);
   const AE* kb = plain_column(plan, j.keys_right[0]);
   if (!ka || !kb) return no("nested join keys are expressions");
@@ -1757,6 +1769,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   auto no = [&](const char* m) { if (why) *why = m; return false; };
   if (gb.input < 0 || plan.ir[gb.input].kind != PLX_IR_JOIN) return no("input is not a join");
   const IRN& jn = plan.ir[gb.input];
+  if (const char* per_node = join_takes_per_node_route(jn)) return no(per_node);
   if ((jn.how != PLX_JOIN_INNER && jn.how != PLX_JOIN_LEFT) || jn.keys.size() != 1 || jn.keys_right.size() != 1) return no("not a single-key inner or left join");
   // LEFT join (single_keys_left.rs:106-195: every left row survives; rows without a match carry nulls in the right table's columns): the matched rows are the inner join's
   // -- the same pipeline with the RIGHT table as the build side -- and the unmatched ones are a group-by of their own over the left table, keyed by the join key, behind
@@ -2373,6 +2386,7 @@ static int join_materialise_mode() { const char* e = getenv("PLX_JOIN_MATERIALIS
 static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::string>* want, FramePtr& out, std::string* why, uint64_t* build_rows_out = nullptr, int* build_side_out = nullptr) {
   auto no = [&](const char* m) { if (why) *why = m; return false; };
   const int mode = join_materialise_mode();
+  if (const char* per_node = join_takes_per_node_route(jn)) return no(per_node);
   if (mode == 0) return no("disabled (PLX_JOIN_MATERIALISE=0)");
   if ((jn.how != PLX_JOIN_INNER && jn.how != PLX_JOIN_LEFT) || jn.keys.size() != 1 || jn.keys_right.size() != 1) return no("not a single-key inner or left join");
   const bool left_join = jn.how == PLX_JOIN_LEFT;
@@ -2548,6 +2562,7 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
 // No pairs, no gathers.  Needs a right key range a bitmap can cover (<= 2^34 keys and <= 256 x the right rows); otherwise the per-node join runs.
 static bool fused_semi_anti_frame(Plan& plan, const IRN& jn, FramePtr& out, std::string* why) {
   auto no = [&](const char* m) { if (why) *why = m; return false; };
+  if (const char* per_node = join_takes_per_node_route(jn)) return no(per_node);
   if (join_materialise_mode() == 0) return no("disabled (PLX_JOIN_MATERIALISE=0)");
   if ((jn.how != PLX_JOIN_SEMI && jn.how != PLX_JOIN_ANTI) || jn.keys.size() != 1 || jn.keys_right.size() != 1) return no("not a single-key semi or anti join");
   const AE* lkx = plain_column(plan, jn.keys[0]);
@@ -2663,16 +2678,21 @@ static FramePtr exec_join(Plan& plan, const IRN& n) {
   ColumnPtr li, ri;
   std::string d;
   bool dup_build_keys = false;
+  int64_t unmatched_build = 0;         // full join: the pairs (no probe row, build row) at the end of the pair list
+  const bool full = n.how == PLX_JOIN_FULL, right_join = n.how == PLX_JOIN_RIGHT;
+  const bool coalesce = n.coalesce == 1 || (n.coalesce == 0 && !full);      // plx_ir.coalesce: 0 = the kind's default (full joins keep both keys)
   if (!wide_why.empty()) {
-    join::join_indices_wide(n.how, lraw, rraw, li, ri, &d, &dup_build_keys);
+    join::join_indices_wide(n.how, lraw, rraw, li, ri, &d, &dup_build_keys, &unmatched_build);
     const size_t at = d.find(", build=");     // "wide_hash_join[words=N, build=...": the reason goes behind the word count
     if (at != std::string::npos) d.insert(at, " (" + wide_why + ")");
-  } else join::join_indices(n.how, lk, rk, li, ri, &d, &dup_build_keys);
+  } else join::join_indices(n.how, lk, rk, li, ri, &d, &dup_build_keys, &unmatched_build);
   d = packed_desc + d;
   if (n.maintain_order != PLX_JOIN_ORDER_NONE && n.how != PLX_JOIN_SEMI && n.how != PLX_JOIN_ANTI) {
-    // join_indices emits at scanned offsets: probe order; its chains (duplicate build keys) are newest first.  It builds on the right unless the left side is not the larger one of an inner join.
-    const bool probe_is_left = n.how == PLX_JOIN_LEFT || left->height > right->height;
+    // join_indices emits at scanned offsets: probe order; its chains (duplicate build keys) are newest first.  It builds on the right unless the left side is not the larger one of an
+    // inner / full join, or the join is a right join (always built on the left).  A full join's unmatched build rows follow the probe-ordered pairs.
+    const bool probe_is_left = n.how == PLX_JOIN_LEFT || (!right_join && left->height > right->height);
     join::PairProps props; props.probe_ordered = true; props.runs_ordered = !dup_build_keys;
+    if (full) props.build_tail = unmatched_build;
     std::string od;
     join::order_pairs(n.maintain_order, probe_is_left, props, probe_is_left ? li : ri, probe_is_left ? ri : li, &od);
     d += ", " + od;
@@ -2685,19 +2705,32 @@ static FramePtr exec_join(Plan& plan, const IRN& n) {
     for (auto& c : left->cols) out->cols.push_back(ops::gather(c, li));
     return out;
   }
-  plan.desc += "Join{" + d + ", gather x" + std::to_string(left->cols.size() + right->cols.size()) + "}; ";
-  // _finish_join (polars-ops/src/frame/join/general.rs:17-49): left columns, then right columns
-  // except the right key when it is a plain column coalesced into the left key; name clashes get the suffix.
+  static const char* const how_names[] = {"inner", "left", "semi", "anti", "full", "right"};
+  plan.desc += "Join{" + d + ", how=" + how_names[n.how] + (n.coalesce == 0 ? "" : coalesce ? ", coalesce=true" : ", coalesce=false") + ", gather x" + std::to_string(left->cols.size() + right->cols.size()) + "}; ";
+  // _finish_join (polars-ops/src/frame/join/general.rs:17-49): left columns, then right columns; name clashes on the right get the suffix.  A key pair of two plain columns
+  // coalesces (plx_ir.coalesce; include/polars_amd.h): inner / left joins drop the right key, a right join drops the left key, a full join keeps the left key column filled
+  // from whichever side has the row and drops the right key.  Without coalescing every column of both sides stays.
+  std::vector<std::pair<std::string, std::string>> plain_keys;   // (left name, right name) of the key pairs made of two plain columns
+  for (size_t j = 0; j < n.keys.size(); j++) {
+    const AE* lkx = plain_column(plan, n.keys[j]);
+    const AE* rkx = plain_column(plan, n.keys_right[j]);
+    if (lkx && rkx) plain_keys.push_back({lkx->name, rkx->name});
+  }
   auto out = std::make_shared<Frame>();
   out->height = li->len;
-  for (size_t i = 0; i < left->cols.size(); i++) { out->names.push_back(left->names[i]); out->cols.push_back(ops::gather(left->cols[i], li)); }
-  std::vector<std::string> coalesced;   // right key columns merged into the left key (both sides plain columns)
-  for (size_t j = 0; j < n.keys.size(); j++) {
-    const AE* rkx = plain_column(plan, n.keys_right[j]);
-    if (rkx && plain_column(plan, n.keys[j])) coalesced.push_back(rkx->name);
+  for (size_t i = 0; i < left->cols.size(); i++) {
+    const auto key = std::find_if(plain_keys.begin(), plain_keys.end(), [&](const std::pair<std::string, std::string>& k) { return k.first == left->names[i]; });
+    if (coalesce && right_join && key != plain_keys.end()) continue;                     // the right key column carries the key
+    out->names.push_back(left->names[i]);
+    if (coalesce && full && key != plain_keys.end()) {
+      const int rki = right->find(key->second);
+      PLX_REQUIRE(rki >= 0, PLX_ERR_NOT_FOUND, "column not found: " + key->second);
+      out->cols.push_back(join::coalesce_keys(left->cols[i], right->cols[rki], li, ri));
+    } else out->cols.push_back(ops::gather(left->cols[i], li));
   }
   for (size_t i = 0; i < right->cols.size(); i++) {
-    if (std::find(coalesced.begin(), coalesced.end(), right->names[i]) != coalesced.end()) continue;  // coalesced key
+    if (coalesce && !right_join && std::find_if(plain_keys.begin(), plain_keys.end(), [&](const std::pair<std::string, std::string>& k) { return k.second == right->names[i]; }) != plain_keys.end())
+      continue;                                                                          // coalesced into the left key column
     std::string name = right->names[i];
     if (out->find(name) >= 0) name += n.suffix;
     out->names.push_back(name);
@@ -2765,8 +2798,11 @@ static FramePtr exec_node(Plan& plan, int node_id) {
         std::set<std::string> want;
         for (int e : n.exprs) collect_columns(plan, e, want);
         FramePtr j; std::string why;
-        if (fused_join_frame(plan, plan.ir[n.input], &want, j, &why)) return exec_select(plan, n, false, j);
-        if (why != "small inputs") plan.desc += "(join not fused: " + why + ") ";
+        // (a join the fused pipelines never take is left to exec_join, which names the reason once)
+        if (!join_takes_per_node_route(plan.ir[n.input])) {
+          if (fused_join_frame(plan, plan.ir[n.input], &want, j, &why)) return exec_select(plan, n, false, j);
+          if (why != "small inputs") plan.desc += "(join not fused: " + why + ") ";
+        }
       }
       if (fuse) {
         std::vector<int> preds;

@@ -31,6 +31,7 @@ struct IRN {
   plx_frame frame = 0;
   std::vector<int> exprs, keys, keys_right;
   int how = 0, maintain_order = 0;
+  int coalesce = 0;   // PLX_IR_JOIN: plx_ir.coalesce (0 = the join kind's default, 1 = coalesce, 2 = keep both key columns)
   std::string suffix = "_right";
   std::vector<uint8_t> sort_descending, sort_nulls_last;
   int64_t slice_offset = 0, slice_len = 0;

@@ -40,6 +40,12 @@ inline int ceil_log2(uint64_t x) { int b = 0; while ((1ull << b) < x) b++; retur
 
 // semi / anti: out_probe[offsets[i]] = i for every probe row with counts[i] != 0 (join_emit_kept_kernel, kernels_join.hip), on the current stream
 void emit_kept_rows(const uint32_t* counts, const uint64_t* offsets, int64_t n, uint32_t* out_probe);
+// full join (kernels_join.hip; both key routes): the build rows whose byte in matched[nb] the count pass left 0, ascending (ballots -> selection words -> the row-id
+// compaction of kernels_filter.hip; *n_out of them; synchronises), and (kNoRow, row) for them written behind the first `at` pairs of the two index columns
+Buf unmatched_build_rows(const uint8_t* matched, int64_t nb, int64_t* n_out);
+void append_unmatched(const Buf& rows, int64_t n, int64_t at, const ColumnPtr& probe_idx, const ColumnPtr& build_idx);
+// the kNoRow entries of an index column become nulls (validity bitmap; none when no entry is kNoRow)
+void null_out_no_row(ColumnPtr& idx);
 
 }  // namespace join
 }  // namespace plx

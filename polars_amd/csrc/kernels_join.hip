@@ -13,6 +13,11 @@
 // Keys are read in their physical dtype and widened in registers (no materialised
 // 64-bit key copy); floats are canonicalised (-0 -> +0, one NaN: total_ord.rs:40-48).
 // Null keys never match (nulls_equal = false).
+// Right join: the left join with the sides exchanged (the left input is the build side, left_idx the nullable index).  Full join: the probe side is joined as a
+// left join; the count pass also flags every build row it walks over (one byte per row, plain stores of the constant 1), the unflagged rows -- null keys were
+// never inserted, so they stay unflagged -- are ballotted into selection words and compacted in row order (kernels_filter.hip), and (kNoRow, row) is appended for
+// them behind the left-join pairs.  The reference tree is not at hand for these two kinds: their contract (include/polars_amd.h) is the maintainers' reading of
+// polars >= 1.0 and is what the tests pin.
 #include "dev.hpp"
 #include "fused.hpp"
 #include "join.hpp"
@@ -71,17 +76,39 @@ __global__ __launch_bounds__(kBlock) void join_build_kernel(KeyCol build, Table 
   }
 }
 
-// counts[i] = number of build matches of probe row i (left join: at least 1)
-__global__ __launch_bounds__(kBlock) void join_count_kernel(KeyCol probe, Table t, int how, uint32_t* __restrict__ counts) {
+// counts[i] = number of build matches of probe row i (left join: at least 1).  kFlag (full join): matched[r] = 1 for every build row r on the chain -- several probe
+// rows that hit one build row store the same byte, so no atomic is needed; the other join kinds run the instantiation without the store.
+template <bool kFlag>
+__device__ __forceinline__ void join_count_rows(const KeyCol& probe, const Table& t, int how, uint32_t* __restrict__ counts, uint8_t* __restrict__ matched) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < probe.n; i += (int64_t)gridDim.x * blockDim.x) {
     uint32_t c = 0;
     if (key_valid(probe, i)) {
       const int64_t slot = find_slot(t, load_key(probe, i));
-      if (slot >= 0) { for (unsigned int r = t.head[slot]; r != kNoRow; r = t.next[r]) c++; }
+      if (slot >= 0) { for (unsigned int r = t.head[slot]; r != kNoRow; r = t.next[r]) { c++; if constexpr (kFlag) matched[r] = 1; } }
     }
     // how: 0 inner, 1 left (unmatched rows emit one pair), 2 semi (row kept once if matched), 3 anti (kept if unmatched; null keys never match)
     counts[i] = how == 2 ? (c ? 1u : 0u) : how == 3 ? (c ? 0u : 1u) : (how == 1 && c == 0) ? 1u : c;
   }
+}
+__global__ __launch_bounds__(kBlock) void join_count_kernel(KeyCol probe, Table t, int how, uint32_t* __restrict__ counts) { join_count_rows<false>(probe, t, how, counts, nullptr); }
+__global__ __launch_bounds__(kBlock) void join_full_count_kernel(KeyCol probe, Table t, uint32_t* __restrict__ counts, uint8_t* __restrict__ matched) {
+  join_count_rows<true>(probe, t, 1, counts, matched);
+}
+
+// full join, after the count pass: bit i of mask = build row i was flagged by no probe row (one ballot per 64 rows; the pad bits of the last word are cleared)
+__global__ __launch_bounds__(kBlock) void join_unmatched_mask_kernel(const uint8_t* __restrict__ matched, int64_t n, unsigned long long* __restrict__ mask) {
+  const int lane = lane_id();
+  const int64_t nwords = (n + 63) >> 6;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t w = wave; w < nwords; w += nwaves) {
+    const int64_t i = w * 64 + lane;
+    const uint64_t m = ballot(i < n && matched[i] == 0);
+    if (lane == 0) mask[w] = m;
+  }
+}
+// ... and behind the left-join pairs: (kNoRow, unmatched build row), in build row order
+__global__ __launch_bounds__(kBlock) void join_append_unmatched_kernel(const uint32_t* __restrict__ rows, int64_t n, uint32_t* __restrict__ out_probe, uint32_t* __restrict__ out_build) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) { out_probe[i] = kNoRow; out_build[i] = rows[i]; }
 }
 
 // semi / anti: the kept probe rows, in probe order (single_keys_semi_anti.rs keeps left order the same way)
@@ -110,15 +137,111 @@ void emit_kept_rows(const uint32_t* counts, const uint64_t* offsets, int64_t n, 
   PLX_HIP(hipGetLastError());
 }
 
-void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys) {
+void null_out_no_row(ColumnPtr& idx) {
+  if (!idx->len) return;
+  plx_scalar s; s.u = kNoRow;
+  ColumnPtr ok = ops::cmp_scalar(PLX_NE, idx, s);
+  idx->validity = ok->values; idx->null_count = -1;
+  if (column_null_count(idx) == 0) { idx->validity = nullptr; idx->null_count = 0; }
+}
+
+Buf unmatched_build_rows(const uint8_t* matched, int64_t nb, int64_t* n_out) {
+  *n_out = 0;
+  if (nb == 0) return nullptr;
+  const int64_t nwords = (nb + 63) >> 6;
+  Buf mask = dev_alloc(sizeof(uint64_t) * (size_t)nwords);
+  {
+    ProfileScope ps("join_unmatched_mask", (uint64_t)nb + (uint64_t)nwords * 8, (uint64_t)nb);
+    hipLaunchKernelGGL(join_unmatched_mask_kernel, dim3(k::grid_for(nb, kBlock * 4)), dim3(kBlock), 0, stream(), matched, nb, mask->as<unsigned long long>());
+    PLX_HIP(hipGetLastError());
+  }
+  const k::FilterPlan fp = k::filter_prepare(mask->as<uint64_t>(), nb);
+  *n_out = fp.n_out;
+  Buf rows = dev_alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(fp.n_out, 1));
+  k::filter_rowids(fp, rows->as<uint32_t>());
+  PLX_HIP(hipStreamSynchronize(stream()));               // `mask` / the plan's offsets are read by the compaction
+  return rows;
+}
+void append_unmatched(const Buf& rows, int64_t n, int64_t at, const ColumnPtr& probe_idx, const ColumnPtr& build_idx) {
+  if (n == 0) return;
+  PLX_REQUIRE(at >= 0 && at + n <= probe_idx->len && probe_idx->len == build_idx->len, PLX_ERR_SHAPE, "full join: the unmatched build rows do not fit the pair list");
+  ProfileScope ps("join_append_unmatched", (uint64_t)n * 12, (uint64_t)n);
+  hipLaunchKernelGGL(join_append_unmatched_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), rows->as<uint32_t>(), n, probe_idx->values->as<uint32_t>() + at,
+                     build_idx->values->as<uint32_t>() + at);
+  PLX_HIP(hipGetLastError());
+  PLX_HIP(hipStreamSynchronize(stream()));               // `rows` is released by the caller
+}
+
+// out[i] = li[i] != kNoRow ? lkey[li[i]] : rkey[ri[i]], validity from the side that was read (the coalesced key column of a full join); one wave per 64 rows
+template <class W>
+__global__ __launch_bounds__(kBlock) void coalesce_key_kernel(const W* __restrict__ lkey, const uint64_t* __restrict__ lvalid, const W* __restrict__ rkey, const uint64_t* __restrict__ rvalid,
+                                                              const uint32_t* __restrict__ li, const uint32_t* __restrict__ ri, int64_t n, W* __restrict__ out,
+                                                              unsigned long long* __restrict__ out_validity) {
+  const int lane = lane_id();
+  const int64_t nwords = (n + 63) >> 6;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t w = wave; w < nwords; w += nwaves) {
+    const int64_t i = w * 64 + lane;
+    bool ok = false;
+    if (i < n) {
+      const uint32_t l = li[i];
+      const bool from_left = l != kNoRow;
+      const uint32_t j = from_left ? l : ri[i];
+      ok = j != kNoRow;                                  // (a pair has at least one side)
+      const W* src = from_left ? lkey : rkey;
+      const uint64_t* val = from_left ? lvalid : rvalid;
+      out[i] = ok ? src[j] : (W)0;
+      if (ok && val) ok = (val[j >> 6] >> (j & 63)) & 1;
+    }
+    if (out_validity) { const uint64_t m = ballot(ok); if (lane == 0) out_validity[w] = m; }
+  }
+}
+ColumnPtr coalesce_keys(const ColumnPtr& lkey, const ColumnPtr& rkey, const ColumnPtr& left_idx, const ColumnPtr& right_idx) {
+  PLX_REQUIRE(lkey->dtype == rkey->dtype, PLX_ERR_INVALID, std::string("coalesced join key: the key columns have different dtypes (") + dtype_name(lkey->dtype) + ", " + dtype_name(rkey->dtype) + ")");
+  const int w = lkey->dtype == PLX_BOOL ? 0 : dtype_width(lkey->dtype);
+  PLX_REQUIRE(w == 1 || w == 2 || w == 4 || w == 8, PLX_ERR_UNSUPPORTED, std::string("full join with coalesce on a ") + dtype_name(lkey->dtype) + " key: keys of 1, 2, 4 or 8 bytes coalesce");
+  PLX_REQUIRE(left_idx->dtype == PLX_U32 && right_idx->dtype == PLX_U32 && left_idx->len == right_idx->len, PLX_ERR_INVALID, "coalesced join key: two u32 index columns of one length");
+  const int64_t n = left_idx->len;
+  const bool need_valid = lkey->validity || rkey->validity;
+  ColumnPtr out = make_column(lkey->dtype, n, need_valid);
+  if (n == 0) return out;
+  if (need_valid) out->null_count = -1;
+  ProfileScope ps("join_coalesce_key", (uint64_t)n * (8 + 2 * (uint64_t)w), (uint64_t)n);
+  const int grid = k::grid_for(n, kBlock * 2);
+  unsigned long long* ov = need_valid ? out->validity->as<unsigned long long>() : nullptr;
+#define C(W) hipLaunchKernelGGL((coalesce_key_kernel<W>), dim3(grid), dim3(kBlock), 0, stream(), (const W*)lkey->data(), lkey->valid_words(), (const W*)rkey->data(), rkey->valid_words(), \
+                                left_idx->values->as<uint32_t>(), right_idx->values->as<uint32_t>(), n, (W*)out->values->ptr, ov)
+  switch (w) {
+    case 1: C(uint8_t); break;
+    case 2: C(uint16_t); break;
+    case 4: C(uint32_t); break;
+    default: C(uint64_t); break;
+  }
+#undef C
+  PLX_HIP(hipGetLastError());
+  return out;
+}
+
+static void join_indices_sides(int how, bool exchanged, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys,
+                               int64_t* unmatched_build);
+void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys, int64_t* unmatched_build) {
+  // a right join is the left join with the sides exchanged: the left input is the build side, left_idx the nullable index
+  if (how == PLX_JOIN_RIGHT) join_indices_sides(PLX_JOIN_LEFT, true, right_key, left_key, right_idx, left_idx, desc, dup_build_keys, unmatched_build);
+  else join_indices_sides(how, false, left_key, right_key, left_idx, right_idx, desc, dup_build_keys, unmatched_build);
+}
+// `exchanged`: the caller swapped the inputs (right join), so the side names in *desc are swapped back
+static void join_indices_sides(int how, bool exchanged, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys,
+                               int64_t* unmatched_build) {
   if (dup_build_keys) *dup_build_keys = false;
+  if (unmatched_build) *unmatched_build = 0;
   PLX_REQUIRE(left_key->dtype == right_key->dtype, PLX_ERR_INVALID,
               std::string("join keys have different dtypes (") + dtype_name(left_key->dtype) + ", " + dtype_name(right_key->dtype) + ")");
-  PLX_REQUIRE(how == PLX_JOIN_INNER || how == PLX_JOIN_LEFT || how == PLX_JOIN_SEMI || how == PLX_JOIN_ANTI, PLX_ERR_UNSUPPORTED, "join type outside the hot path");
+  PLX_REQUIRE(how == PLX_JOIN_INNER || how == PLX_JOIN_LEFT || how == PLX_JOIN_SEMI || how == PLX_JOIN_ANTI || how == PLX_JOIN_FULL, PLX_ERR_UNSUPPORTED, "join type outside the hot path");
   PLX_REQUIRE(left_key->len < 0xffffffffll && right_key->len < 0xffffffffll, PLX_ERR_UNSUPPORTED, "join side exceeds u32 IdxSize");
   const bool left_join = how == PLX_JOIN_LEFT;
+  const bool full = how == PLX_JOIN_FULL;
   const bool semi_anti = how == PLX_JOIN_SEMI || how == PLX_JOIN_ANTI;
-  // det_hash_prone_order (hash_join/mod.rs:41-50): build on the shorter relation; left / semi / anti joins build on the right
+  // det_hash_prone_order (hash_join/mod.rs:41-50): build on the shorter relation (inner and full joins); left / semi / anti joins build on the right
   const bool swapped = !left_join && !semi_anti && !(left_key->len > right_key->len);
   const ColumnPtr& probe = (left_join || semi_anti) ? left_key : (swapped ? right_key : left_key);
   const ColumnPtr& build = (left_join || semi_anti) ? right_key : (swapped ? left_key : right_key);
@@ -140,14 +263,21 @@ void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key
   const int64_t np = probe->len;
   Buf counts = dev_alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(np, 1));
   Buf offsets = dev_alloc(sizeof(uint64_t) * (size_t)(np + 1));
+  Buf matched = full ? dev_alloc_zero((size_t)std::max<int64_t>(build->len, 1)) : nullptr;     // full join: one byte per build row, set by the count pass
   if (np) {
     ProfileScope ps("join_probe_count", (uint64_t)np * (kw + 4), (uint64_t)np);
-    hipLaunchKernelGGL(join_count_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), key_col(probe), t, how, counts->as<uint32_t>());
+    if (full) hipLaunchKernelGGL(join_full_count_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), key_col(probe), t, counts->as<uint32_t>(), matched->as<uint8_t>());
+    else hipLaunchKernelGGL(join_count_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), key_col(probe), t, how, counts->as<uint32_t>());
     PLX_HIP(hipGetLastError());
   }
   k::exclusive_scan_u32(counts->as<uint32_t>(), offsets->as<uint64_t>(), np);
   uint64_t total = 0;
   d2h_sync(&total, offsets->as<uint64_t>() + np, 8);
+  // full join: the unflagged build rows, known before the pair list is allocated
+  int64_t tail = 0;
+  Buf tail_rows = full ? unmatched_build_rows(matched->as<uint8_t>(), build->len, &tail) : nullptr;
+  PLX_REQUIRE(!full || total + (uint64_t)tail < 0xffffffffull, PLX_ERR_UNSUPPORTED, "join output exceeds u32 IdxSize");
+  if (unmatched_build) *unmatched_build = tail;
   auto mk_idx = [&](int64_t n) { auto c = std::make_shared<Column>(); c->dtype = PLX_U32; c->len = n; c->values = dev_alloc(values_bytes(PLX_U32, n)); c->null_count = 0; return c; };
   if (semi_anti) {
     ColumnPtr kept = mk_idx((int64_t)total);
@@ -160,25 +290,23 @@ void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key
     left_idx = kept; right_idx = nullptr;
     return;
   }
-  ColumnPtr pidx = mk_idx((int64_t)total), bidx = mk_idx((int64_t)total);
+  ColumnPtr pidx = mk_idx((int64_t)total + tail), bidx = mk_idx((int64_t)total + tail);
   if (total) {
     ProfileScope ps("join_probe_emit", (uint64_t)np * (kw + 8) + total * 8, (uint64_t)np);
-    hipLaunchKernelGGL(join_emit_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), key_col(probe), t, left_join ? 1 : 0, offsets->as<uint64_t>(),
+    hipLaunchKernelGGL(join_emit_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), key_col(probe), t, (left_join || full) ? 1 : 0, offsets->as<uint64_t>(),
                        pidx->values->as<uint32_t>(), bidx->values->as<uint32_t>());
     PLX_HIP(hipGetLastError());
   }
-  if (left_join && total) {
-    // unmatched rows carry the kNoRow sentinel -> validity bitmap
-    plx_scalar s; s.u = kNoRow;
-    ColumnPtr ok = ops::cmp_scalar(PLX_NE, bidx, s);
-    bidx->validity = ok->values; bidx->null_count = -1;
-    if (column_null_count(bidx) == 0) { bidx->validity = nullptr; bidx->null_count = 0; }
-  }
+  if (full) append_unmatched(tail_rows, tail, (int64_t)total, pidx, bidx);
+  // unmatched rows carry the kNoRow sentinel -> validity bitmap
+  if (left_join || full) null_out_no_row(bidx);
+  if (full) null_out_no_row(pidx);
   if (desc || dup_build_keys) {
     uint32_t f = 0; d2h_sync(&f, flags->ptr, 4);
     if (dup_build_keys) *dup_build_keys = f != 0;
-    if (desc) *desc = std::string("hash_join[build=") + (left_join ? "right" : (swapped ? "left" : "right")) + " rows=" + std::to_string(build->len) + " cap=2^" + std::to_string(log2_cap) +
-            (f ? " dup-keys" : " unique-keys") + ", probe rows=" + std::to_string(np) + ", pairs=" + std::to_string(total) + "]";
+    const bool build_is_left = (left_join ? false : swapped) != exchanged;
+    if (desc) *desc = std::string(full ? "hash_full_join[build=" : "hash_join[build=") + (build_is_left ? "left" : "right") + " rows=" + std::to_string(build->len) + " cap=2^" + std::to_string(log2_cap) +
+            (f ? " dup-keys" : " unique-keys") + ", probe rows=" + std::to_string(np) + ", pairs=" + std::to_string(total) + (full ? ", unmatched build rows=" + std::to_string(tail) : std::string()) + "]";
   }
   if (left_join || !swapped) { left_idx = pidx; right_idx = bidx; }
   else { left_idx = bidx; right_idx = pidx; }
@@ -269,13 +397,6 @@ static void join_pairs_impl(int how, const ColumnPtr& probe_key, const ColumnPtr
   const bool left = how == PLX_JOIN_LEFT, multi = t.links != nullptr;
   const int64_t n = cand ? cand->len : probe_key->len;
   auto mk_idx = [&](int64_t m) { auto c = std::make_shared<Column>(); c->dtype = PLX_U32; c->len = m; c->values = dev_alloc(values_bytes(PLX_U32, std::max<int64_t>(m, 1))); c->null_count = 0; return c; };
-  auto null_out_no_row = [&](ColumnPtr& bidx) {          // unmatched rows of a left join carry the kNoRow sentinel -> validity bitmap
-    if (!bidx->len) return;
-    plx_scalar s; s.u = kNoRow;
-    ColumnPtr ok = ops::cmp_scalar(PLX_NE, bidx, s);
-    bidx->validity = ok->values; bidx->null_count = -1;
-    if (column_null_count(bidx) == 0) { bidx->validity = nullptr; bidx->null_count = 0; }
-  };
   if (n == 0) { probe_idx = mk_idx(0); build_idx = mk_idx(0); if (desc) *desc = "join_pairs[no candidates]"; return; }
   const uint32_t* cp = cand ? cand->values->as<uint32_t>() : nullptr;
   const int kw = dtype_width(probe_key->dtype) ? dtype_width(probe_key->dtype) : 1;

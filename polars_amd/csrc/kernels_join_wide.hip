@@ -13,6 +13,8 @@
 // order: newest build row first).  A null in any key part makes the row's key null: it matches nothing (nulls_equal = false).
 // No per-lane array of key words exists: the hash is one pass over the columns, the compare a second pass that reloads the row's own words (cache hits); the
 // column descriptors are read with wave-uniform loads from a small device array (dev::uniform_ld), so nothing is indexed at run time in registers.
+// Right and full joins as in kernels_join.hip: a right join is the left join with the sides exchanged; a full join's count pass (its own kernel, so that the other
+// kinds do not pay for the store) flags the build rows it walks over, the unflagged ones are compacted in row order and appended as (kNoRow, row).
 #include "dev.hpp"
 #include "fused_sinks.hpp"
 #include "join.hpp"
@@ -113,17 +115,24 @@ __global__ __launch_bounds__(kBlock) void join_wide_build_kernel(WideKeys build,
   }
 }
 
-// counts[i] = pairs of probe row i; the `how` rules of join_count_kernel (kernels_join.hip)
-__global__ __launch_bounds__(kBlock) void join_wide_count_kernel(WideKeys probe, WideKeys build, WideTable t, int how, uint32_t* __restrict__ counts) {
+// counts[i] = pairs of probe row i; the `how` rules of join_count_kernel (kernels_join.hip).  kFlag (full join): matched[r] = 1 for every build row on the chain.
+template <bool kFlag>
+__device__ __forceinline__ void join_wide_count_rows(const WideKeys& probe, const WideKeys& build, const WideTable& t, int how, uint32_t* __restrict__ counts, uint8_t* __restrict__ matched) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < probe.n; i += (int64_t)gridDim.x * blockDim.x) {
     uint32_t c = 0;
     uint64_t h;
     if (wide_hash(probe, i, &h)) {
       const int64_t slot = wide_find(t, probe, i, build, h);
-      if (slot >= 0) { for (unsigned int r = t.head[slot]; r != kNoRow; r = t.next[r]) c++; }
+      if (slot >= 0) { for (unsigned int r = t.head[slot]; r != kNoRow; r = t.next[r]) { c++; if constexpr (kFlag) matched[r] = 1; } }
     }
     counts[i] = how == 2 ? (c ? 1u : 0u) : how == 3 ? (c ? 0u : 1u) : (how == 1 && c == 0) ? 1u : c;
   }
+}
+__global__ __launch_bounds__(kBlock) void join_wide_count_kernel(WideKeys probe, WideKeys build, WideTable t, int how, uint32_t* __restrict__ counts) {
+  join_wide_count_rows<false>(probe, build, t, how, counts, nullptr);
+}
+__global__ __launch_bounds__(kBlock) void join_wide_full_count_kernel(WideKeys probe, WideKeys build, WideTable t, uint32_t* __restrict__ counts, uint8_t* __restrict__ matched) {
+  join_wide_count_rows<true>(probe, build, t, 1, counts, matched);
 }
 
 __global__ __launch_bounds__(kBlock) void join_wide_emit_kernel(WideKeys probe, WideKeys build, WideTable t, int left_join, const uint64_t* __restrict__ offsets,
@@ -145,9 +154,19 @@ __global__ __launch_bounds__(kBlock) void join_wide_emit_kernel(WideKeys probe, 
 
 static int wide_tag_bits() { const char* e = getenv("PLX_JOIN_WIDE_TAG_BITS"); const int v = e && e[0] ? atoi(e) : 32; return v >= 0 && v <= 32 ? v : 32; }   // (read at every call: the tests switch it)
 
+static void join_indices_wide_sides(int how, bool exchanged, const std::vector<ColumnPtr>& left_keys, const std::vector<ColumnPtr>& right_keys, ColumnPtr& left_idx, ColumnPtr& right_idx,
+                                    std::string* desc, bool* dup_build_keys, int64_t* unmatched_build);
 void join_indices_wide(int how, const std::vector<ColumnPtr>& left_keys, const std::vector<ColumnPtr>& right_keys, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc,
-                       bool* dup_build_keys) {
+                       bool* dup_build_keys, int64_t* unmatched_build) {
+  // a right join is the left join with the sides exchanged: the left input is the build side, left_idx the nullable index
+  if (how == PLX_JOIN_RIGHT) join_indices_wide_sides(PLX_JOIN_LEFT, true, right_keys, left_keys, right_idx, left_idx, desc, dup_build_keys, unmatched_build);
+  else join_indices_wide_sides(how, false, left_keys, right_keys, left_idx, right_idx, desc, dup_build_keys, unmatched_build);
+}
+// `exchanged`: the caller swapped the inputs (right join), so the side names in *desc are swapped back
+static void join_indices_wide_sides(int how, bool exchanged, const std::vector<ColumnPtr>& left_keys, const std::vector<ColumnPtr>& right_keys, ColumnPtr& left_idx, ColumnPtr& right_idx,
+                                    std::string* desc, bool* dup_build_keys, int64_t* unmatched_build) {
   if (dup_build_keys) *dup_build_keys = false;
+  if (unmatched_build) *unmatched_build = 0;
   PLX_REQUIRE(left_keys.size() == right_keys.size() && left_keys.size() >= 2, PLX_ERR_INVALID, "wide-key join: 2 or more key columns per side, the same number on both");
   PLX_REQUIRE(left_keys.size() <= (size_t)kMaxWideKeyCols, PLX_ERR_UNSUPPORTED,
               "join on " + std::to_string(left_keys.size()) + " key columns: at most " + std::to_string(kMaxWideKeyCols) + " key columns are supported");
@@ -157,12 +176,13 @@ void join_indices_wide(int how, const std::vector<ColumnPtr>& left_keys, const s
                 std::string("join keys have different dtypes (") + dtype_name(left_keys[j]->dtype) + ", " + dtype_name(right_keys[j]->dtype) + ")");
     PLX_REQUIRE(left_keys[j]->len == left_keys[0]->len && right_keys[j]->len == right_keys[0]->len, PLX_ERR_INVALID, "join key columns of one side differ in length");
   }
-  PLX_REQUIRE(how == PLX_JOIN_INNER || how == PLX_JOIN_LEFT || how == PLX_JOIN_SEMI || how == PLX_JOIN_ANTI, PLX_ERR_UNSUPPORTED, "join type outside the hot path");
+  PLX_REQUIRE(how == PLX_JOIN_INNER || how == PLX_JOIN_LEFT || how == PLX_JOIN_SEMI || how == PLX_JOIN_ANTI || how == PLX_JOIN_FULL, PLX_ERR_UNSUPPORTED, "join type outside the hot path");
   const int64_t nl = left_keys[0]->len, nr = right_keys[0]->len;
   PLX_REQUIRE(nl < 0xffffffffll && nr < 0xffffffffll, PLX_ERR_UNSUPPORTED, "join side exceeds u32 IdxSize");
   const bool left_join = how == PLX_JOIN_LEFT;
+  const bool full = how == PLX_JOIN_FULL;
   const bool semi_anti = how == PLX_JOIN_SEMI || how == PLX_JOIN_ANTI;
-  // det_hash_prone_order, as in join_indices: left / semi / anti joins build on the right, an inner join on the right only when the left side is the larger one
+  // det_hash_prone_order, as in join_indices: left / semi / anti joins build on the right, an inner or full join on the right only when the left side is the larger one
   const bool swapped = !left_join && !semi_anti && !(nl > nr);
   const std::vector<ColumnPtr>& probe = swapped ? right_keys : left_keys;
   const std::vector<ColumnPtr>& build = swapped ? left_keys : right_keys;
@@ -203,15 +223,21 @@ void join_indices_wide(int how, const std::vector<ColumnPtr>& left_keys, const s
   }
   Buf counts = dev_alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(np, 1));
   Buf offsets = dev_alloc(sizeof(uint64_t) * (size_t)(np + 1));
+  Buf matched = full ? dev_alloc_zero((size_t)std::max<int64_t>(nb, 1)) : nullptr;               // full join: one byte per build row, set by the count pass
   if (np) {
     ProfileScope ps("join_wide_probe_count", (uint64_t)np * (row_bytes + 12 + 4), (uint64_t)np);
-    hipLaunchKernelGGL(join_wide_count_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), pk, bk, t, how, counts->as<uint32_t>());
+    if (full) hipLaunchKernelGGL(join_wide_full_count_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), pk, bk, t, counts->as<uint32_t>(), matched->as<uint8_t>());
+    else hipLaunchKernelGGL(join_wide_count_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), pk, bk, t, how, counts->as<uint32_t>());
     PLX_HIP(hipGetLastError());
   }
   k::exclusive_scan_u32(counts->as<uint32_t>(), offsets->as<uint64_t>(), np);
   uint64_t total = 0;
   d2h_sync(&total, offsets->as<uint64_t>() + np, 8);
-  PLX_REQUIRE(total < 0xffffffffull, PLX_ERR_UNSUPPORTED, "join output exceeds u32 IdxSize");
+  // full join: the unflagged build rows, known before the pair list is allocated
+  int64_t tail = 0;
+  Buf tail_rows = full ? unmatched_build_rows(matched->as<uint8_t>(), nb, &tail) : nullptr;
+  PLX_REQUIRE(total + (uint64_t)tail < 0xffffffffull, PLX_ERR_UNSUPPORTED, "join output exceeds u32 IdxSize");
+  if (unmatched_build) *unmatched_build = tail;
   auto mk_idx = [&](int64_t n) { auto c = std::make_shared<Column>(); c->dtype = PLX_U32; c->len = n; c->values = dev_alloc(values_bytes(PLX_U32, n)); c->null_count = 0; return c; };
   const std::string words = "words=" + std::to_string(nc);
   if (semi_anti) {
@@ -225,24 +251,22 @@ void join_indices_wide(int how, const std::vector<ColumnPtr>& left_keys, const s
     left_idx = kept; right_idx = nullptr;
     return;
   }
-  ColumnPtr pidx = mk_idx((int64_t)total), bidx = mk_idx((int64_t)total);
+  ColumnPtr pidx = mk_idx((int64_t)total + tail), bidx = mk_idx((int64_t)total + tail);
   if (total) {
     ProfileScope ps("join_wide_probe_emit", (uint64_t)np * (row_bytes + 12 + 16) + total * 8, (uint64_t)np);
-    hipLaunchKernelGGL(join_wide_emit_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), pk, bk, t, left_join ? 1 : 0, offsets->as<uint64_t>(),
+    hipLaunchKernelGGL(join_wide_emit_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), pk, bk, t, (left_join || full) ? 1 : 0, offsets->as<uint64_t>(),
                        pidx->values->as<uint32_t>(), bidx->values->as<uint32_t>());
     PLX_HIP(hipGetLastError());
   }
-  if (left_join && total) {
-    // unmatched rows carry the kNoRow sentinel -> validity bitmap
-    plx_scalar s; s.u = kNoRow;
-    ColumnPtr ok = ops::cmp_scalar(PLX_NE, bidx, s);
-    bidx->validity = ok->values; bidx->null_count = -1;
-    if (column_null_count(bidx) == 0) { bidx->validity = nullptr; bidx->null_count = 0; }
-  }
+  if (full) append_unmatched(tail_rows, tail, (int64_t)total, pidx, bidx);
+  // unmatched rows carry the kNoRow sentinel -> validity bitmap
+  if (left_join || full) null_out_no_row(bidx);
+  if (full) null_out_no_row(pidx);
   uint32_t f = 0; d2h_sync(&f, flags->ptr, 4);
   if (dup_build_keys) *dup_build_keys = f != 0;
-  if (desc) *desc = std::string("wide_hash_join[") + words + ", build=" + (swapped ? "left" : "right") + " rows=" + std::to_string(nb) + " cap=2^" + std::to_string(log2_cap) +
-                    (f ? " dup-keys" : " unique-keys") + ", probe rows=" + std::to_string(np) + ", pairs=" + std::to_string(total) + "]";
+  if (desc) *desc = std::string(full ? "wide_hash_full_join[" : "wide_hash_join[") + words + ", build=" + (swapped != exchanged ? "left" : "right") + " rows=" + std::to_string(nb) + " cap=2^" +
+                    std::to_string(log2_cap) + (f ? " dup-keys" : " unique-keys") + ", probe rows=" + std::to_string(np) + ", pairs=" + std::to_string(total) +
+                    (full ? ", unmatched build rows=" + std::to_string(tail) : std::string()) + "]";
   if (!swapped) { left_idx = pidx; right_idx = bidx; }
   else { left_idx = bidx; right_idx = pidx; }
 }

@@ -633,8 +633,9 @@ class DataFrame:
     def group_by(self, *keys, maintain_order: bool = False) -> "GroupBy":
         return GroupBy(self.lazy(), keys, maintain_order, eager=True)
 
-    def join(self, other: "DataFrame", on=None, how: str = "inner", left_on=None, right_on=None, suffix: str = "_right", maintain_order: str = "none") -> "DataFrame":
-        return self.lazy().join(other.lazy(), on=on, how=how, left_on=left_on, right_on=right_on, suffix=suffix, maintain_order=maintain_order).collect()
+    def join(self, other: "DataFrame", on=None, how: str = "inner", left_on=None, right_on=None, suffix: str = "_right", maintain_order: str = "none",
+             coalesce: Optional[bool] = None) -> "DataFrame":
+        return self.lazy().join(other.lazy(), on=on, how=how, left_on=left_on, right_on=right_on, suffix=suffix, maintain_order=maintain_order, coalesce=coalesce).collect()
 
     def sort(self, by, *more_by, descending=False, nulls_last=False, maintain_order: bool = False) -> "DataFrame":
         return self.lazy().sort(by, *more_by, descending=descending, nulls_last=nulls_last, maintain_order=maintain_order).collect()
@@ -777,17 +778,28 @@ class LazyFrame:
     def group_by(self, *keys, maintain_order: bool = False) -> "GroupBy":
         return GroupBy(self, keys, maintain_order)
 
-    def join(self, other: "LazyFrame", on=None, how: str = "inner", left_on=None, right_on=None, suffix: str = "_right", maintain_order: str = "none") -> "LazyFrame":
-        """maintain_order (polars JoinArgs.maintain_order): "none" (unspecified row order), "left" (left row order), "left_right" (left, then right row
-        order: a total order), "right", "right_left".  A left join takes none / left / left_right; semi / anti joins return left order whatever is asked.
+    def join(self, other: "LazyFrame", on=None, how: str = "inner", left_on=None, right_on=None, suffix: str = "_right", maintain_order: str = "none",
+             coalesce: Optional[bool] = None) -> "LazyFrame":
+        """how: "inner" | "left" | "right" | "full" | "semi" | "anti".  A full join keeps every row of both sides (null keys match nothing and count as unmatched); a right join
+        is the left join with the sides exchanged.
+        maintain_order (polars JoinArgs.maintain_order): "none" (unspecified row order), "left" (left row order), "left_right" (left, then right row
+        order: a total order), "right", "right_left".  A left join takes none / left / left_right, a right join none / right / right_left, a full join all five (the rows
+        without a row of the leading side come last, in the other side's row order); semi / anti joins return left order whatever is asked.
+        coalesce (polars JoinArgs.coalesce): None = the join kind's default (inner, left and right merge a key pair of two plain columns into one column; full keeps both, the
+        right one under `suffix`), True = merge (a full join's key holds the value of whichever side has the row; a Boolean key column cannot be merged on a full join:
+        the engine refuses it), False = keep both key columns.  Keys of different dtypes are cast to their supertype for the match and do not merge on right / full joins.
         Multi-column keys (`on=[...]` or `left_on=[...], right_on=[...]`): 2..8 columns of integer, Boolean or float dtype, column j of one dtype on both sides, any
         value range; a null in any part makes the row's key null (it matches nothing).  `last_plan()` names the route (packed into one Int64, or `wide_hash_join`)."""
         if maintain_order not in P.JOIN_ORDERS:
             raise ValueError(f"maintain_order must be one of {list(P.JOIN_ORDERS)}, got {maintain_order!r}")
+        if not isinstance(how, str) or how not in P.JOIN_HOWS:
+            raise ValueError(f"how must be one of {list(P.JOIN_HOWS)}, got {how!r}")
+        if coalesce is not None and not isinstance(coalesce, bool):
+            raise ValueError(f"coalesce must be None, True or False, got {coalesce!r}")
         if on is not None:
             left_on = right_on = on
         lo, ro = _as_exprs([left_on]), _as_exprs([right_on])
-        return LazyFrame(P.Node("join", left=self._node, right=other._node, left_on=lo, right_on=ro, how=how, suffix=suffix, maintain_order=maintain_order))
+        return LazyFrame(P.Node("join", left=self._node, right=other._node, left_on=lo, right_on=ro, how=how, suffix=suffix, maintain_order=maintain_order, coalesce=coalesce))
 
     def sort(self, by, *more_by, descending=False, nulls_last=False, maintain_order: bool = False) -> "LazyFrame":
         """LazyFrame.sort (py-polars lazyframe/frame.py sort): `descending` / `nulls_last` are one flag or one per key.

@@ -770,11 +770,7 @@ def output_names(n: P.Node) -> List[str]:
     if k == "group_by":
         return [P.expr_output_name(e) for e in n.keys] + [P.expr_output_name(e) for e in n.aggs]
     if k == "join":
-        left = output_names(n.left)
-        if n.how in ("semi", "anti"):
-            return left
-        rkeys = {b.name for a, b in zip(n.left_on, n.right_on) if a.kind == "col" and b.kind == "col"}
-        return left + [(r + n.suffix if r in left else r) for r in output_names(n.right) if r not in rkeys]
+        return list(P.join_schema(n.how, getattr(n, "coalesce", None), n.left_on, n.right_on, dict.fromkeys(output_names(n.left)), dict.fromkeys(output_names(n.right)), n.suffix))
     raise TypeError(k)
 
 

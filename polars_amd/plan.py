@@ -31,6 +31,33 @@ class Node:
 JOIN_ORDERS = {"none": F.JOIN_ORDER_NONE, "left": F.JOIN_ORDER_LEFT, "right": F.JOIN_ORDER_RIGHT, "left_right": F.JOIN_ORDER_LEFT_RIGHT, "right_left": F.JOIN_ORDER_RIGHT_LEFT}
 
 
+# join kinds -> plx_join_how; JoinArgs.coalesce (None: the kind's default, True, False) -> plx_ir.coalesce
+JOIN_HOWS = {"inner": F.JOIN_INNER, "left": F.JOIN_LEFT, "semi": F.JOIN_SEMI, "anti": F.JOIN_ANTI, "full": F.JOIN_FULL, "right": F.JOIN_RIGHT}
+JOIN_COALESCE = {None: F.JOIN_COALESCE_DEFAULT, True: F.JOIN_COALESCE, False: F.JOIN_KEEP_BOTH}
+
+
+def join_schema(how: str, coalesce, left_on, right_on, ls: Schema, rs: Schema, suffix: str) -> Schema:
+    """Output columns of a join (plx_ir.coalesce in include/polars_amd.h): left columns, then right columns, the suffix on a right name that clashes.  A key pair of two
+    plain columns coalesces unless told otherwise (a full join: only when told to): inner / left / full drop the right key, a right join drops the left key.
+    On right and full joins a pair whose dtypes differ does not coalesce: lowering casts such keys to their supertype, and the engine merges plain columns only
+    (schemas that carry dtypes, i.e. lowering and collect_schema; inner / left joins keep the rule they had)."""
+    if how in ("semi", "anti"):            # left columns only (single_keys_semi_anti.rs)
+        return dict(ls)
+    merge = (how != "full") if coalesce is None else bool(coalesce)
+    def cast_apart(a, b):
+        adt, bdt = ls.get(a.name), rs.get(b.name)
+        return how in ("right", "full") and adt is not None and bdt is not None and adt.physical != bdt.physical
+    plain = [(a.name, b.name) for a, b in zip(left_on, right_on) if a.kind == "col" and b.kind == "col" and not cast_apart(a, b)] if merge else []
+    drop_left = {a for a, _ in plain} if how == "right" else set()
+    drop_right = {b for _, b in plain} if how != "right" else set()
+    out = {name: dt for name, dt in ls.items() if name not in drop_left}
+    for name, dt in rs.items():
+        if name in drop_right:
+            continue
+        out[name + suffix if name in out else name] = dt
+    return out
+
+
 def describe_join_orders(node: Node) -> List[str]:
     """One line per join under `node` that was asked to keep a row order (LazyFrame.explain)."""
     out: List[str] = []
@@ -283,7 +310,7 @@ class Lowering:
     def lower_node(self, n: Node) -> Tuple[int, Schema]:
         def push(**kw) -> int:
             node = dict(kind=0, input=-1, input_right=-1, predicate=-1, frame=None, exprs=[], keys=[], keys_right=[], how=0,
-                        maintain_order=0, suffix="_right", sort_descending=[], sort_nulls_last=[], slice_offset=0, slice_len=0)
+                        maintain_order=0, suffix="_right", sort_descending=[], sort_nulls_last=[], slice_offset=0, slice_len=0, coalesce=0)
             node.update(kw)
             self.irs.append(node)
             return len(self.irs) - 1
@@ -332,17 +359,13 @@ class Lowering:
                     bi = self._cast(bi, bdt, st)
                 lk.append(ai)
                 rk.append(bi)
-            how = {"inner": F.JOIN_INNER, "left": F.JOIN_LEFT, "semi": F.JOIN_SEMI, "anti": F.JOIN_ANTI}[n.how]
+            if n.how not in JOIN_HOWS:
+                raise ValueError(f"how must be one of {list(JOIN_HOWS)}, got {n.how!r}")
+            how = JOIN_HOWS[n.how]
             order = JOIN_ORDERS[getattr(n, "maintain_order", "none")]
-            if n.how in ("semi", "anti"):   # left columns only (single_keys_semi_anti.rs)
-                return push(kind=F.IR_JOIN, input=li, input_right=ri, keys=lk, keys_right=rk, how=how, suffix=n.suffix, maintain_order=order), dict(ls)
-            out_schema = dict(ls)
-            right_key_names = {b.name for a, b in zip(n.left_on, n.right_on) if b.kind == "col" and a.kind == "col"}
-            for name, dt in rs.items():
-                if name in right_key_names:
-                    continue
-                out_schema[name + n.suffix if name in out_schema else name] = dt
-            return push(kind=F.IR_JOIN, input=li, input_right=ri, keys=lk, keys_right=rk, how=how, suffix=n.suffix, maintain_order=order), out_schema
+            coalesce = getattr(n, "coalesce", None)
+            out_schema = join_schema(n.how, coalesce, n.left_on, n.right_on, ls, rs, n.suffix)
+            return push(kind=F.IR_JOIN, input=li, input_right=ri, keys=lk, keys_right=rk, how=how, suffix=n.suffix, maintain_order=order, coalesce=JOIN_COALESCE[coalesce]), out_schema
         if k == "sort":
             inp, schema = self.lower_node(n.input)
             keys = [self.lower_expr(e, schema)[0] for e in n.by]
@@ -402,6 +425,7 @@ class Lowering:
                     keep.append(arr)
                     setattr(r, field, C.cast(arr, C.POINTER(C.c_uint8)))
             r.slice_offset, r.slice_len = d["slice_offset"], d["slice_len"]
+            r.coalesce = d["coalesce"]
         return ir, n_ir, ae, n_ae, keep
 
 

@@ -213,14 +213,17 @@ class Translator:
         if kind == "Join":
             how, nulls_equal, jslice, suffix, coalesce, _maintain = node.options      # visitor/nodes.rs:583-652
             how = how if isinstance(how, str) else how[0]
-            if how not in ("inner", "left", "semi", "anti") or nulls_equal or jslice is not None or not coalesce and how in ("inner", "left"):
+            # (the optimized plan carries `coalesce` resolved to a bool.  A full join reaches this engine in its default form, both keys kept; a full join that was asked to
+            # coalesce stays with the CPU engine)
+            if how not in ("inner", "left", "semi", "anti", "full", "right") or nulls_equal or jslice is not None or (how == "full" and coalesce):
                 raise NotSupported(f"join options how={how} nulls_equal={nulls_equal} slice={jslice} coalesce={coalesce}")
             order = str(_maintain)                                                     # MaintainOrderJoin as its snake_case name
-            if order not in ("none", "left", "right", "left_right", "right_left") or (how == "left" and order in ("right", "right_left")):
+            if (order not in ("none", "left", "right", "left_right", "right_left") or (how == "left" and order in ("right", "right_left"))
+                    or (how == "right" and order in ("left", "left_right"))):
                 raise NotSupported(f"join how={how} maintain_order={order}")
             left, right = self.plan(node.input_left), self.plan(node.input_right)
             return left.join(right, left_on=[self.named(e) for e in node.left_on], right_on=[self.named(e) for e in node.right_on], how=how, suffix=str(suffix),
-                             maintain_order=order)
+                             maintain_order=order, coalesce=None if how in ("semi", "anti") or bool(coalesce) == (how != "full") else bool(coalesce))
         if kind == "Sort":
             maintain_order, nulls_last, descending = node.sort_options                 # visitor/nodes.rs:533-549
             out = self.plan(node.input).sort([self.named(e) for e in node.by_column], descending=list(descending), nulls_last=list(nulls_last),
