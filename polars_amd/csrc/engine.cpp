@@ -2681,11 +2681,8 @@ static FramePtr exec_join(Plan& plan, const IRN& n) {
   int64_t unmatched_build = 0;         // full join: the pairs (no probe row, build row) at the end of the pair list
   const bool full = n.how == PLX_JOIN_FULL, right_join = n.how == PLX_JOIN_RIGHT;
   const bool coalesce = n.coalesce == 1 || (n.coalesce == 0 && !full);      // plx_ir.coalesce: 0 = the kind's default (full joins keep both keys)
-  if (!wide_why.empty()) {
-    join::join_indices_wide(n.how, lraw, rraw, li, ri, &d, &dup_build_keys, &unmatched_build);
-    const size_t at = d.find(", build=");     // "wide_hash_join[words=N, build=...": the reason goes behind the word count
-    if (at != std::string::npos) d.insert(at, " (" + wide_why + ")");
-  } else join::join_indices(n.how, lk, rk, li, ri, &d, &dup_build_keys, &unmatched_build);
+  if (!wide_why.empty()) join::join_indices_wide(n.how, lraw, rraw, li, ri, &d, &dup_build_keys, &unmatched_build, wide_why);
+  else join::join_indices(n.how, lk, rk, li, ri, &d, &dup_build_keys, &unmatched_build);
   d = packed_desc + d;
   if (n.maintain_order != PLX_JOIN_ORDER_NONE && n.how != PLX_JOIN_SEMI && n.how != PLX_JOIN_ANTI) {
     // join_indices emits at scanned offsets: probe order; its chains (duplicate build keys) are newest first.  It builds on the right unless the left side is not the larger one of an

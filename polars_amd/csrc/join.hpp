@@ -1,4 +1,5 @@
-// join.hpp -- hash join on one key column pair (kernels_join.hip) or on a key of several columns (kernels_join_wide.hip).
+// join.hpp -- hash join on one key column pair (kernels_join.hip) or on a key of several columns (kernels_join_wide.hip); both are one driver and one set of row loops
+// (join_driver.hpp) under a key policy per route.
 // Replaces polars-ops/src/frame/join/hash_join/{single_keys.rs:16-167 (build_tables),
 // single_keys_inner.rs:11-149 (probe_inner / hash_join_tuples_inner),
 // single_keys_left.rs:106-195, single_keys_dispatch.rs:234-357,476-553}.
@@ -22,9 +23,9 @@ void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key
                   int64_t* unmatched_build = nullptr);
 // The same contract on a key of 2..8 columns of any integer / Boolean / float dtype (kernels_join_wide.hip; column j has one dtype on both sides, a null in any part makes
 // the row's key null).  The table holds row ids, the key words are compared at the build columns; *desc = "wide_hash_join[words=N, ...]" / wide_hash_semi_join / wide_hash_anti_join /
-// wide_hash_full_join.
+// wide_hash_full_join; `why` (may be empty) = the caller's reason for this route, written behind the word count: "wide_hash_join[words=N (why), ...]".
 void join_indices_wide(int how, const std::vector<ColumnPtr>& left_keys, const std::vector<ColumnPtr>& right_keys, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc,
-                       bool* dup_build_keys = nullptr, int64_t* unmatched_build = nullptr);
+                       bool* dup_build_keys = nullptr, int64_t* unmatched_build = nullptr, const std::string& why = std::string());
 // The coalesced key column of a full join: lkey at left_idx where the pair has a left row, rkey at right_idx otherwise; validity from the side that was read.
 // Key columns of one dtype, 1 / 2 / 4 / 8 bytes wide.
 ColumnPtr coalesce_keys(const ColumnPtr& lkey, const ColumnPtr& rkey, const ColumnPtr& left_idx, const ColumnPtr& right_idx);

@@ -1,4 +1,5 @@
-// join_keys.hpp -- how the join kernels read a key column (device-only header shared by kernels_join.hip and kernels_join_wide.hip).
+// join_keys.hpp -- how the join kernels read a key column, and the host helpers of kernels_join.hip that every join route calls (shared by kernels_join.hip,
+// kernels_join_wide.hip and kernels_join_order.hip; the table, the row loops and the driver the two hash-join routes share are join_driver.hpp).
 // A key is read in its physical dtype and widened to one 64-bit word in registers (no materialised 64-bit key copy); floats are
 // canonicalised (-0 -> +0, one NaN: total_ord.rs:40-48) so that equal keys have equal words.
 #pragma once
@@ -44,6 +45,8 @@ void emit_kept_rows(const uint32_t* counts, const uint64_t* offsets, int64_t n, 
 // compaction of kernels_filter.hip; *n_out of them; synchronises), and (kNoRow, row) for them written behind the first `at` pairs of the two index columns
 Buf unmatched_build_rows(const uint8_t* matched, int64_t nb, int64_t* n_out);
 void append_unmatched(const Buf& rows, int64_t n, int64_t at, const ColumnPtr& probe_idx, const ColumnPtr& build_idx);
+// a PLX_U32 index column of n rows without nulls, values uninitialised (room for at least min_alloc_rows)
+ColumnPtr make_idx_column(int64_t n, int64_t min_alloc_rows = 0);
 // the kNoRow entries of an index column become nulls (validity bitmap; none when no entry is kNoRow)
 void null_out_no_row(ColumnPtr& idx);
 

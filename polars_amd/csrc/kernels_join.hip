@@ -13,6 +13,9 @@
 // Keys are read in their physical dtype and widened in registers (no materialised
 // 64-bit key copy); floats are canonicalised (-0 -> +0, one NaN: total_ord.rs:40-48).
 // Null keys never match (nulls_equal = false).
+// This file holds the SINGLE-KEY POLICY (Table, SingleKey: the key-word table and its two walks) and the __global__ wrappers join_build_kernel / join_count_kernel /
+// join_full_count_kernel / join_emit_kernel; the row loops they wrap and the host driver behind join_indices are join_driver.hpp, shared with kernels_join_wide.hip.
+// The helpers both routes call (index columns, kNoRow -> validity, the kept rows of semi / anti joins, a full join's unmatched tail) are here too.
 // Right join: the left join with the sides exchanged (the left input is the build side, left_idx the nullable index).  Full join: the probe side is joined as a
 // left join; the count pass also flags every build row it walks over (one byte per row, plain stores of the constant 1), the unflagged rows -- null keys were
 // never inserted, so they stay unflagged -- are ballotted into selection words and compacted in row order (kernels_filter.hip), and (kNoRow, row) is appended for
@@ -21,6 +24,7 @@
 #include "dev.hpp"
 #include "fused.hpp"
 #include "join.hpp"
+#include "join_driver.hpp"
 #include "join_keys.hpp"
 #include "kernels.hpp"
 #include "ops.hpp"
@@ -32,67 +36,83 @@ namespace join {
 using namespace dev;
 using k::kBlock;
 
+// The single-key policy of join_driver.hpp (a key packed from several columns is one Int64 column here).  The table holds the key words and the row's "hash" is the key word
+// itself, so the `build` column is not read on the probe side (the single-key kernels have no such argument: their wrappers pass the probe column).
 struct Table {
   unsigned long long* keys;  // [cap + 1]; slot cap = the key whose bits equal kEmpty
-  unsigned int* head;        // [cap + 1]
-  unsigned int* next;        // [n_build]
-  unsigned int* flags;       // [0] = a chain longer than 1 exists (build keys not unique)
-  uint32_t log2_cap;
+  Chains ch;                 // head[cap + 1]
+};
+struct SingleKey {
+  using Keys = KeyCol;
+  using Table = join::Table;
+  static __device__ __forceinline__ bool hash_row(const KeyCol& kc, int64_t i, uint64_t* key) {
+    if (!key_valid(kc, i)) return false;
+    *key = load_key(kc, i);
+    return true;
+  }
+  // the walk both sides make; kClaim (build side): an empty slot is claimed for the key with one 64-bit CAS
+  template <bool kClaim>
+  static __device__ __forceinline__ int64_t walk(const Table& t, uint64_t key) {
+    const uint64_t cap = 1ull << t.ch.log2_cap;
+    if (key == kEmpty) return (int64_t)cap;
+    uint64_t slot = (key * kRandomOdd) >> (64 - t.ch.log2_cap);
+    for (;;) {
+      unsigned long long cur = t.keys[slot];
+      if (cur == key) return (int64_t)slot;
+      if (cur == kEmpty) {
+        if constexpr (!kClaim) return -1;
+        unsigned long long old = atomicCAS(&t.keys[slot], (unsigned long long)kEmpty, (unsigned long long)key);
+        if (old == kEmpty || old == key) return (int64_t)slot;
+      }
+      slot = (slot + 1) & (cap - 1);
+    }
+  }
+  static __device__ __forceinline__ int64_t find_or_claim(const Table& t, const KeyCol&, int64_t, uint64_t key) { return walk<true>(t, key); }
+  static __device__ __forceinline__ int64_t find(const Table& t, const KeyCol&, int64_t, const KeyCol&, uint64_t key) { return walk<false>(t, key); }
+
+  // host side
+  using HostKeys = ColumnPtr;
+  static int64_t rows(const ColumnPtr& c) { return c->len; }
+  static constexpr uint64_t kSlotsBeyondCap = 1;
+  // a pair list beyond the u32 IdxSize is refused for full joins only (their tail is appended at a u32-checked place); an inner join with more pairs runs, as it always has
+  static constexpr bool kRefuseLargeOutputAlways = false;
+  static constexpr const char* kPlanPrefix = "";
+  static constexpr const char *kBuildScope = "join_build", *kCountScope = "join_probe_count", *kEmitScope = "join_probe_emit";
+  static constexpr uint64_t kBuildSlotBytes = 0, kCountSlotBytes = 4, kEmitSlotBytes = 8;       // declared bytes per row next to the key: the count / the two offsets
+  std::string plan_lead() const { return std::string(); }
+  uint64_t key_bytes = 0;
+  Buf keys;
+  KeyCol probe, build;
+  Table table;
+  void prepare(const ColumnPtr& probe_key, const ColumnPtr& build_key, const Chains& ch) {
+    const uint64_t slots = (1ull << ch.log2_cap) + kSlotsBeyondCap;
+    keys = dev_alloc(sizeof(uint64_t) * slots);
+    PLX_HIP(hipMemsetAsync(keys->ptr, 0xff, sizeof(uint64_t) * slots, stream()));
+    table.keys = keys->as<unsigned long long>(); table.ch = ch;
+    probe = key_col(probe_key); build = key_col(build_key);
+    key_bytes = dtype_width(build_key->dtype) ? dtype_width(build_key->dtype) : 1;
+  }
+  void launch_build(int grid);
+  void launch_count(int grid, int how, uint32_t* counts, uint8_t* matched);
+  void launch_emit(int grid, int left_join, const uint64_t* offsets, uint32_t* out_probe, uint32_t* out_build);
 };
 
-__device__ __forceinline__ int64_t find_or_claim(const Table& t, uint64_t key) {
-  const uint64_t cap = 1ull << t.log2_cap;
-  if (key == kEmpty) return (int64_t)cap;
-  uint64_t slot = (key * kRandomOdd) >> (64 - t.log2_cap);
-  for (;;) {
-    unsigned long long cur = t.keys[slot];
-    if (cur == key) return (int64_t)slot;
-    if (cur == kEmpty) {
-      unsigned long long old = atomicCAS(&t.keys[slot], (unsigned long long)kEmpty, (unsigned long long)key);
-      if (old == kEmpty || old == key) return (int64_t)slot;
-    }
-    slot = (slot + 1) & (cap - 1);
-  }
-}
-__device__ __forceinline__ int64_t find_slot(const Table& t, uint64_t key) {
-  const uint64_t cap = 1ull << t.log2_cap;
-  if (key == kEmpty) return (int64_t)cap;
-  uint64_t slot = (key * kRandomOdd) >> (64 - t.log2_cap);
-  for (;;) {
-    unsigned long long cur = t.keys[slot];
-    if (cur == key) return (int64_t)slot;
-    if (cur == kEmpty) return -1;
-    slot = (slot + 1) & (cap - 1);
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void join_build_kernel(KeyCol build, Table t) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < build.n; i += (int64_t)gridDim.x * blockDim.x) {
-    if (!key_valid(build, i)) { t.next[i] = kNoRow; continue; }
-    const int64_t slot = find_or_claim(t, load_key(build, i));
-    const unsigned int old = atomicExch(&t.head[slot], (unsigned int)i);
-    t.next[i] = old;
-    if (old != kNoRow) t.flags[0] = 1u;
-  }
-}
-
-// counts[i] = number of build matches of probe row i (left join: at least 1).  kFlag (full join): matched[r] = 1 for every build row r on the chain -- several probe
-// rows that hit one build row store the same byte, so no atomic is needed; the other join kinds run the instantiation without the store.
-template <bool kFlag>
-__device__ __forceinline__ void join_count_rows(const KeyCol& probe, const Table& t, int how, uint32_t* __restrict__ counts, uint8_t* __restrict__ matched) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < probe.n; i += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t c = 0;
-    if (key_valid(probe, i)) {
-      const int64_t slot = find_slot(t, load_key(probe, i));
-      if (slot >= 0) { for (unsigned int r = t.head[slot]; r != kNoRow; r = t.next[r]) { c++; if constexpr (kFlag) matched[r] = 1; } }
-    }
-    // how: 0 inner, 1 left (unmatched rows emit one pair), 2 semi (row kept once if matched), 3 anti (kept if unmatched; null keys never match)
-    counts[i] = how == 2 ? (c ? 1u : 0u) : how == 3 ? (c ? 0u : 1u) : (how == 1 && c == 0) ? 1u : c;
-  }
-}
-__global__ __launch_bounds__(kBlock) void join_count_kernel(KeyCol probe, Table t, int how, uint32_t* __restrict__ counts) { join_count_rows<false>(probe, t, how, counts, nullptr); }
+__global__ __launch_bounds__(kBlock) void join_build_kernel(KeyCol build, Table t) { join_build_rows<SingleKey>(build, t); }
+__global__ __launch_bounds__(kBlock) void join_count_kernel(KeyCol probe, Table t, int how, uint32_t* __restrict__ counts) { join_count_rows<SingleKey, false>(probe, probe, t, how, counts, nullptr); }
 __global__ __launch_bounds__(kBlock) void join_full_count_kernel(KeyCol probe, Table t, uint32_t* __restrict__ counts, uint8_t* __restrict__ matched) {
-  join_count_rows<true>(probe, t, 1, counts, matched);
+  join_count_rows<SingleKey, true>(probe, probe, t, 1, counts, matched);
+}
+__global__ __launch_bounds__(kBlock) void join_emit_kernel(KeyCol probe, Table t, int left_join, const uint64_t* __restrict__ offsets, uint32_t* __restrict__ out_probe,
+                                                           uint32_t* __restrict__ out_build) {
+  join_emit_rows<SingleKey>(probe, probe, t, left_join, offsets, out_probe, out_build);
+}
+void SingleKey::launch_build(int grid) { hipLaunchKernelGGL(join_build_kernel, dim3(grid), dim3(kBlock), 0, stream(), build, table); }
+void SingleKey::launch_count(int grid, int how, uint32_t* counts, uint8_t* matched) {
+  if (matched) hipLaunchKernelGGL(join_full_count_kernel, dim3(grid), dim3(kBlock), 0, stream(), probe, table, counts, matched);
+  else hipLaunchKernelGGL(join_count_kernel, dim3(grid), dim3(kBlock), 0, stream(), probe, table, how, counts);
+}
+void SingleKey::launch_emit(int grid, int left_join, const uint64_t* offsets, uint32_t* out_probe, uint32_t* out_build) {
+  hipLaunchKernelGGL(join_emit_kernel, dim3(grid), dim3(kBlock), 0, stream(), probe, table, left_join, offsets, out_probe, out_build);
 }
 
 // full join, after the count pass: bit i of mask = build row i was flagged by no probe row (one ballot per 64 rows; the pad bits of the last word are cleared)
@@ -117,26 +137,16 @@ __global__ __launch_bounds__(kBlock) void join_emit_kept_kernel(const uint32_t* 
     if (counts[i]) out_probe[offsets[i]] = (uint32_t)i;
 }
 
-__global__ __launch_bounds__(kBlock) void join_emit_kernel(KeyCol probe, Table t, int left_join, const uint64_t* __restrict__ offsets,
-                                                           uint32_t* __restrict__ out_probe, uint32_t* __restrict__ out_build) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < probe.n; i += (int64_t)gridDim.x * blockDim.x) {
-    uint64_t o = offsets[i];
-    bool any = false;
-    if (key_valid(probe, i)) {
-      const int64_t slot = find_slot(t, load_key(probe, i));
-      if (slot >= 0) {
-        for (unsigned int r = t.head[slot]; r != kNoRow; r = t.next[r]) { out_probe[o] = (uint32_t)i; out_build[o] = r; o++; any = true; }
-      }
-    }
-    if (left_join && !any) { out_probe[o] = (uint32_t)i; out_build[o] = kNoRow; }
-  }
-}
-
 void emit_kept_rows(const uint32_t* counts, const uint64_t* offsets, int64_t n, uint32_t* out_probe) {
   hipLaunchKernelGGL(join_emit_kept_kernel, dim3(k::grid_for(n, kBlock * 2)), dim3(kBlock), 0, stream(), counts, offsets, n, out_probe);
   PLX_HIP(hipGetLastError());
 }
 
+ColumnPtr make_idx_column(int64_t n, int64_t min_alloc_rows) {
+  auto c = std::make_shared<Column>();
+  c->dtype = PLX_U32; c->len = n; c->values = dev_alloc(values_bytes(PLX_U32, std::max(n, min_alloc_rows))); c->null_count = 0;
+  return c;
+}
 void null_out_no_row(ColumnPtr& idx) {
   if (!idx->len) return;
   plx_scalar s; s.u = kNoRow;
@@ -222,94 +232,11 @@ ColumnPtr coalesce_keys(const ColumnPtr& lkey, const ColumnPtr& rkey, const Colu
   return out;
 }
 
-static void join_indices_sides(int how, bool exchanged, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys,
-                               int64_t* unmatched_build);
 void join_indices(int how, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys, int64_t* unmatched_build) {
-  // a right join is the left join with the sides exchanged: the left input is the build side, left_idx the nullable index
-  if (how == PLX_JOIN_RIGHT) join_indices_sides(PLX_JOIN_LEFT, true, right_key, left_key, right_idx, left_idx, desc, dup_build_keys, unmatched_build);
-  else join_indices_sides(how, false, left_key, right_key, left_idx, right_idx, desc, dup_build_keys, unmatched_build);
-}
-// `exchanged`: the caller swapped the inputs (right join), so the side names in *desc are swapped back
-static void join_indices_sides(int how, bool exchanged, const ColumnPtr& left_key, const ColumnPtr& right_key, ColumnPtr& left_idx, ColumnPtr& right_idx, std::string* desc, bool* dup_build_keys,
-                               int64_t* unmatched_build) {
-  if (dup_build_keys) *dup_build_keys = false;
-  if (unmatched_build) *unmatched_build = 0;
   PLX_REQUIRE(left_key->dtype == right_key->dtype, PLX_ERR_INVALID,
               std::string("join keys have different dtypes (") + dtype_name(left_key->dtype) + ", " + dtype_name(right_key->dtype) + ")");
-  PLX_REQUIRE(how == PLX_JOIN_INNER || how == PLX_JOIN_LEFT || how == PLX_JOIN_SEMI || how == PLX_JOIN_ANTI || how == PLX_JOIN_FULL, PLX_ERR_UNSUPPORTED, "join type outside the hot path");
-  PLX_REQUIRE(left_key->len < 0xffffffffll && right_key->len < 0xffffffffll, PLX_ERR_UNSUPPORTED, "join side exceeds u32 IdxSize");
-  const bool left_join = how == PLX_JOIN_LEFT;
-  const bool full = how == PLX_JOIN_FULL;
-  const bool semi_anti = how == PLX_JOIN_SEMI || how == PLX_JOIN_ANTI;
-  // det_hash_prone_order (hash_join/mod.rs:41-50): build on the shorter relation (inner and full joins); left / semi / anti joins build on the right
-  const bool swapped = !left_join && !semi_anti && !(left_key->len > right_key->len);
-  const ColumnPtr& probe = (left_join || semi_anti) ? left_key : (swapped ? right_key : left_key);
-  const ColumnPtr& build = (left_join || semi_anti) ? right_key : (swapped ? left_key : right_key);
-  const int log2_cap = std::max(4, ceil_log2((uint64_t)std::max<int64_t>(build->len, 1) * 2));
-  const uint64_t cap = 1ull << log2_cap;
-  Buf keys = dev_alloc(sizeof(uint64_t) * (cap + 1));
-  Buf head = dev_alloc(sizeof(uint32_t) * (cap + 1));
-  Buf next = dev_alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(build->len, 1));
-  Buf flags = dev_alloc_zero(16);
-  PLX_HIP(hipMemsetAsync(keys->ptr, 0xff, sizeof(uint64_t) * (cap + 1), stream()));
-  PLX_HIP(hipMemsetAsync(head->ptr, 0xff, sizeof(uint32_t) * (cap + 1), stream()));
-  Table t; t.keys = keys->as<unsigned long long>(); t.head = head->as<unsigned int>(); t.next = next->as<unsigned int>(); t.flags = flags->as<unsigned int>(); t.log2_cap = (uint32_t)log2_cap;
-  const int kw = dtype_width(build->dtype) ? dtype_width(build->dtype) : 1;
-  if (build->len) {
-    ProfileScope ps("join_build", (uint64_t)build->len * kw, (uint64_t)build->len);
-    hipLaunchKernelGGL(join_build_kernel, dim3(k::grid_for(build->len, kBlock * 2)), dim3(kBlock), 0, stream(), key_col(build), t);
-    PLX_HIP(hipGetLastError());
-  }
-  const int64_t np = probe->len;
-  Buf counts = dev_alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(np, 1));
-  Buf offsets = dev_alloc(sizeof(uint64_t) * (size_t)(np + 1));
-  Buf matched = full ? dev_alloc_zero((size_t)std::max<int64_t>(build->len, 1)) : nullptr;     // full join: one byte per build row, set by the count pass
-  if (np) {
-    ProfileScope ps("join_probe_count", (uint64_t)np * (kw + 4), (uint64_t)np);
-    if (full) hipLaunchKernelGGL(join_full_count_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), key_col(probe), t, counts->as<uint32_t>(), matched->as<uint8_t>());
-    else hipLaunchKernelGGL(join_count_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), key_col(probe), t, how, counts->as<uint32_t>());
-    PLX_HIP(hipGetLastError());
-  }
-  k::exclusive_scan_u32(counts->as<uint32_t>(), offsets->as<uint64_t>(), np);
-  uint64_t total = 0;
-  d2h_sync(&total, offsets->as<uint64_t>() + np, 8);
-  // full join: the unflagged build rows, known before the pair list is allocated
-  int64_t tail = 0;
-  Buf tail_rows = full ? unmatched_build_rows(matched->as<uint8_t>(), build->len, &tail) : nullptr;
-  PLX_REQUIRE(!full || total + (uint64_t)tail < 0xffffffffull, PLX_ERR_UNSUPPORTED, "join output exceeds u32 IdxSize");
-  if (unmatched_build) *unmatched_build = tail;
-  auto mk_idx = [&](int64_t n) { auto c = std::make_shared<Column>(); c->dtype = PLX_U32; c->len = n; c->values = dev_alloc(values_bytes(PLX_U32, n)); c->null_count = 0; return c; };
-  if (semi_anti) {
-    ColumnPtr kept = mk_idx((int64_t)total);
-    if (total) {
-      ProfileScope ps("join_emit_kept", (uint64_t)np * 12 + total * 4, (uint64_t)np);
-      emit_kept_rows(counts->as<uint32_t>(), offsets->as<uint64_t>(), np, kept->values->as<uint32_t>());
-    }
-    if (desc) *desc = std::string(how == PLX_JOIN_SEMI ? "hash_semi_join" : "hash_anti_join") + "[build=right rows=" + std::to_string(build->len) + " cap=2^" + std::to_string(log2_cap) +
-                      ", probe rows=" + std::to_string(np) + ", kept=" + std::to_string(total) + "]";
-    left_idx = kept; right_idx = nullptr;
-    return;
-  }
-  ColumnPtr pidx = mk_idx((int64_t)total + tail), bidx = mk_idx((int64_t)total + tail);
-  if (total) {
-    ProfileScope ps("join_probe_emit", (uint64_t)np * (kw + 8) + total * 8, (uint64_t)np);
-    hipLaunchKernelGGL(join_emit_kernel, dim3(k::grid_for(np, kBlock * 2)), dim3(kBlock), 0, stream(), key_col(probe), t, (left_join || full) ? 1 : 0, offsets->as<uint64_t>(),
-                       pidx->values->as<uint32_t>(), bidx->values->as<uint32_t>());
-    PLX_HIP(hipGetLastError());
-  }
-  if (full) append_unmatched(tail_rows, tail, (int64_t)total, pidx, bidx);
-  // unmatched rows carry the kNoRow sentinel -> validity bitmap
-  if (left_join || full) null_out_no_row(bidx);
-  if (full) null_out_no_row(pidx);
-  if (desc || dup_build_keys) {
-    uint32_t f = 0; d2h_sync(&f, flags->ptr, 4);
-    if (dup_build_keys) *dup_build_keys = f != 0;
-    const bool build_is_left = (left_join ? false : swapped) != exchanged;
-    if (desc) *desc = std::string(full ? "hash_full_join[build=" : "hash_join[build=") + (build_is_left ? "left" : "right") + " rows=" + std::to_string(build->len) + " cap=2^" + std::to_string(log2_cap) +
-            (f ? " dup-keys" : " unique-keys") + ", probe rows=" + std::to_string(np) + ", pairs=" + std::to_string(total) + (full ? ", unmatched build rows=" + std::to_string(tail) : std::string()) + "]";
-  }
-  if (left_join || !swapped) { left_idx = pidx; right_idx = bidx; }
-  else { left_idx = bidx; right_idx = pidx; }
+  SingleKey p;
+  join_indices_driver(p, how, left_key, right_key, left_idx, right_idx, desc, dup_build_keys, unmatched_build);
 }
 
 // ------------------------------------------------ materialising join: pairs over a candidate list ---
@@ -396,11 +323,10 @@ static void join_pairs_impl(int how, const ColumnPtr& probe_key, const ColumnPtr
   PLX_REQUIRE(probe_key->len < 0xffffffffll, PLX_ERR_UNSUPPORTED, "join side exceeds u32 IdxSize");
   const bool left = how == PLX_JOIN_LEFT, multi = t.links != nullptr;
   const int64_t n = cand ? cand->len : probe_key->len;
-  auto mk_idx = [&](int64_t m) { auto c = std::make_shared<Column>(); c->dtype = PLX_U32; c->len = m; c->values = dev_alloc(values_bytes(PLX_U32, std::max<int64_t>(m, 1))); c->null_count = 0; return c; };
-  if (n == 0) { probe_idx = mk_idx(0); build_idx = mk_idx(0); if (desc) *desc = "join_pairs[no candidates]"; return; }
+  if (n == 0) { probe_idx = make_idx_column(0, 1); build_idx = make_idx_column(0, 1); if (desc) *desc = "join_pairs[no candidates]"; return; }
   const uint32_t* cp = cand ? cand->values->as<uint32_t>() : nullptr;
   const int kw = dtype_width(probe_key->dtype) ? dtype_width(probe_key->dtype) : 1;
-  ColumnPtr head = mk_idx(n);
+  ColumnPtr head = make_idx_column(n, 1);
   const bool counted = multi;                           // unique build keys: 0 / 1 pairs per candidate (left join: exactly 1), no scan
   Buf cnt = counted ? dev_alloc(sizeof(uint32_t) * (size_t)n) : nullptr;
   const int64_t nwords = (n + 63) >> 6;
@@ -415,14 +341,14 @@ static void join_pairs_impl(int how, const ColumnPtr& probe_key, const ColumnPtr
   if (!counted && left) {
     // one pair per candidate: the candidate list IS the probe index, the heads are the build index
     if (cand) probe_idx = cand;
-    else { probe_idx = mk_idx(n); hipLaunchKernelGGL(iota_u32_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), probe_idx->values->as<uint32_t>(), n); PLX_HIP(hipGetLastError()); }
+    else { probe_idx = make_idx_column(n, 1); hipLaunchKernelGGL(iota_u32_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), probe_idx->values->as<uint32_t>(), n); PLX_HIP(hipGetLastError()); }
     build_idx = head;
     null_out_no_row(build_idx);
     total = (uint64_t)n;
   } else if (!counted) {
     const k::FilterPlan fp = k::filter_prepare(mask->as<uint64_t>(), n);
     total = (uint64_t)fp.n_out;
-    probe_idx = mk_idx(fp.n_out); build_idx = mk_idx(fp.n_out);
+    probe_idx = make_idx_column(fp.n_out, 1); build_idx = make_idx_column(fp.n_out, 1);
     if (cand) k::filter_apply(fp, 4, cp, nullptr, probe_idx->values->ptr, nullptr);
     else k::filter_rowids(fp, probe_idx->values->as<uint32_t>());
     k::filter_apply(fp, 4, head->values->ptr, nullptr, build_idx->values->ptr, nullptr);
@@ -432,7 +358,7 @@ static void join_pairs_impl(int how, const ColumnPtr& probe_key, const ColumnPtr
     k::exclusive_scan_u32(cnt->as<uint32_t>(), off->as<uint64_t>(), n);
     d2h_sync(&total, off->as<uint64_t>() + n, 8);
     PLX_REQUIRE(total < 0xffffffffull, PLX_ERR_UNSUPPORTED, "join output exceeds u32 IdxSize");
-    probe_idx = mk_idx((int64_t)total); build_idx = mk_idx((int64_t)total);
+    probe_idx = make_idx_column((int64_t)total, 1); build_idx = make_idx_column((int64_t)total, 1);
     if (total) {
       ProfileScope ps("join_pairs_emit", (uint64_t)n * 24 + total * 8, (uint64_t)n);
       hipLaunchKernelGGL(join_pairs_emit_kernel, dim3(k::grid_for(n, kBlock * 2)), dim3(kBlock), 0, stream(), cp, n, t.links, head->values->as<uint32_t>(), off->as<uint64_t>(),
@@ -505,8 +431,7 @@ void hash_partition_dev(const ColumnPtr& key, int n_partitions, uint64_t seed, C
   uint64_t s = fold(seed ^ 0x85921e81c41226a0ull, 0x3bc1d0faba166294ull);
   s = fold(s, 0xfbde893e21a73756ull) | 1;
   const int64_t n = key->len;
-  perm = std::make_shared<Column>();
-  perm->dtype = PLX_U32; perm->len = n; perm->values = dev_alloc(values_bytes(PLX_U32, n)); perm->null_count = 0;
+  perm = make_idx_column(n);
   counts = dev_alloc_zero(sizeof(uint64_t) * (size_t)n_partitions);
   if (n) {
     ProfileScope ps("hash_partition", (uint64_t)n * (dtype_width(key->dtype) * 2 + 4), (uint64_t)n);
