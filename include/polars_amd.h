@@ -29,6 +29,8 @@
  *       crates/polars-compute/src/arithmetic/mod.rs:8-150 (ArithmeticKernel)
  *   plx_cast
  *       crates/polars-expr/src/expressions/cast.rs (numeric casts only)
+ *   plx_if_then_else
+ *       crates/polars-expr/src/expressions/ternary.rs (TernaryExpr), crates/polars-core/src/chunked_array/ops/zip.rs (zip_with)
  *   plx_filter
  *       crates/polars-compute/src/filter/mod.rs:18-28 (filter)
  *   plx_gather
@@ -260,6 +262,10 @@ int plx_bitmap_binop(plx_bitmap_op op, plx_column lhs, plx_column rhs, plx_colum
 int plx_bitmap_not(plx_column col, plx_column* out);
 /* Same-dtype operands (type coercion happens in the optimizer). */
 int plx_arith(plx_arith_op op, plx_column lhs, plx_column rhs, plx_column* out);
+/* Row-wise select (the reference's zip_with): out[i] = mask[i] is valid and true ? if_true[i] : if_false[i], value and validity of the chosen side; a null mask row
+ * selects if_false.  mask is Boolean, if_true / if_false have one dtype (any fixed-width dtype or Boolean); a length-1 operand broadcasts.  The result carries a
+ * validity bitmap only when a side can be null. */
+int plx_if_then_else(plx_column mask, plx_column if_true, plx_column if_false, plx_column* out);
 /* scalar_on_left: computes scalar OP col instead of col OP scalar. */
 int plx_arith_scalar(plx_arith_op op, plx_column col, plx_scalar scalar, int scalar_on_left, plx_column* out);
 /* numeric -> numeric cast (non-strict: out-of-range -> null like polars cast(strict=False)). */
@@ -334,7 +340,9 @@ typedef enum plx_aexpr_kind {
   PLX_AE_NOT = 7,     /* lhs (boolean) */
   PLX_AE_IS_NULL = 8,     /* lhs -> Boolean, never null (FunctionExpr::Boolean(IsNull)) */
   PLX_AE_IS_NOT_NULL = 9, /* lhs -> Boolean, never null */
-  PLX_AE_FILL_NULL = 10   /* lhs, rhs = non-null literal of the same dtype (fill_null(literal)); inside fused pipelines only */
+  PLX_AE_FILL_NULL = 10,  /* lhs, rhs = non-null literal of the same dtype (fill_null(literal)); inside fused pipelines only */
+  PLX_AE_TERNARY = 11     /* when(cond).then(lhs).otherwise(rhs): cond Boolean, lhs / rhs of one dtype (type coercion casts upstream).  A row takes lhs where cond is
+                           * valid and true and rhs everywhere else (a null cond selects rhs); value and validity are those of the chosen side.  Output name: that of lhs */
 } plx_aexpr_kind;
 
 /* polars_plan::dsl::Operator subset */
@@ -353,6 +361,7 @@ typedef struct plx_aexpr {
   int32_t is_null; /* literal is NULL */
   plx_scalar lit;
   const char* name; /* column name / alias */
+  int32_t cond;     /* PLX_AE_TERNARY: arena index of the predicate; read for that kind only (appended last: arenas of earlier callers never carry the kind) */
 } plx_aexpr;
 
 typedef enum plx_ir_kind {
@@ -660,7 +669,7 @@ int plx_profile_clear(void);
  *   _polars_plugin_field_<name>(fields, n, out, kwargs, kwargs_len)   output field (minor 1 signature, plugin.rs:186-207)
  * Functions: plx_cmp / plx_arith (kwargs {"op": "gt" | ... | "add" | ...}) and one symbol per operator for callers
  * without kwargs: plx_eq ne lt le gt ge, plx_add sub mul truediv floordiv mod, plx_filter(values, mask),
- * plx_sum mean min max (length-1 result).  Python side: polars.plugins.register_plugin_function(
+ * plx_when_then_otherwise(mask, then, otherwise), plx_sum mean min max (length-1 result).  Python side: polars.plugins.register_plugin_function(
  *     plugin_path=".../libpolars_amd.so", function_name="plx_gt", args=[pl.col("a"), pl.lit(3)]).           */
 typedef struct plx_caller_context { uint64_t bitflags; } plx_caller_context;
 uint32_t _polars_plugin_get_version(void);
@@ -674,6 +683,7 @@ PLX_DECLARE_PLUGIN(plx_cmp) PLX_DECLARE_PLUGIN(plx_arith) PLX_DECLARE_PLUGIN(plx
 PLX_DECLARE_PLUGIN(plx_eq) PLX_DECLARE_PLUGIN(plx_ne) PLX_DECLARE_PLUGIN(plx_lt) PLX_DECLARE_PLUGIN(plx_le) PLX_DECLARE_PLUGIN(plx_gt) PLX_DECLARE_PLUGIN(plx_ge)
 PLX_DECLARE_PLUGIN(plx_add) PLX_DECLARE_PLUGIN(plx_sub) PLX_DECLARE_PLUGIN(plx_mul) PLX_DECLARE_PLUGIN(plx_truediv) PLX_DECLARE_PLUGIN(plx_floordiv) PLX_DECLARE_PLUGIN(plx_mod)
 PLX_DECLARE_PLUGIN(plx_sum) PLX_DECLARE_PLUGIN(plx_mean) PLX_DECLARE_PLUGIN(plx_min) PLX_DECLARE_PLUGIN(plx_max)
+PLX_DECLARE_PLUGIN(plx_when_then_otherwise)   /* (mask, then, otherwise): plx_if_then_else; the field is the `then` input's */
 
 #ifdef __cplusplus
 }

@@ -28,7 +28,7 @@ AGG_SUM, AGG_MEAN, AGG_MIN, AGG_MAX, AGG_COUNT, AGG_LEN, AGG_FIRST = range(7)
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI, JOIN_FULL, JOIN_RIGHT = range(6)
 JOIN_COALESCE_DEFAULT, JOIN_COALESCE, JOIN_KEEP_BOTH = range(3)          # plx_ir.coalesce
 JOIN_ORDER_NONE, JOIN_ORDER_LEFT, JOIN_ORDER_RIGHT, JOIN_ORDER_LEFT_RIGHT, JOIN_ORDER_RIGHT_LEFT = range(5)   # plx_join_order
-AE_COLUMN, AE_LITERAL, AE_BINARY, AE_CAST, AE_AGG, AE_LEN, AE_ALIAS, AE_NOT, AE_IS_NULL, AE_IS_NOT_NULL, AE_FILL_NULL = range(11)
+AE_COLUMN, AE_LITERAL, AE_BINARY, AE_CAST, AE_AGG, AE_LEN, AE_ALIAS, AE_NOT, AE_IS_NULL, AE_IS_NOT_NULL, AE_FILL_NULL, AE_TERNARY = range(12)
 (OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_PLUS, OP_MINUS, OP_MULTIPLY, OP_TRUE_DIVIDE,
  OP_FLOOR_DIVIDE, OP_MODULUS, OP_AND, OP_OR, OP_XOR) = range(15)
 IR_SCAN, IR_FILTER, IR_SELECT, IR_HSTACK, IR_GROUPBY, IR_JOIN, IR_SORT, IR_SLICE = range(8)
@@ -71,7 +71,7 @@ class SeriesExport(C.Structure):
 
 class AExpr(C.Structure):
     _fields_ = [("kind", C.c_int32), ("op", C.c_int32), ("lhs", C.c_int32), ("rhs", C.c_int32), ("dtype", C.c_int32),
-                ("is_null", C.c_int32), ("lit", Scalar), ("name", C.c_char_p)]
+                ("is_null", C.c_int32), ("lit", Scalar), ("name", C.c_char_p), ("cond", C.c_int32)]
 
 
 class IR(C.Structure):
@@ -176,6 +176,7 @@ SIGNATURES = {
     "plx_arith": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _u64p]),
     "plx_arith_scalar": (C.c_int, [C.c_int, C.c_uint64, Scalar, C.c_int, _u64p]),
     "plx_cast": (C.c_int, [C.c_uint64, C.c_int, _u64p]),
+    "plx_if_then_else": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, _u64p]),
     "plx_filter": (C.c_int, [C.c_uint64, C.c_uint64, _u64p]),
     "plx_gather": (C.c_int, [C.c_uint64, C.c_uint64, _u64p]),
     "plx_reduce": (C.c_int, [C.c_int, C.c_uint64, C.POINTER(Scalar), _i32p, _i32p]),

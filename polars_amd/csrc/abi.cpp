@@ -284,6 +284,7 @@ int plx_arith(plx_arith_op op, plx_column lhs, plx_column rhs, plx_column* out) 
 int plx_arith_scalar(plx_arith_op op, plx_column col, plx_scalar scalar, int scalar_on_left, plx_column* out) {
   PLX_TRY *out = register_column(ops::arith_scalar(op, get_column(col), scalar, scalar_on_left != 0)); PLX_CATCH
 }
+int plx_if_then_else(plx_column mask, plx_column if_true, plx_column if_false, plx_column* out) { PLX_TRY *out = register_column(ops::if_then_else(get_column(mask), get_column(if_true), get_column(if_false))); PLX_CATCH }
 int plx_cast(plx_column col, plx_dtype to, plx_column* out) { PLX_TRY *out = register_column(ops::cast(get_column(col), to)); PLX_CATCH }
 int plx_filter(plx_column col, plx_column mask, plx_column* out) { PLX_TRY *out = register_column(ops::filter(get_column(col), get_column(mask))); PLX_CATCH }
 int plx_gather(plx_column col, plx_column idx, plx_column* out) { PLX_TRY *out = register_column(ops::gather(get_column(col), get_column(idx))); PLX_CATCH }
@@ -672,6 +673,23 @@ void _polars_plugin_plx_filter(PLX_PLUGIN_SIG) {
     if (in[1].is_scalar) { plx_scalar v = in[1].scalar; mask = ops::full_column(PLX_BOOL, v, in[1].scalar_valid, in[0].col->len); }
     return ops::filter(in[0].col, mask);
   });
+}
+// when(mask).then(a).otherwise(b): inputs (mask, then, otherwise); the output field is the `then` input's, as the reference names a ternary
+void _polars_plugin_plx_when_then_otherwise(PLX_PLUGIN_SIG) {
+  (void)kwargs; (void)kwargs_len;
+  plugin_call(inputs, n_inputs, out, ctx, 3, [&](std::vector<PluginInput>& in) {
+    PLX_REQUIRE(in[0].dtype == PLX_BOOL, PLX_ERR_INVALID, "plx_when_then_otherwise: the mask must be Boolean");
+    PLX_REQUIRE(in[1].dtype == in[2].dtype, PLX_ERR_INVALID, "plx_when_then_otherwise: branches differ in dtype (type coercion happens in the optimizer)");
+    ColumnPtr c[3];
+    for (int i = 0; i < 3; i++) c[i] = in[i].is_scalar ? ops::full_column(in[i].dtype, in[i].scalar, in[i].scalar_valid, 1) : in[i].col;
+    ColumnPtr res = ops::if_then_else(c[0], c[1], c[2]);
+    in[0].name = in[1].name;      // plugin_call exports under the first input's name
+    return res;
+  });
+}
+void _polars_plugin_field_plx_when_then_otherwise(PLX_FIELD_SIG) {
+  (void)kwargs; (void)kwargs_len;
+  if (fields && n_fields == 3) plugin_field(fields + 1, 2, out, FIELD_SAME, 0); else plugin_field(nullptr, 0, out, FIELD_SAME, 0);
 }
 void _polars_plugin_field_plx_filter(PLX_FIELD_SIG) { (void)kwargs; (void)kwargs_len; plugin_field(fields, n_fields, out, FIELD_SAME, 0); }
 

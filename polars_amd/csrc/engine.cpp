@@ -38,7 +38,11 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
     AE e;
     e.kind = ae[i].kind; e.op = ae[i].op; e.lhs = ae[i].lhs; e.rhs = ae[i].rhs; e.dtype = ae[i].dtype; e.is_null = ae[i].is_null; e.lit = ae[i].lit;
     if (ae[i].name) e.name = ae[i].name;
-    PLX_REQUIRE(e.lhs < i && e.rhs < i, PLX_ERR_INVALID, "AExpr arena must be topologically ordered (children before parents)");
+    if (e.kind == PLX_AE_TERNARY) {
+      e.cond = ae[i].cond;
+      PLX_REQUIRE(e.cond >= 0 && e.lhs >= 0 && e.rhs >= 0, PLX_ERR_INVALID, "ternary expression needs a predicate (cond), a then (lhs) and an otherwise (rhs) input");
+    }
+    PLX_REQUIRE(e.lhs < i && e.rhs < i && e.cond < i, PLX_ERR_INVALID, "AExpr arena must be topologically ordered (children before parents)");
     p.ae.push_back(std::move(e));
   }
   for (int i = 0; i < n_ir; i++) {
@@ -103,6 +107,12 @@ int infer_dtype(const Plan& plan, int e, const Frame& schema) {
     case PLX_AE_CAST: return x.dtype;
     case PLX_AE_NOT: case PLX_AE_IS_NULL: case PLX_AE_IS_NOT_NULL: return PLX_BOOL;
     case PLX_AE_FILL_NULL: return infer_dtype(plan, x.lhs, schema);
+    case PLX_AE_TERNARY: {
+      const int l = infer_dtype(plan, x.lhs, schema), r = infer_dtype(plan, x.rhs, schema);
+      PLX_REQUIRE(infer_dtype(plan, x.cond, schema) == PLX_BOOL, PLX_ERR_INVALID, "when/then/otherwise: the predicate must be Boolean");
+      PLX_REQUIRE(l == r, PLX_ERR_INVALID, std::string("when/then/otherwise branches have different dtypes (") + dtype_name(l) + ", " + dtype_name(r) + "); the optimizer's type coercion must insert casts");
+      return l;
+    }
     case PLX_AE_LEN: return PLX_U32;
     case PLX_AE_AGG: {
       int in = infer_dtype(plan, x.lhs, schema);
@@ -139,14 +149,14 @@ static bool contains_agg(const Plan& plan, int e) {
   if (e < 0) return false;
   const AE& x = plan.ae[e];
   if (x.kind == PLX_AE_AGG || x.kind == PLX_AE_LEN) return true;
-  return contains_agg(plan, x.lhs) || contains_agg(plan, x.rhs);
+  return contains_agg(plan, x.lhs) || contains_agg(plan, x.rhs) || contains_agg(plan, x.cond);
 }
 static bool contains_column_outside_agg(const Plan& plan, int e) {
   if (e < 0) return false;
   const AE& x = plan.ae[e];
   if (x.kind == PLX_AE_AGG || x.kind == PLX_AE_LEN) return false;
   if (x.kind == PLX_AE_COLUMN) return true;
-  return contains_column_outside_agg(plan, x.lhs) || contains_column_outside_agg(plan, x.rhs);
+  return contains_column_outside_agg(plan, x.lhs) || contains_column_outside_agg(plan, x.rhs) || contains_column_outside_agg(plan, x.cond);
 }
 static void collect_aggs(const Plan& plan, int e, std::vector<int>& out) {
   if (e < 0) return;
@@ -154,6 +164,7 @@ static void collect_aggs(const Plan& plan, int e, std::vector<int>& out) {
   if (x.kind == PLX_AE_AGG || x.kind == PLX_AE_LEN) { if (std::find(out.begin(), out.end(), e) == out.end()) out.push_back(e); return; }
   collect_aggs(plan, x.lhs, out);
   collect_aggs(plan, x.rhs, out);
+  collect_aggs(plan, x.cond, out);
 }
 
 // -------------------------------------------------- materialising evaluator ----
@@ -161,15 +172,7 @@ static void collect_aggs(const Plan& plan, int e, std::vector<int>& out) {
 // `overrides` maps expression ids to precomputed columns (aggregation results).
 struct Evaluated { ColumnPtr col; bool scalar; };  // scalar: length-1, broadcastable
 
-static plx_scalar scalar_of(const ColumnPtr& c, bool* valid) {
-  plx_scalar s; s.u = 0;
-  uint8_t v = 0xff; int32_t hv = 0;
-  uint64_t buf[2] = {0, 0};
-  column_to_host(c, buf, &v, &hv);
-  *valid = v & 1;
-  if (c->dtype == PLX_BOOL) s.u = buf[0] & 1; else memcpy(&s, buf, (size_t)dtype_width(c->dtype));
-  return s;
-}
+using ops::scalar_of;
 
 static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<int, ColumnPtr>* overrides) {
   check_cancel();
@@ -204,6 +207,13 @@ static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<i
       PLX_REQUIRE(l.kind == PLX_AE_LITERAL && !l.is_null, PLX_ERR_UNSUPPORTED, "fill_null with a non-literal value");
       PLX_REQUIRE(l.dtype == c.col->dtype, PLX_ERR_INVALID, std::string("fill_null literal dtype ") + dtype_name(l.dtype) + " differs from the column's " + dtype_name(c.col->dtype));
       return {ops::fill_null(c.col, l.lit), c.scalar};
+    }
+    case PLX_AE_TERNARY: {
+      // a length-1 operand broadcasts inside the kernel (select_kernel's scalar forms); all three scalar: a scalar
+      Evaluated p = eval(plan, x.cond, df, overrides), a = eval(plan, x.lhs, df, overrides), b = eval(plan, x.rhs, df, overrides);
+      PLX_REQUIRE(p.col->dtype == PLX_BOOL, PLX_ERR_INVALID, "when/then/otherwise: the predicate must be Boolean");
+      PLX_REQUIRE(a.col->dtype == b.col->dtype, PLX_ERR_INVALID, std::string("when/then/otherwise branches have different dtypes (") + dtype_name(a.col->dtype) + ", " + dtype_name(b.col->dtype) + ")");
+      return {ops::if_then_else(p.col, a.col, b.col), p.scalar && a.scalar && b.scalar};
     }
     case PLX_AE_LEN: { ops::ScalarValue s; s.dtype = PLX_U32; s.valid = true; s.v.u = (uint32_t)df.height; return {ops::scalar_column(s), true}; }
     case PLX_AE_AGG: {
@@ -260,6 +270,7 @@ static ColumnPtr broadcast(const Evaluated& ev, int64_t height) {
 struct DNode {
   uint8_t code = OP_NOP, c = 0;
   int a = -1, b = -1;
+  int p = -1;       // third source node (OP_SELECT: the predicate; its slot becomes Op::c)
   uint64_t imm = 0;
   int col = -1;     // frame column index for OP_LOAD
   char ty = 'i';    // 'i' signed, 'u' unsigned 64, 'f' f64, 'b' bool
@@ -283,7 +294,7 @@ class Compiler {
 
   int add(DNode n) {
     std::ostringstream k;
-    k << (int)n.code << ':' << n.a << ':' << n.b << ':' << (int)n.c << ':' << n.imm << ':' << n.col << ':' << n.ty;
+    k << (int)n.code << ':' << n.a << ':' << n.b << ':' << n.p << ':' << (int)n.c << ':' << n.imm << ':' << n.col << ':' << n.ty;
     auto it = memo.find(k.str());
     if (it != memo.end()) return it->second;
     nodes.push_back(n);
@@ -301,6 +312,8 @@ class Compiler {
   // membership of integer node `a` in lookup bitmap `lut` (args.lut[lut] is filled in by the caller before the launch)
   // node `a` with its validity cut down to the rows where boolean node `m` is valid and true (OP_MASKV)
   int mask_valid(int a, int m) { DNode n; n.code = OP_MASKV; n.a = a; n.b = m; n.ty = nodes[a].ty; n.nullable = true; return add(n); }
+  // when(p).then(a).otherwise(b) (OP_SELECT): the chosen side's value and validity
+  int select(int p, int a, int b, char ty) { DNode n; n.code = OP_SELECT; n.a = a; n.b = b; n.p = p; n.ty = ty; n.nullable = nodes[a].nullable || nodes[b].nullable; return add(n); }
   int bit_lookup(int a, int lut, int64_t kmin) { DNode n; n.code = OP_BITLOOKUP; n.a = a; n.b = a; n.c = (uint8_t)lut; n.imm = (uint64_t)kmin; n.ty = 'b'; n.nullable = nodes[a].nullable; return add(n); }
   int col_id(const ColumnPtr& c) {
     for (size_t i = 0; i < cols.size(); i++) if (cols[i].get() == c.get()) return (int)i;
@@ -377,6 +390,23 @@ class Compiler {
         if (dt == PLX_F32) throw Unsupported("f32 fill_null");
         int a = lower(x.lhs);
         return nodes[a].nullable ? ifnull(a, widen_literal(l.dtype, l.lit)) : a;
+      }
+      case PLX_AE_TERNARY: {
+        const int dt = infer_dtype(plan, e, *df);      // (fails when the branches differ in dtype or the predicate is not Boolean)
+        if (dt == PLX_F32) throw Unsupported("f32 when/then/otherwise");
+        const int p = lower(x.cond);
+        if (nodes[p].ty != 'b') throw Unsupported("when/then/otherwise predicate is not boolean");
+        if (nodes[p].code == OP_CONST) return lower((nodes[p].imm & 1) ? x.lhs : x.rhs);      // a constant predicate: the chosen branch
+        auto null_literal = [&](int b) { const AE* y = &plan.ae.at(b); while (y->kind == PLX_AE_ALIAS) y = &plan.ae.at(y->lhs); return y->kind == PLX_AE_LITERAL && y->is_null; };
+        const bool a_null = null_literal(x.lhs), b_null = null_literal(x.rhs);
+        if (a_null && b_null) throw Unsupported("when/then/otherwise of two null literals");
+        // a null-literal branch needs no constant: the other branch with its validity cut down to the rows that choose it (OP_MASKV)
+        if (b_null) return mask_valid(lower(x.lhs), p);
+        if (a_null) { const int t = nodes[p].nullable ? ifnull(p, 0) : p; return mask_valid(lower(x.rhs), mk(OP_NOT, t, t, 'b')); }
+        const int a = lower(x.lhs), b = lower(x.rhs);
+        if (a == b) return a;
+        // both branches hold the dtype's 64-bit widening already (a cast that only widens leaves its operand's tag on the node: the tag follows the dtype here)
+        return select(p, a, b, dt == PLX_F64 ? 'f' : dt == PLX_U64 ? 'u' : dt == PLX_BOOL ? 'b' : 'i');
       }
       case PLX_AE_CAST: {
         int from = infer_dtype(plan, x.lhs, *df), to = x.dtype;
@@ -494,8 +524,11 @@ class Compiler {
     if (nodes[n].code != OP_LOAD && nodes[n].code != OP_CONST) {
       count_uses(nodes[n].a, seen);
       if (nodes[n].b != nodes[n].a) count_uses(nodes[n].b, seen);
+      if (third_source(nodes[n])) count_uses(nodes[n].p, seen);
     }
   }
+  // the predicate of an OP_SELECT, when it is a node of its own (one use per DISTINCT source, as for a == b)
+  static bool third_source(const DNode& d) { return d.p >= 0 && d.p != d.a && d.p != d.b; }
   void release(int n) {
     if (n < 0) return;
     if (--nodes[n].uses == 0) slot_busy[nodes[n].slot] = false;
@@ -504,12 +537,14 @@ class Compiler {
     DNode& d = nodes[n];
     if (d.emitted) return d.slot;
     const bool leaf = d.code == OP_LOAD || d.code == OP_CONST;
-    int sa = -1, sb = -1;
+    int sa = -1, sb = -1, sp = -1;
     if (!leaf) {
       sa = emit(d.a);
       sb = (d.b == d.a) ? sa : emit(d.b);
+      if (d.p >= 0) sp = emit(d.p);      // (an emitted node returns its slot)
       release(d.a);
       if (d.b != d.a) release(d.b);
+      if (third_source(d)) release(d.p);
     }
     int slot = -1;
     for (int s = 0; s < kSlots; s++) if (!slot_busy[s]) { slot = s; break; }
@@ -533,6 +568,7 @@ class Compiler {
       args.imm[pc] = d.imm;
     } else {
       op.a = (uint8_t)sa; op.b = (uint8_t)sb;
+      if (d.p >= 0) op.c = (uint8_t)sp;
       if (d.code == OP_IFNULL || d.code == OP_BITLOOKUP) args.imm[pc] = d.imm;
     }
     shape.ops[pc] = op;
@@ -560,6 +596,7 @@ class Compiler {
         if (nodes[n].code == OP_CONST) return;
         dfs(nodes[n].a);
         if (nodes[n].b != nodes[n].a) dfs(nodes[n].b);
+        dfs(nodes[n].p);
       };
       for (int r : roots) dfs(r);
       for (int n : order) emit(n);
@@ -1482,6 +1519,7 @@ static void collect_columns(const Plan& plan, int e, std::set<std::string>& out)
   if (x.kind == PLX_AE_COLUMN) { out.insert(x.name); return; }
   collect_columns(plan, x.lhs, out);
   collect_columns(plan, x.rhs, out);
+  collect_columns(plan, x.cond, out);
 }
 // Resolves one input of the outer join to a scan node: [Filter]* Scan, or [Filter]* Join(inner; A, B) with A, B = [Filter]* Scan
 // where one of A / B is a pure filter with respect to `used` (the column names referenced above).  Appends the payload side's
@@ -1829,7 +1867,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
     if (e < 0) return true;
     const AE& x = plan.ae[e];
     if (x.kind == PLX_AE_COLUMN) return pview.find(x.name) >= 0;
-    return probe_only(x.lhs) && probe_only(x.rhs);
+    return probe_only(x.lhs) && probe_only(x.rhs) && probe_only(x.cond);
   };
   for (int e : gb.exprs) {
     if (!contains_agg(plan, e) || contains_column_outside_agg(plan, e)) return no("aggregation list contains a non-aggregated column");

@@ -23,6 +23,7 @@ namespace engine {
 
 struct AE {
   int kind = 0, op = 0, lhs = -1, rhs = -1, dtype = 0, is_null = 0;
+  int cond = -1;   // PLX_AE_TERNARY: the predicate (lhs = then, rhs = otherwise)
   plx_scalar lit{};
   std::string name;
 };

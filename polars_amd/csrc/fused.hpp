@@ -57,7 +57,10 @@ enum OpCode : uint8_t {
   // dst <- a, valid only in rows where b is valid and true.  In front of a bitmap lookup it takes the rows an earlier, cheaper conjunct of the predicate already
   // rejected out of the lookup: an invalid lane issues no load (a random lookup moves a whole line from the L2 to the CU: TPC-H Q3's orders scan with the customer
   // filter was bound by those lines, not by HBM)
-  OP_MASKV
+  OP_MASKV,
+  // dst <- rows where c is valid and true take a, every other row takes b (a null predicate selects b); value AND validity are the chosen side's, the predicate's own
+  // validity never reaches dst.  when(c).then(a).otherwise(b): the only op with three source slots (op_src_slots)
+  OP_SELECT
 };
 
 struct Op {
@@ -96,7 +99,7 @@ struct Shape {
 struct ProgramSplit { uint32_t early; bool any_late; };
 PLX_HD constexpr uint32_t op_src_slots(const Op& op) {
   if (op.code == OP_LOAD || op.code == OP_CONST || op.code == OP_NOP) return 0;
-  return (1u << op.a) | (1u << op.b);
+  return (1u << op.a) | (1u << op.b) | (op.code == OP_SELECT ? (1u << op.c) : 0u);
 }
 PLX_HD constexpr ProgramSplit split_program(const Shape& s) {
   const uint32_t all = s.n_ops >= 32 ? ~0u : ((1u << s.n_ops) - 1u);
@@ -228,7 +231,20 @@ struct RecLayout {
 PLX_FHD constexpr bool shape_may_have_nulls(const Shape& sh) {
   for (int i = 0; i < sh.n_inputs; i++) if (sh.in_nullable[i]) return true;
   for (int i = 0; i < sh.n_ops; i++) if (sh.ops[i].code >= OP_FDIV_I && sh.ops[i].code <= OP_MOD_U) return true;   // integer div / mod: divisor 0 -> null
-  return false;
+  // OP_MASKV makes nulls out of inputs that have none (when(p).then(a) without an otherwise): they count when they reach a key or an aggregate source
+  // (inside a predicate they end in OP_IFNULL, and the predicate slot is no part of a record)
+  uint32_t masked = 0;
+  for (int i = 0; i < sh.n_ops; i++) {
+    const Op op = sh.ops[i];
+    if (op.code == OP_NOP) continue;
+    const bool m = op.code == OP_MASKV || (op.code != OP_IFNULL && (op_src_slots(op) & masked));
+    masked = m ? (masked | (1u << op.dst)) : (masked & ~(1u << op.dst));
+  }
+  uint32_t sinks = 0;
+  if (sh.key != kNone) sinks |= 1u << sh.key;
+  for (int i = 0; i < sh.n_keys; i++) sinks |= 1u << sh.keys[i];
+  for (int k = 0; k < sh.n_aggs; k++) if (sh.aggs[k].kind != AGG_LEN && sh.aggs[k].kind != AGG_FIRST_ROW) sinks |= 1u << sh.aggs[k].src;
+  return (masked & sinks) != 0;
 }
 PLX_FHD constexpr RecLayout rec_layout(const Shape& sh) {
   RecLayout L{};

@@ -321,6 +321,17 @@ __device__ __forceinline__ void exec_op(const Op op, const Shape& sh, const Args
         for (int r = 0; r < kRows; r++) { d[r] = a[r]; tb |= (uint32_t)(b[r] & 1) << r; }
         vd = va & vb & tb;
       } break;
+      case OP_SELECT: {   // the third source is read here: a and b are the only slots fetched in front of the switch
+        const uint32_t vc = rf.getv(op.c);
+        uint32_t t = 0;
+#pragma unroll
+        for (int r = 0; r < kRows; r++) {
+          const bool take = (rf.get(r, op.c) & 1) && ((vc >> r) & 1);
+          d[r] = take ? a[r] : b[r];
+          t |= (uint32_t)take << r;
+        }
+        vd = (t & va) | (~t & vb);
+      } break;
       default:  // OP_MOV / OP_NOP
 #pragma unroll
         for (int r = 0; r < kRows; r++) d[r] = a[r];

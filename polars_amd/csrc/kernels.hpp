@@ -33,6 +33,10 @@ void bitmap_blit(uint64_t* dst, int64_t dst_off, const uint64_t* src, int64_t n_
 // out[i] = pattern (width 1/2/4/8 bytes)
 void fill(int width, void* out, uint64_t pattern, int64_t n);
 void fill_null(int width /* 0: bitmap */, const void* in, const uint64_t* validity, uint64_t pattern, int64_t n, void* out);
+// out[i] = (mask[i] & mask_valid[i]) ? a[i] : b[i], values and validity (out_valid may be null: neither side can be null).  A side whose values pointer is null is the
+// scalar given next to it (scalar_valid false: a null scalar).  width 0: Boolean sides (bitmaps); float sides travel as their bits.
+void select(int width /* 0: bitmap */, const uint64_t* mask, const uint64_t* mask_valid, const void* a, const uint64_t* a_valid, plx_scalar a_scalar, bool a_scalar_valid,
+            const void* b, const uint64_t* b_valid, plx_scalar b_scalar, bool b_scalar_valid, int64_t n, void* out, uint64_t* out_valid);
 void fill_iota_u32(uint32_t* out, int64_t n);
 // result download of small frames: up to kPackMax device buffers are copied into one staging buffer by ONE launch
 constexpr int kPackMax = 32;

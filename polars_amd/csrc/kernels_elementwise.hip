@@ -400,6 +400,99 @@ void fill_null(int width, const void* in, const uint64_t* validity, uint64_t pat
   PLX_HIP(hipGetLastError());
 }
 
+// ------------------------------------------------------------------- select ---
+// when(mask).then(a).otherwise(b) per node (the reference's zip_with; fused programs use OP_SELECT): a row takes a where the mask is valid and true and b
+// everywhere else, value and validity.  Shaped like cmp_kernel: one wave covers the 64 rows of a validity word, 4 words in flight.  Every lane holds the
+// effective mask word m = mask values & mask validity (the word index is wave-uniform: one load), selects its own row, and one lane writes the output
+// validity word (m & va) | (~m & vb).  A scalar side has its value in `s` and its validity as a whole word (all ones, or 0 for a null scalar: no load).
+struct SelectSide {
+  const void* values;          // null: a scalar
+  const uint64_t* validity;    // may be null
+  uint64_t scalar;             // the scalar's bits
+  uint64_t scalar_valid;       // ~0 or 0
+};
+template <class W, bool A_SCALAR, bool B_SCALAR>
+__global__ __launch_bounds__(kBlock) void select_kernel(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ mask_valid, SelectSide sa, SelectSide sb,
+                                                        int64_t n, W* __restrict__ out, uint64_t* __restrict__ out_valid) {
+  const int lane = lane_id();
+  const W* __restrict__ a = reinterpret_cast<const W*>(sa.values);
+  const W* __restrict__ b = reinterpret_cast<const W*>(sb.values);
+  const W as = (W)sa.scalar, bs = (W)sb.scalar;
+  const int64_t nwords = (n + 63) >> 6;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  auto side_valid = [](const SelectSide& s, bool scalar, int64_t w) -> uint64_t { return scalar ? s.scalar_valid : (s.validity ? s.validity[w] : ~0ull); };
+  for (int64_t w = wave * 4; w < nwords; w += nwaves * 4) {
+    if ((w + 4) * 64 <= n) {
+      uint64_t m[4];
+      W x[4], y[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        m[u] = mask[w + u] & (mask_valid ? mask_valid[w + u] : ~0ull);
+        x[u] = A_SCALAR ? as : a[(w + u) * 64 + lane];
+        y[u] = B_SCALAR ? bs : b[(w + u) * 64 + lane];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        out[(w + u) * 64 + lane] = ((m[u] >> lane) & 1) ? x[u] : y[u];
+        if (out_valid && lane == u) out_valid[w + u] = (m[u] & side_valid(sa, A_SCALAR, w + u)) | (~m[u] & side_valid(sb, B_SCALAR, w + u));
+      }
+    } else {
+      for (int u = 0; u < 4 && w + u < nwords; u++) {
+        const int64_t i = (w + u) * 64 + lane;
+        const uint64_t m = mask[w + u] & (mask_valid ? mask_valid[w + u] : ~0ull);
+        if (i < n) { const W x = A_SCALAR ? as : a[i]; const W y = B_SCALAR ? bs : b[i]; out[i] = ((m >> lane) & 1) ? x : y; }
+        if (out_valid && lane == 0) {
+          uint64_t v = (m & side_valid(sa, A_SCALAR, w + u)) | (~m & side_valid(sb, B_SCALAR, w + u));
+          if (w + u == nwords - 1 && (n & 63)) v &= (~0ull) >> (64 - (n & 63));
+          out_valid[w + u] = v;
+        }
+      }
+    }
+  }
+}
+// Boolean sides: values are bitmaps as well, so the select is word-wise like fill_null_bool_kernel: out = (m & a) | (~m & b)
+__global__ __launch_bounds__(kBlock) void select_bool_kernel(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ mask_valid, SelectSide sa, SelectSide sb,
+                                                             int64_t n, uint64_t* __restrict__ out, uint64_t* __restrict__ out_valid) {
+  const int64_t nwords = (n + 63) >> 6;
+  const uint64_t* __restrict__ a = reinterpret_cast<const uint64_t*>(sa.values);
+  const uint64_t* __restrict__ b = reinterpret_cast<const uint64_t*>(sb.values);
+  for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nwords; w += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t m = mask[w] & (mask_valid ? mask_valid[w] : ~0ull);
+    const uint64_t tail = (w == nwords - 1 && (n & 63)) ? (~0ull) >> (64 - (n & 63)) : ~0ull;
+    const uint64_t x = a ? a[w] : ((sa.scalar & 1) ? ~0ull : 0ull), y = b ? b[w] : ((sb.scalar & 1) ? ~0ull : 0ull);
+    out[w] = ((m & x) | (~m & y)) & tail;
+    if (out_valid) {
+      const uint64_t vx = a ? (sa.validity ? sa.validity[w] : ~0ull) : sa.scalar_valid, vy = b ? (sb.validity ? sb.validity[w] : ~0ull) : sb.scalar_valid;
+      out_valid[w] = ((m & vx) | (~m & vy)) & tail;
+    }
+  }
+}
+template <class W>
+static void select_launch(const uint64_t* mask, const uint64_t* mask_valid, const SelectSide& a, const SelectSide& b, int64_t n, void* out, uint64_t* out_valid) {
+  const int grid = grid_for(n, kBlock * 4);
+#define L(AS, BS) hipLaunchKernelGGL((select_kernel<W, AS, BS>), dim3(grid), dim3(kBlock), 0, stream(), mask, mask_valid, a, b, n, (W*)out, out_valid)
+  if (a.values) { if (b.values) L(false, false); else L(false, true); }
+  else { if (b.values) L(true, false); else L(true, true); }
+#undef L
+}
+void select(int width, const uint64_t* mask, const uint64_t* mask_valid, const void* a, const uint64_t* a_valid, plx_scalar a_scalar, bool a_scalar_valid,
+            const void* b, const uint64_t* b_valid, plx_scalar b_scalar, bool b_scalar_valid, int64_t n, void* out, uint64_t* out_valid) {
+  if (n == 0) return;
+  const uint64_t w = width ? (uint64_t)width * (uint64_t)n : (uint64_t)n / 8;      // one side's / the output's values
+  ProfileScope ps("select", w * ((a ? 1 : 0) + (b ? 1 : 0) + 1) + (uint64_t)n / 8 * (1 + (mask_valid ? 1 : 0) + (a_valid ? 1 : 0) + (b_valid ? 1 : 0) + (out_valid ? 1 : 0)), (uint64_t)n);
+  const SelectSide sa{a, a ? a_valid : nullptr, a_scalar.u, a_scalar_valid ? ~0ull : 0ull}, sb{b, b ? b_valid : nullptr, b_scalar.u, b_scalar_valid ? ~0ull : 0ull};
+  switch (width) {
+    case 0: hipLaunchKernelGGL(select_bool_kernel, dim3(grid_for((n + 63) / 64, kBlock * 4)), dim3(kBlock), 0, stream(), mask, mask_valid, sa, sb, n, (uint64_t*)out, out_valid); break;
+    case 1: select_launch<uint8_t>(mask, mask_valid, sa, sb, n, out, out_valid); break;
+    case 2: select_launch<uint16_t>(mask, mask_valid, sa, sb, n, out, out_valid); break;
+    case 4: select_launch<uint32_t>(mask, mask_valid, sa, sb, n, out, out_valid); break;
+    case 8: select_launch<uint64_t>(mask, mask_valid, sa, sb, n, out, out_valid); break;
+    default: fail(PLX_ERR_INVALID, "select: bad width");
+  }
+  PLX_HIP(hipGetLastError());
+}
+
 __global__ __launch_bounds__(kBlock) void popcount_kernel(const uint64_t* __restrict__ a, int64_t n_bits, unsigned long long* __restrict__ out) {
   const int64_t nwords = (n_bits + 63) >> 6;
   uint64_t acc = 0;

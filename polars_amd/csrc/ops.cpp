@@ -352,6 +352,44 @@ ColumnPtr fill_null(const ColumnPtr& c, plx_scalar v) {
   return out;
 }
 
+plx_scalar scalar_of(const ColumnPtr& c, bool* valid) {
+  plx_scalar s; s.u = 0;
+  uint8_t v = 0xff; int32_t hv = 0;
+  uint64_t buf[2] = {0, 0};
+  column_to_host(c, buf, &v, &hv);
+  *valid = v & 1;
+  if (c->dtype == PLX_BOOL) s.u = buf[0] & 1; else memcpy(&s, buf, (size_t)dtype_width(c->dtype));
+  return s;
+}
+
+// when / then / otherwise per node (reference: TernaryExpr over ChunkZip::zip_with, polars-core/src/chunked_array/ops/zip.rs)
+ColumnPtr if_then_else(const ColumnPtr& mask, const ColumnPtr& a, const ColumnPtr& b) {
+  PLX_REQUIRE(mask->dtype == PLX_BOOL, PLX_ERR_INVALID, "if_then_else: the mask must be Boolean");
+  require_same_dtype(a, b, "if_then_else");
+  int64_t len = 1;
+  for (const ColumnPtr* c : {&mask, &a, &b}) if ((*c)->len != 1) len = (*c)->len;
+  for (const ColumnPtr* c : {&mask, &a, &b})
+    PLX_REQUIRE((*c)->len == len || (*c)->len == 1, PLX_ERR_SHAPE, "if_then_else: length mismatch " + std::to_string((*c)->len) + " vs " + std::to_string(len) + " (only a length-1 operand broadcasts)");
+  ColumnPtr m = mask;
+  if (m->len != len) { bool v; const plx_scalar s = scalar_of(m, &v); m = full_column(PLX_BOOL, s, v, len); }      // a literal predicate: rare, not worth a kernel form
+  struct Side { const void* values = nullptr; const uint64_t* validity = nullptr; plx_scalar s{}; bool s_valid = true; bool nullable = false; };
+  auto side_of = [&](const ColumnPtr& c) {
+    Side sd;
+    if (c->len != len) { sd.s = scalar_of(c, &sd.s_valid); sd.nullable = !sd.s_valid; }
+    else { sd.values = c->values ? c->values->ptr : nullptr; sd.nullable = c->validity && c->null_count != 0; sd.validity = sd.nullable ? c->valid_words() : nullptr; }
+    return sd;
+  };
+  const Side sa = side_of(a), sb = side_of(b);
+  auto out = std::make_shared<Column>();
+  out->dtype = a->dtype; out->len = len;
+  const int w = dtype_width(a->dtype);
+  out->values = w ? dev_alloc(values_bytes(a->dtype, len)) : dev_alloc_zero(bitmap_bytes(len));
+  if (sa.nullable || sb.nullable) { out->validity = dev_alloc_zero(bitmap_bytes(len)); out->null_count = -1; } else out->null_count = 0;
+  if (len) k::select(w, m->values->as<uint64_t>(), m->valid_words(), sa.values, sa.validity, sa.s, sa.s_valid, sb.values, sb.validity, sb.s, sb.s_valid, len,
+                     out->values->ptr, out->validity ? out->validity->as<uint64_t>() : nullptr);
+  return out;
+}
+
 ColumnPtr concat(const std::vector<ColumnPtr>& chunks) {
   PLX_REQUIRE(!chunks.empty(), PLX_ERR_INVALID, "concat: no chunks");
   if (chunks.size() == 1) return chunks[0];

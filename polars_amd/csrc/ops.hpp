@@ -32,6 +32,10 @@ ScalarValue reduce(int agg_op, const ColumnPtr& c);
 ColumnPtr scalar_column(const ScalarValue& s);                 // length-1 column
 ColumnPtr full_column(int dtype, plx_scalar v, bool valid, int64_t len);  // broadcast literal
 ColumnPtr fill_null(const ColumnPtr& c, plx_scalar v);                     // valid ? value : literal (same dtype)
+// when(mask).then(a).otherwise(b): a where the mask is valid and true, b elsewhere (a null mask row selects b); value and validity of the chosen side.  mask Boolean,
+// a / b of one dtype; a length-1 operand broadcasts.  The result has a validity bitmap only when a side can be null
+ColumnPtr if_then_else(const ColumnPtr& mask, const ColumnPtr& a, const ColumnPtr& b);
+plx_scalar scalar_of(const ColumnPtr& c, bool* valid);         // value and validity of row 0 (a length-1 column), read back to the host
 ColumnPtr concat(const std::vector<ColumnPtr>& chunks);
 ColumnPtr slice_copy(const ColumnPtr& c, int64_t offset, int64_t len);
 

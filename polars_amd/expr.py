@@ -14,11 +14,16 @@ from . import datatypes as T
 
 
 class Expr:
-    __slots__ = ("kind", "op", "lhs", "rhs", "name", "value", "dtype")
+    __slots__ = ("kind", "op", "lhs", "rhs", "name", "value", "dtype", "cond")
 
     def __init__(self, kind: str, op: Optional[int] = None, lhs: "Optional[Expr]" = None, rhs: "Optional[Expr]" = None,
-                 name: Optional[str] = None, value: Any = None, dtype: Optional[T.DataType] = None):
+                 name: Optional[str] = None, value: Any = None, dtype: Optional[T.DataType] = None, cond: "Optional[Expr]" = None):
         self.kind, self.op, self.lhs, self.rhs, self.name, self.value, self.dtype = kind, op, lhs, rhs, name, value, dtype
+        self.cond = cond        # kind "ternary": the predicate (lhs = then, rhs = otherwise or None)
+
+    def children(self):
+        """The expressions this one reads, for walkers: lhs, rhs and a ternary's predicate."""
+        return [c for c in (self.lhs, self.rhs, self.cond) if c is not None]
 
     # -- operators ---------------------------------------------------------------------
     def _bin(self, op: int, other: Any, swap: bool = False) -> "Expr":
@@ -105,10 +110,53 @@ class Expr:
         if self.kind == "not": return f"~{self.lhs!r}"
         if self.kind in ("is_null", "is_not_null"): return f"{self.lhs!r}.{self.kind}()"
         if self.kind == "fill_null": return f"{self.lhs!r}.fill_null({self.rhs!r})"
+        if self.kind == "ternary":
+            return f"when({self.cond!r}).then({self.lhs!r})" + (f".otherwise({self.rhs!r})" if self.rhs is not None else "")
         return self.kind
 
     def __bool__(self):
         raise TypeError("the truth value of an Expr is ambiguous; use & / | / ~")
+
+
+def _as_expr(x: Any) -> Expr:
+    return x if isinstance(x, Expr) else lit(x)
+
+
+class When:
+    """pl.when(predicate): waits for .then(value) (py-polars functions/whenthen.py)."""
+
+    def __init__(self, predicate: Expr, chain: tuple = ()):
+        self._predicate, self._chain = _as_expr(predicate), chain
+
+    def then(self, value: Any) -> "Then":
+        return Then(self._chain + ((self._predicate, _as_expr(value)),))
+
+    def __repr__(self) -> str:
+        return "".join(f"when({p!r}).then({v!r})." for p, v in self._chain) + f"when({self._predicate!r})"
+
+
+class Then(Expr):
+    """when(p).then(a): an expression of kind "ternary" whose otherwise is still open -- a null of a's dtype until .otherwise(b) closes it.
+    A chain when(p1).then(a1).when(p2).then(a2).otherwise(b) nests in the falsy branch: the first true predicate wins."""
+    __slots__ = ("_chain",)
+
+    def __init__(self, chain: tuple, otherwise: Optional[Expr] = None):
+        tail = otherwise
+        for p, v in reversed(chain[1:]):
+            tail = Expr("ternary", lhs=v, rhs=tail, cond=p)
+        Expr.__init__(self, "ternary", lhs=chain[0][1], rhs=tail, cond=chain[0][0])
+        self._chain = chain
+
+    def when(self, predicate: Any) -> When:
+        return When(predicate, self._chain)
+
+    def otherwise(self, value: Any) -> Expr:
+        closed = Then(self._chain, _as_expr(value))
+        return Expr("ternary", lhs=closed.lhs, rhs=closed.rhs, cond=closed.cond)
+
+
+def when(predicate: Any) -> When:
+    return When(predicate)
 
 
 def col(name: str) -> Expr:

@@ -750,9 +750,8 @@ def expr_columns(e: Optional[Expr], out: Optional[Set[str]] = None) -> Set[str]:
         return out
     if e.kind == "col":
         out.add(e.name)
-    for child in (e.lhs, e.rhs):
-        if isinstance(child, Expr):
-            expr_columns(child, out)
+    for child in e.children():
+        expr_columns(child, out)
     return out
 
 
@@ -806,7 +805,7 @@ def _row_preserving(exprs) -> bool:
             return True
         if e.kind in ("agg", "len"):
             return False
-        return all(walk(c) for c in (e.lhs, e.rhs) if isinstance(c, Expr))
+        return all(walk(c) for c in e.children())
     return all(walk(e) for e in exprs) and any(expr_columns(e) for e in exprs)
 
 

@@ -89,7 +89,7 @@ class Lowering:
 
     # -- expressions ---------------------------------------------------------------------
     def _push(self, **kw) -> int:
-        node = dict(kind=0, op=0, lhs=-1, rhs=-1, dtype=0, is_null=0, lit=None, name=None)
+        node = dict(kind=0, op=0, lhs=-1, rhs=-1, dtype=0, is_null=0, lit=None, name=None, cond=-1)
         node.update(kw)
         self.aexprs.append(node)
         return len(self.aexprs) - 1
@@ -192,6 +192,8 @@ class Lowering:
             return self._push(kind=F.AE_AGG, op=e.op, lhs=idx), out
         if k == "binary":
             return self._lower_binary(e, schema)
+        if k == "ternary":
+            return self._lower_ternary(e, schema)
         raise TypeError(f"unsupported expression {e!r}")
 
     def _lower_string_compare(self, e: Expr, schema: Schema):
@@ -254,20 +256,10 @@ class Lowering:
             return self._push(kind=F.AE_BINARY, op=F.OP_AND, lhs=ge(lower(L)), rhs=le(upper(L))), T.Boolean
         return self._push(kind=F.AE_BINARY, op=F.OP_OR, lhs=lt(lower(L)), rhs=gt(upper(L))), T.Boolean
 
-    def _lower_binary(self, e: Expr, schema: Schema):
-        op = e.op
-        if (e.lhs.kind == "lit" and isinstance(e.lhs.value, str)) or (e.rhs.kind == "lit" and isinstance(e.rhs.value, str)):
-            return self._lower_string_compare(e, schema)
-        li, ldt = self._lower_maybe_dyn(e.lhs, schema)
-        ri, rdt = self._lower_maybe_dyn(e.rhs, schema)
+    def _coerce_pair(self, li, ldt, ri, rdt):
+        """Type coercion of two operands that must meet in one dtype (type_coercion/binary.rs): a python literal (still a (value, tag) pair)
+        takes the other side's dtype, then both sides are cast to their supertype.  Returns (li, ldt, ri, rdt) with ldt == rdt."""
         ldyn, rdyn = isinstance(li, tuple), isinstance(ri, tuple)
-        if not ldyn and not rdyn and isinstance(ldt, T.DatetimeType) and isinstance(rdt, T.DatetimeType) and ldt.time_unit != rdt.time_unit:
-            return self._lower_mixed_time_units(op, li, ldt, ri, rdt)
-        if op in (F.OP_AND, F.OP_OR, F.OP_XOR):
-            if ldyn or rdyn or ldt != T.Boolean or rdt != T.Boolean:
-                raise TypeError("& | ^ need boolean operands on this path")
-            return self._push(kind=F.AE_BINARY, op=op, lhs=li, rhs=ri), T.Boolean
-        # --- type coercion (type_coercion/binary.rs) ---
         if ldyn and rdyn:
             li, ldt = self._materialise_dyn(li, None)
             ri, rdt = self._materialise_dyn(ri, None)
@@ -298,6 +290,22 @@ class Lowering:
             li = self._cast(li, ldt, st)
             ri = self._cast(ri, rdt, st)
             ldt = rdt = st
+        return li, ldt, ri, rdt
+
+    def _lower_binary(self, e: Expr, schema: Schema):
+        op = e.op
+        if (e.lhs.kind == "lit" and isinstance(e.lhs.value, str)) or (e.rhs.kind == "lit" and isinstance(e.rhs.value, str)):
+            return self._lower_string_compare(e, schema)
+        li, ldt = self._lower_maybe_dyn(e.lhs, schema)
+        ri, rdt = self._lower_maybe_dyn(e.rhs, schema)
+        ldyn, rdyn = isinstance(li, tuple), isinstance(ri, tuple)
+        if not ldyn and not rdyn and isinstance(ldt, T.DatetimeType) and isinstance(rdt, T.DatetimeType) and ldt.time_unit != rdt.time_unit:
+            return self._lower_mixed_time_units(op, li, ldt, ri, rdt)
+        if op in (F.OP_AND, F.OP_OR, F.OP_XOR):
+            if ldyn or rdyn or ldt != T.Boolean or rdt != T.Boolean:
+                raise TypeError("& | ^ need boolean operands on this path")
+            return self._push(kind=F.AE_BINARY, op=op, lhs=li, rhs=ri), T.Boolean
+        li, ldt, ri, rdt = self._coerce_pair(li, ldt, ri, rdt)
         if op in (F.OP_EQ, F.OP_NE, F.OP_LT, F.OP_LE, F.OP_GT, F.OP_GE):
             out = T.Boolean
         elif op == F.OP_TRUE_DIVIDE:
@@ -305,6 +313,32 @@ class Lowering:
         else:
             out = ldt
         return self._push(kind=F.AE_BINARY, op=op, lhs=li, rhs=ri), out
+
+    def _lower_ternary(self, e: Expr, schema: Schema):
+        """when(cond).then(lhs).otherwise(rhs) (TernaryExpr): the branches meet in their supertype by the rules of a binary expression; an open otherwise, or a
+        bare None on either side, is a null of the other branch's dtype."""
+        pi, pdt = self.lower_expr(e.cond, schema)
+        if pdt != T.Boolean:
+            raise TypeError(f"when(...) needs a Boolean predicate, got {pdt}")
+        bare_null = lambda x: x is None or (x.kind == "lit" and x.value is None and x.dtype is None)
+        if bare_null(e.lhs) and bare_null(e.rhs):
+            ai, adt = self.lower_expr(e.lhs, schema)
+            return self._push(kind=F.AE_TERNARY, lhs=ai, rhs=self._null_node(adt), cond=pi), adt
+        if bare_null(e.lhs) or bare_null(e.rhs):
+            oi, odt = self.lower_expr(e.rhs if bare_null(e.lhs) else e.lhs, schema)
+            ni = self._null_node(odt)
+            ai, bi = (ni, oi) if bare_null(e.lhs) else (oi, ni)
+            return self._push(kind=F.AE_TERNARY, lhs=ai, rhs=bi, cond=pi), odt
+        ai, adt = self._lower_maybe_dyn(e.lhs, schema)
+        bi, bdt = self._lower_maybe_dyn(e.rhs, schema)
+        dyn = isinstance(ai, tuple) or isinstance(bi, tuple)
+        if not dyn and isinstance(adt, T.DatetimeType) and isinstance(bdt, T.DatetimeType) and adt.time_unit != bdt.time_unit:
+            raise TypeError(f"when/then/otherwise branches Datetime[{adt.time_unit}] and Datetime[{bdt.time_unit}]: casts between time units are not on this path")
+        ai, adt, bi, bdt = self._coerce_pair(ai, adt, bi, bdt)
+        return self._push(kind=F.AE_TERNARY, lhs=ai, rhs=bi, cond=pi), adt
+
+    def _null_node(self, dt: T.DataType) -> int:
+        return self._push(kind=F.AE_LITERAL, dtype=dt.physical, lit=0, is_null=1)
 
     # -- IR ----------------------------------------------------------------------------------
     def lower_node(self, n: Node) -> Tuple[int, Schema]:
@@ -388,7 +422,7 @@ class Lowering:
         ae = (F.AExpr * max(n_ae, 1))()
         for i, d in enumerate(self.aexprs):
             a = ae[i]
-            a.kind, a.op, a.lhs, a.rhs, a.dtype, a.is_null = d["kind"], d["op"], d["lhs"], d["rhs"], d["dtype"], d["is_null"]
+            a.kind, a.op, a.lhs, a.rhs, a.dtype, a.is_null, a.cond = d["kind"], d["op"], d["lhs"], d["rhs"], d["dtype"], d["is_null"], d["cond"]
             if d["kind"] == F.AE_LITERAL and not d["is_null"]:
                 dt = d["dtype"]
                 if dt == F.F64:

@@ -163,6 +163,12 @@ class Translator:
             return E.len()
         if kind == "Alias":
             return self.expr(x.expr).alias(str(x.name))
+        if kind == "Ternary":                                   # visitor/expr_nodes.rs: predicate, truthy, falsy (expression node ids); the optimizer has cast the branches
+            parts = [getattr(x, f, None) for f in ("predicate", "truthy", "falsy")]
+            if any(p is None for p in parts):
+                raise NotSupported("Ternary node without predicate / truthy / falsy")
+            cond, truthy, falsy = (self.expr(p) for p in parts)
+            return E.Expr("ternary", lhs=truthy, rhs=falsy, cond=cond)
         raise NotSupported(f"expression node {kind}")
 
     def named(self, e: Any) -> E.Expr:

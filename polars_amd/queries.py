@@ -128,3 +128,23 @@ def q3_top10(lineitem, orders, date=Q3_DATE, seg_mod=5):
     """TPC-H Q3 including its ORDER BY revenue DESC, o_orderdate LIMIT 10: the Slice directly above the Sort becomes a
     radix select over the ~1e6 groups."""
     return q3(lineitem, orders, date, seg_mod).sort("revenue", "o_orderdate", descending=[True, False]).head(10)
+
+
+def q12(lineitem, orders, modes=(3, 5), high=(0, 1)):
+    """TPC-H Q12's shape over caller-supplied frames: lineitem[l_shipmode in modes] JOIN orders ON orderkey, grouped by ship mode, with the two conditional counts
+    sum(case when o_orderpriority in high then 1 else 0 end) and its complement.  Ship modes and priorities are whatever the frames hold: integer codes, or
+    strings against dictionary-encoded columns."""
+    c = E.col
+    is_high = c("o_orderpriority").is_in(high)
+    j = lineitem.filter(c("l_shipmode").is_in(modes)).join(orders, left_on="l_orderkey", right_on="o_orderkey")
+    return j.group_by("l_shipmode").agg(E.when(is_high).then(1).otherwise(0).sum().alias("high_line_count"),
+                                        E.when(~is_high).then(1).otherwise(0).sum().alias("low_line_count"))
+
+
+def q14_sums(lineitem, part, promo_below=25):
+    """The two sums of TPC-H Q14 over caller-supplied frames: lineitem JOIN part ON partkey, then sum(case when promo then revenue else 0 end) and sum(revenue) with
+    promo = p_type < promo_below (dbgen's PROMO% types as a code range).  The final ratio is arithmetic over aggregates, left to the caller."""
+    c = E.col
+    rev = c("l_extendedprice") * (1 - c("l_discount"))
+    j = lineitem.join(part, left_on="l_partkey", right_on="p_partkey")
+    return j.select(E.when(c("p_type") < promo_below).then(rev).otherwise(0.0).sum().alias("promo_revenue"), rev.sum().alias("revenue"))
