@@ -222,6 +222,12 @@ int plx_column_from_device(plx_dtype dtype, void* dev_values, void* dev_validity
  * rejects it. */
 int plx_column_placeholder(plx_dtype dtype, int64_t len, int nullable, int has_range, int64_t range_min, int64_t range_max,
                            plx_column* out);
+/* Planning-only: declares the encoded shadow a placeholder column would have (kind 1 = affine, value = base + stride * code; 2 = dictionary; width = bytes per
+ * code, 1 | 2), so that plx_describe_fusion / plx_debug_program_json show the program a scan of the encoded column runs.  Placeholder columns only. */
+int plx_column_placeholder_encoding(plx_column col, int32_t kind, int32_t width, int64_t base, uint64_t stride);
+/* The affine chooser of the encoded shadows, a pure function: from the exact minimum / maximum of a column's valid rows and gcd = gcd(v - min) over them (0: not
+ * computed) -> whether the column encodes, code width in bytes, base and stride.  needs_gcd: the span alone does not decide, the gcd pass has to run. */
+int plx_encoding_choose_affine(int64_t min, int64_t max, uint64_t gcd, int32_t* ok, int32_t* width, int64_t* base, uint64_t* stride, int32_t* needs_gcd);
 /* Caller-provided value bounds of an integer column (dictionary size of a Categorical, Parquet column-chunk min / max
  * statistics): every valid value lies in [lo, hi].  The planner uses them the way the reference uses sortedness flags and
  * metadata statistics -- to choose dense / direct-address group tables without a pass over the data.  Kernels that rely on
@@ -229,7 +235,7 @@ int plx_column_placeholder(plx_dtype dtype, int64_t len, int nullable, int has_r
 int plx_column_set_bounds(plx_column col, int64_t lo, int64_t hi);
 /* Forgets what the library has LEARNED about the column (value range computed by a statistics pass or as a by-product of a scan, the group-by
  * planner's key sample and heavy hitters, the sampled sortedness): the next query pays for them again, as the first query on a fresh column
- * does.  Bounds declared with plx_column_set_bounds stay.  Measurement support (bench.py `one_shot_ms`); never changes a result. */
+ * does.  The column's encoded shadow and the count of scans towards one go too.  Bounds declared with plx_column_set_bounds stay.  Measurement support (bench.py `one_shot_ms`); never changes a result. */
 int plx_column_drop_statistics(plx_column col);
 /* Arrow C Data Interface import: copies to HBM, then calls array->release and
  * schema->release (callee takes ownership: plugin.rs:122-125 convention). */
@@ -469,6 +475,10 @@ int plx_jit_set_min_rows(int64_t min_rows);
 /* Human-readable physical plan (which fused pipeline / kernels were chosen) of the
  * last plx_execute_plan on this thread. */
 const char* plx_last_plan_description(void);
+/* The inputs that the fused aggregate scans of the calling thread's last plx_execute_plan read through their encoded shadows, one
+ * "encoded{l_shipdate:affine16,l_discount:dict8}; " per scan; "" when every scan read its columns as stored.  Kept beside the plan description, not in
+ * it: the description names the route, and the route of a query is the same whether its inputs are read plain or encoded. */
+const char* plx_last_plan_encodings(void);
 
 /* ---- synthetic benchmark data (no reference counterpart: dbgen lives outside the reference tree) -------
  * Fills n_rows of the TPC-H Q1 lineitem columns directly in HBM with a counter-based generator (row i is a pure

@@ -120,6 +120,8 @@ SIGNATURES = {
     "plx_column_from_host": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _u64p]),
     "plx_column_from_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _u64p]),
     "plx_column_placeholder": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, _u64p]),
+    "plx_column_placeholder_encoding": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.c_uint64]),
+    "plx_encoding_choose_affine": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, _i32p, _i32p, C.POINTER(C.c_int64), _u64p, _i32p]),
     "plx_column_set_bounds": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64]),
     "plx_column_drop_statistics": (C.c_int, [C.c_uint64]),
     "plx_strview_dict_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, _u64p, _u64p]),
@@ -209,6 +211,7 @@ SIGNATURES = {
     "plx_jit_stats": (C.c_int, [_i32p, C.POINTER(C.c_double)]),
     "plx_jit_set_min_rows": (C.c_int, [C.c_int64]),
     "plx_last_plan_description": (C.c_char_p, []),
+    "plx_last_plan_encodings": (C.c_char_p, []),
     "plx_profile_enable": (C.c_int, [C.c_int]),
     "plx_profile_fetch": (C.c_int, [C.POINTER(ProfileRecord), C.c_int32, _i32p]),
     "plx_profile_clear": (C.c_int, []),
@@ -271,6 +274,11 @@ def set_plan_note(note) -> None:
 def last_plan() -> str:
     note = getattr(_tls, "plan_note", None)
     return note if note is not None else lib().plx_last_plan_description().decode()
+
+
+def last_plan_encodings() -> str:
+    """The inputs the last collect()'s fused aggregate scans read through their encoded shadows ("encoded{l_shipdate:affine16,l_discount:dict8}; "), or ""."""
+    return lib().plx_last_plan_encodings().decode()
 
 
 def jit_set_min_rows(min_rows: int) -> None:

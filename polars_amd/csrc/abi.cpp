@@ -9,6 +9,7 @@
 
 #include "core.hpp"
 #include "datagen_device.hpp"
+#include "encoded_inputs.hpp"
 #include "engine.hpp"
 #include "fused_shapes.hpp"
 #include "jit.hpp"
@@ -44,6 +45,7 @@ using namespace plx;
   return PLX_OK;
 
 static thread_local std::string t_plan_desc;
+static thread_local std::string t_plan_encoded;
 
 extern "C" {
 
@@ -101,6 +103,27 @@ int plx_column_placeholder(plx_dtype dtype, int64_t len, int nullable, int has_r
   PLX_CATCH
 }
 
+int plx_column_placeholder_encoding(plx_column col, int32_t kind, int32_t width, int64_t base, uint64_t stride) {
+  PLX_TRY
+  ColumnPtr c = get_column(col);
+  PLX_REQUIRE(!c->values, PLX_ERR_INVALID, "placeholder_encoding: placeholder columns only");
+  PLX_REQUIRE((kind == EncodedShadow::kAffine || kind == EncodedShadow::kDict) && (width == 1 || width == 2) && stride >= 1, PLX_ERR_INVALID, "placeholder_encoding: kind 1 | 2, width 1 | 2, stride >= 1");
+  auto s = std::make_shared<EncodedShadow>();
+  s->kind = kind; s->width = width; s->base = base; s->stride = stride;
+  std::atomic_store(&c->shadow, s);
+  PLX_CATCH
+}
+int plx_encoding_choose_affine(int64_t mn, int64_t mx, uint64_t gcd, int32_t* ok, int32_t* width, int64_t* base, uint64_t* stride, int32_t* needs_gcd) {
+  PLX_TRY
+  const enc::AffineChoice ch = enc::choose_affine(mn, mx, gcd);
+  if (ok) *ok = ch.ok ? 1 : 0;
+  if (width) *width = ch.width;
+  if (base) *base = ch.base;
+  if (stride) *stride = ch.stride;
+  if (needs_gcd) *needs_gcd = enc::affine_needs_gcd(mn, mx) ? 1 : 0;
+  PLX_CATCH
+}
+
 int plx_column_set_bounds(plx_column col, int64_t lo, int64_t hi) {
   PLX_TRY
   ColumnPtr c = get_column(col);
@@ -117,6 +140,7 @@ int plx_column_drop_statistics(plx_column col) {
   std::atomic_store(&c->key_sample, std::shared_ptr<void>());
   c->order_state = 0;
   c->repeats_as_build_key = false;
+  std::atomic_store(&c->shadow, std::shared_ptr<EncodedShadow>());
   PLX_CATCH
 }
 
@@ -831,10 +855,12 @@ int plx_execute_plan(const plx_ir* ir, int32_t n_ir, const plx_aexpr* exprs, int
   engine::Plan p = engine::import_plan(ir, n_ir, exprs, n_exprs, flags);
   FramePtr f = engine::execute(p, root);
   t_plan_desc = p.desc;
+  t_plan_encoded = p.encoded;
   *out = register_frame(f);
   PLX_CATCH
 }
 const char* plx_last_plan_description(void) { return t_plan_desc.c_str(); }
+const char* plx_last_plan_encodings(void) { return t_plan_encoded.c_str(); }
 
 int plx_debug_program_json(const plx_ir* ir, int32_t n_ir, const plx_aexpr* exprs, int32_t n_exprs, int32_t root, char* buf, size_t cap) {
   PLX_TRY

@@ -97,6 +97,20 @@ void pool_stats(uint64_t* in_use, uint64_t* high_water);
 void pool_trim(bool force = false);   // force: the reserved block (pool_reserve) is released as well
 
 // --------------------------------------------------------------- columns ----
+// An exact narrow copy of a column for the fused aggregate scans (encoded_inputs.hpp; engine.cpp encoded_shadow_for_scan), and what the engine remembers on the way
+// to one.  Immutable once published: a change is a new object (std::atomic_store on Column::shadow, like key_sample).
+struct EncodedShadow {
+  enum Kind { kNone = 0, kAffine = 1, kDict = 2 };
+  int kind = kNone;         // kNone: no codes (yet); only `scans` / `never_encode` mean anything
+  int width = 0;            // bytes per code: 1 | 2
+  int64_t base = 0;         // affine: value = base + stride * code
+  uint64_t stride = 1;
+  Buf codes;                // one code per row (null rows: code 0); the validity bitmap stays the column's own
+  Buf dict;                 // dict: fused::kDictSlots u64 bit patterns in HBM, sorted, n_dict in use
+  int n_dict = 0;
+  int scans = 0;            // qualifying scans seen since the statistics were last dropped
+  bool never_encode = false;   // the column was tried and does not encode (or its codes could not be allocated)
+};
 struct Column {
   int dtype = PLX_I64;
   int64_t len = 0;
@@ -115,6 +129,7 @@ struct Column {
   // group estimate): a column is immutable, so the next group-by on it with no predicate skips the 8 sample launches (0.3 ms per query)
   std::shared_ptr<void> key_sample;
   int order_state = 0;         // 0 unknown, 1 (roughly) ascending, 2 unordered: sampled once when the column is the probe key of a large join (k::sample_sortedness)
+  std::shared_ptr<EncodedShadow> shadow;   // null until the first qualifying scan; dropped with the statistics, freed with the column
   bool repeats_as_build_key = false;   // learned by a join that built on this column: some key occurs more than once (the next join skips the unique-key attempt; a fact about the column, whatever the predicate was)
   const void* data() const { return values ? values->ptr : nullptr; }
   const uint64_t* valid_words() const { return validity ? validity->as<uint64_t>() : nullptr; }

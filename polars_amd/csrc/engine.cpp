@@ -10,6 +10,7 @@
 #include <set>
 #include <sstream>
 
+#include "encoded_inputs.hpp"
 #include "fused_shapes.hpp"
 #include "jit.hpp"
 #include "join.hpp"
@@ -1038,6 +1039,101 @@ static int64_t sample_keys_cached(const ColumnPtr& key_col, const Shape& sh, con
   return d;
 }
 
+// ---- encoded inputs: narrow shadows of low-cardinality columns (encoded_inputs.hpp, DESIGN.md "Encoded shadows") ----
+// The whole policy lives here.  A column QUALIFIES in a scan when the program reads it whole through a plain OP_LOAD, the scan ends in the register or the LDS
+// aggregate sink (the only callers), the library owns its buffer (a borrowed one can be rewritten by its owner behind our back), and its codes would take at most a
+// quarter of its bytes: 8-byte integers and f64, 4-byte integers when one byte a row is enough.  The SECOND qualifying scan since the statistics were last dropped
+// tries to build the shadow before it launches; one that fails -- too many values, no memory, a row that does not decode to itself -- is never tried again.
+static bool encoded_inputs_enabled() { static const bool v = [] { const char* e = getenv("PLX_ENCODED_INPUTS"); return !(e && e[0] == '0'); }(); return v; }
+static std::shared_ptr<EncodedShadow> build_shadow(const ColumnPtr& col) {
+  auto s = std::make_shared<EncodedShadow>();
+  const int64_t n = col->len;
+  const size_t groups = (size_t)((n + 7) / 8) * 8;      // the encoders store eight codes at a time
+  if (col->dtype == PLX_F64) {
+    std::vector<uint64_t> pats;
+    const int64_t step = (n + ((int64_t)1 << 20) - 1) >> 20;      // a strided sample of at most 2^20 rows first: a high-cardinality column costs microseconds, not a pass
+    if (step > 1 && !enc::dict_collect(col->values->as<uint64_t>(), col->valid_words(), n, step, &pats)) return nullptr;
+    if (!enc::dict_collect(col->values->as<uint64_t>(), col->valid_words(), n, 1, &pats) || pats.empty()) return nullptr;
+    s->kind = EncodedShadow::kDict; s->width = 1; s->n_dict = (int)pats.size();
+    pats.resize(kDictSlots, 0);
+    s->dict = dev_alloc(sizeof(uint64_t) * kDictSlots);
+    s->codes = dev_alloc(groups);
+    h2d_async(s->dict->ptr, pats.data(), sizeof(uint64_t) * kDictSlots);
+    PLX_HIP(hipStreamSynchronize(stream()));
+    if (!enc::dict_encode(col->values->as<uint64_t>(), col->valid_words(), n, s->dict->as<unsigned long long>(), s->n_dict, s->codes->as<uint8_t>())) return nullptr;
+    return s;
+  }
+  // integers: the EXACT range of the valid rows -- the column's cached one only when the library measured it itself, never declared or assumed bounds
+  int64_t mn, mx;
+  if (col->range_state == 1 && col->range_trusted && !col->range_assumed) { mn = col->range_min; mx = col->range_max; }
+  else {
+    const k::ReduceResult rr = k::reduce_all(col->dtype, col->data(), col->valid_words(), n);
+    if (rr.n_valid == 0) return nullptr;
+    mn = (int64_t)rr.minmax_lo; mx = (int64_t)rr.minmax_hi;
+  }
+  uint64_t g = 0;
+  if (enc::affine_needs_gcd(mn, mx)) {
+    if (col->dtype != PLX_I64) return nullptr;      // (a 4-byte column needs one-byte codes: a span past 65535 would have to be a multiple of 2^8 strides -- not worth a pass)
+    g = enc::affine_gcd(col->values->as<int64_t>(), col->valid_words(), n, mn);
+  }
+  const enc::AffineChoice ch = enc::choose_affine(mn, mx, g);
+  if (!ch.ok || ch.width * 4 > dtype_width(col->dtype)) return nullptr;
+  s->kind = EncodedShadow::kAffine; s->width = ch.width; s->base = ch.base; s->stride = ch.stride;
+  s->codes = dev_alloc(groups * (size_t)ch.width);
+  if (!enc::affine_encode(col->dtype, col->data(), col->valid_words(), n, ch.base, ch.stride, ch.width, s->codes->ptr)) return nullptr;
+  return s;
+}
+// the shadow this scan of `col` reads, or null; `may_build`: this is a scan that runs (a compile-only caller sees what is there and counts nothing)
+static std::shared_ptr<EncodedShadow> encoded_shadow_for_scan(const ColumnPtr& col, bool may_build) {
+  if (!encoded_inputs_enabled()) return nullptr;
+  std::shared_ptr<EncodedShadow> s = std::atomic_load(&col->shadow);
+  if (s && s->kind != EncodedShadow::kNone) return s;
+  if (!may_build || (s && s->never_encode) || !col->values || !col->values->owned || col->len <= 0) return nullptr;
+  if (col->dtype != PLX_I64 && col->dtype != PLX_F64 && col->dtype != PLX_I32 && col->dtype != PLX_U32) return nullptr;
+  auto next = std::make_shared<EncodedShadow>();
+  next->scans = (s ? s->scans : 0) + 1;
+  if (next->scans >= 2) {
+    std::shared_ptr<EncodedShadow> built;
+    try { built = build_shadow(col); }
+    catch (const Error& e) { if (e.code != PLX_ERR_OOM) throw; (void)hipGetLastError(); }      // no memory for the codes: the query runs plain
+    if (built) { built->scans = next->scans; next = built; }
+    else next->never_encode = true;
+  }
+  std::atomic_store(&col->shadow, next);
+  return next->kind != EncodedShadow::kNone ? next : nullptr;
+}
+// The program a register / LDS aggregate scan runs: c.shape / c.args, or their rewrite over the shadows of the inputs that have one.
+struct ScanProgram { Shape shape; Args args; int static_id; std::string note; };
+static ScanProgram scan_program_with_encodings(const Compiler& c, bool may_build) {
+  ScanProgram sp{c.shape, c.args, -1, ""};
+  enc::InputEncoding e[kMaxInputs];
+  bool any = false;
+  for (int i = 0; i < c.shape.n_inputs; i++) {
+    const ColumnPtr& col = c.cols[c.input_cols[i]];
+    if (c.args.in[i].values != col->data() || c.args.n_rows != col->len) continue;      // not the whole column
+    const std::shared_ptr<EncodedShadow> s = encoded_shadow_for_scan(col, may_build);
+    if (!s) continue;
+    e[i].kind = s->kind; e[i].width = s->width; e[i].base = s->base; e[i].stride = s->stride;
+    e[i].codes = s->codes ? s->codes->ptr : nullptr; e[i].dict = s->dict ? s->dict->as<unsigned long long>() : nullptr;
+    any = true;      // (the codes outlive the launch: a buffer freed later goes back to a pool that is stream-ordered, see DevBuf)
+  }
+  uint32_t taken = 0;
+  if (any && enc::encode_program(c.shape, c.args, e, &sp.shape, &sp.args, &taken)) {
+    sp.note = "encoded{";
+    bool first = true;
+    for (int i = 0; i < c.shape.n_inputs; i++) {
+      if (!((taken >> i) & 1u)) continue;
+      std::string name = "?";
+      for (size_t j = 0; j < c.df->cols.size(); j++) if (c.df->cols[j] == c.cols[c.input_cols[i]]) name = c.df->names[j];
+      sp.note += std::string(first ? "" : ",") + name + ":" + (e[i].kind == EncodedShadow::kDict ? "dict" : "affine") + std::to_string(8 * e[i].width);
+      first = false;
+    }
+    sp.note += "}";
+  }
+  sp.static_id = find_static_shape(sp.shape);
+  return sp;
+}
+
 // ---- the fused group-by driver: run_fused_groupby chooses the route, each route is one function that says whether it produced the result ----
 namespace {
 // what the routes of one run share
@@ -1244,13 +1340,22 @@ void hash_hbm_table(GroupByRun& q, int log2_cap) {
 }
 }  // namespace
 
-static void run_fused_groupby(Compiler& c, const KeyPlan& kp, int len_idx, FusedAggResult& res, std::string& desc) {
+static bool lds_table_route(const KeyPlan& kp, const Shape& sh) { return kp.packed && kp.total_bits <= 12 && k::lds_agg_copies(1 << kp.total_bits, sh.n_aggs) > 0; }
+static void run_fused_groupby(Compiler& c, const KeyPlan& kp, int len_idx, FusedAggResult& res, std::string& desc, std::string& encoded) {
   const Shape& sh = c.shape;
   const int64_t n = c.args.n_rows;
   res.n_aggs = sh.n_aggs;
   if (n == 0) { res.n_groups = 0; res.acc = dev_alloc(8); res.packed_keys = dev_alloc(8); return; }
   GroupByRun q{c, kp, sh, c.args, len_idx, find_static_shape(sh), !(c.plan.flags & PLX_PLAN_NO_PARTITION) && n >= ((int64_t)1 << 24), res, desc};
-  if (kp.packed && kp.total_bits <= 12 && k::lds_agg_copies(1 << kp.total_bits, sh.n_aggs) > 0) return lds_table(q);
+  if (lds_table_route(kp, sh)) {
+    // the route is chosen on the plain program; this one may read encoded inputs (every other route keeps the plain program and its record packing)
+    const ScanProgram sp = scan_program_with_encodings(c, true);
+    if (sp.note.empty()) return lds_table(q);
+    GroupByRun qe{c, kp, sp.shape, sp.args, len_idx, sp.static_id, q.may_partition, res, desc};
+    lds_table(qe);
+    encoded += sp.note + "; ";      // (beside the plan text, not in it: Plan::encoded)
+    return;
+  }
   if (kp.packed && kp.total_bits > 12 && q.may_partition && partitioned_packed_ids(q)) return;
   if (kp.packed && kp.total_bits <= 28 && ((size_t)sh.n_aggs << (kp.total_bits + 3)) <= (size_t(8) << 30)) return dense_hbm_table(q);
   HashSizing hs = size_hash_table(q);
@@ -1316,9 +1421,10 @@ struct ProgramDump {
 static thread_local ProgramDump* t_program_dump = nullptr;   // set only for the duration of a dump_program_json call
 static std::string jstr(const std::string& x) { std::string o = "\""; for (char ch : x) { if (ch == '"' || ch == '\\') o += '\\'; o += ch; } return o + "\""; }
 // the register program of one compiled scan as JSON fields (no braces); input names are looked up in `frame` by buffer identity
-static std::string program_fields(const Compiler& c, const Frame& frame) {
+static std::string program_fields(const Compiler& c, const Frame& frame, const Shape* sh_run = nullptr, const Args* args_run = nullptr) {
   std::ostringstream o;
-  const Shape& sh = c.shape;
+  const Shape& sh = sh_run ? *sh_run : c.shape;      // (the program as it runs: c's own, or its rewrite over encoded inputs -- same inputs, same order)
+  const Args& args = args_run ? *args_run : c.args;
   o << "\"n_rows\":" << c.args.n_rows << ",\"inputs\":[";
   auto name_of = [&](int col_id) -> std::string {   // input_cols holds the compiler's own column ids: map the buffer back to its frame column
     const ColumnPtr& buf = c.cols[col_id];
@@ -1329,7 +1435,7 @@ static std::string program_fields(const Compiler& c, const Frame& frame) {
     o << (i ? "," : "") << "{\"name\":" << jstr(name_of(c.input_cols[i])) << ",\"dtype\":" << (int)sh.in_dtype[i] << ",\"nullable\":" << (int)sh.in_nullable[i] << "}";
   o << "],\"ops\":[";
   for (int i = 0; i < sh.n_ops; i++)
-    o << (i ? "," : "") << "[" << (int)sh.ops[i].code << "," << (int)sh.ops[i].dst << "," << (int)sh.ops[i].a << "," << (int)sh.ops[i].b << "," << (int)sh.ops[i].c << ",\"" << c.args.imm[i] << "\"]";
+    o << (i ? "," : "") << "[" << (int)sh.ops[i].code << "," << (int)sh.ops[i].dst << "," << (int)sh.ops[i].a << "," << (int)sh.ops[i].b << "," << (int)sh.ops[i].c << ",\"" << args.imm[i] << "\"]";
   o << "],\"pred\":" << (int)sh.pred << ",\"key\":" << (int)sh.key << ",\"keys\":[";
   for (int i = 0; i < sh.n_keys; i++) o << (i ? "," : "") << (int)sh.keys[i];
   o << "],\"aggs\":[";
@@ -1356,10 +1462,11 @@ static std::string finals_outputs_fields(const Plan& plan, const std::vector<int
   o << "]";
   return o.str();
 }
-static std::string compiled_json(const char* kind, const Plan& plan, const Compiler& c, const KeyPlan* kp, const std::vector<int>& agg_nodes,
+static std::string compiled_json(const char* kind, const Plan& plan, const Compiler& c, const ScanProgram& sp, const KeyPlan* kp, const std::vector<int>& agg_nodes,
                                  const std::vector<FinalSpec>& specs, const std::vector<int>& out_exprs, int len_idx, int first_idx, bool maintain_order) {
   std::ostringstream o;
-  o << "{\"kind\":\"" << kind << "\"," << program_fields(c, *c.df);
+  o << "{\"kind\":\"" << kind << "\"," << program_fields(c, *c.df, &sp.shape, &sp.args);
+  if (!sp.note.empty()) o << ",\"encoded\":" << jstr(sp.note);
   o << ",\"len_idx\":" << len_idx << ",\"first_idx\":" << first_idx << ",\"maintain_order\":" << (maintain_order ? 1 : 0);
   if (kp) {
     o << ",\"key_plan\":{\"packed\":" << (kp->packed ? 1 : 0) << ",\"wide\":" << (kp->wide ? 1 : 0) << ",\"parts\":[";
@@ -1373,9 +1480,9 @@ static std::string compiled_json(const char* kind, const Plan& plan, const Compi
   o << "," << finals_outputs_fields(plan, agg_nodes, specs, out_exprs) << "}";
   return o.str();
 }
-static void dump_compiled(ProgramDump* dump, const char* kind, const Plan& plan, const Compiler& c, const KeyPlan* kp, const std::vector<int>& agg_nodes,
+static void dump_compiled(ProgramDump* dump, const char* kind, const Plan& plan, const Compiler& c, const ScanProgram& sp, const KeyPlan* kp, const std::vector<int>& agg_nodes,
                           const std::vector<FinalSpec>& specs, const std::vector<int>& out_exprs, int len_idx, int first_idx, bool maintain_order) {
-  if (dump) dump->json = compiled_json(kind, plan, c, kp, agg_nodes, specs, out_exprs, len_idx, first_idx, maintain_order);
+  if (dump) dump->json = compiled_json(kind, plan, c, sp, kp, agg_nodes, specs, out_exprs, len_idx, first_idx, maintain_order);
 }
 // conjunction of the predicates `preds` lowered into `c`: its node, or -1 when there is none
 static int and_predicates(Compiler& c, const std::vector<int>& preds) {
@@ -1397,18 +1504,20 @@ static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& pr
     for (int a : agg_nodes) specs.push_back(c.lower_agg(a));
     c.finish();
   } catch (const Unsupported& u) { if (why) *why = u.why; return false; }
-  const int static_id = find_static_shape(c.shape);
-  if (shape_out) *shape_out = c.shape;
+  const ScanProgram sp = scan_program_with_encodings(c, !compile_only && src->height > 0);
+  const int static_id = sp.static_id;
+  if (shape_out) *shape_out = sp.shape;
   if (sid_out) *sid_out = static_id;
-  if (compile_only) { dump_compiled(t_program_dump, "select", plan, c, nullptr, agg_nodes, specs, node.exprs, -1, -1, false); return true; }
+  if (compile_only) { dump_compiled(t_program_dump, "select", plan, c, sp, nullptr, agg_nodes, specs, node.exprs, -1, -1, false); return true; }
   FusedAggResult r; r.n_groups = 1; r.n_aggs = c.shape.n_aggs;
   std::vector<uint64_t> host(kMaxAggs, 0);
   if (src->height == 0) { for (int k2 = 0; k2 < c.shape.n_aggs; k2++) host[k2] = agg_identity(c.shape.aggs[k2].kind); }
-  else k::fused_regagg(c.shape, c.args, static_id, host.data());
+  else k::fused_regagg(sp.shape, sp.args, static_id, host.data());
   r.acc = dev_alloc(sizeof(uint64_t) * kMaxAggs);
   h2d_async(r.acc->ptr, host.data(), sizeof(uint64_t) * (size_t)c.shape.n_aggs);
   PLX_HIP(hipStreamSynchronize(stream()));
   plan.desc += std::string("FusedFilterAgg{fused_scan[") + jit::program_mode(static_id, c.args.n_rows) + "]+register_sink, inputs=" + std::to_string(c.shape.n_inputs) + ", ops=" + std::to_string(c.shape.n_ops) + ", aggs=" + std::to_string(c.shape.n_aggs) + "}; ";
+  if (!sp.note.empty()) plan.encoded += sp.note + "; ";
   std::map<int, ColumnPtr> overrides;
   FinBatch batch{};
   for (size_t i = 0; i < agg_nodes.size(); i++) overrides[agg_nodes[i]] = finalize_column(r, specs[i], batch);
@@ -1448,13 +1557,20 @@ static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& p
     if (node.maintain_order) first_idx = c.add_agg(AGG_FIRST_ROW, -1);
     c.finish();
   } catch (const Unsupported& u) { if (why) *why = u.why; return false; }
+  if (compile_only) {
+    // what the run would launch: the LDS-table route reads the encoded inputs that exist (nothing is counted or built here)
+    const ScanProgram sp = lds_table_route(kp, c.shape) ? scan_program_with_encodings(c, false) : ScanProgram{c.shape, c.args, find_static_shape(c.shape), ""};
+    if (shape_out) *shape_out = sp.shape;
+    if (sid_out) *sid_out = sp.static_id;
+    dump_compiled(t_program_dump, "group_by", plan, c, sp, &kp, agg_nodes, specs, node.exprs, len_idx, first_idx, node.maintain_order != 0);
+    return true;
+  }
   if (shape_out) *shape_out = c.shape;
   if (sid_out) *sid_out = find_static_shape(c.shape);
-  if (compile_only) { dump_compiled(t_program_dump, "group_by", plan, c, &kp, agg_nodes, specs, node.exprs, len_idx, first_idx, node.maintain_order != 0); return true; }
   FusedAggResult r;
   std::string d;
   try {
-    run_fused_groupby(c, kp, len_idx, r, d);
+    run_fused_groupby(c, kp, len_idx, r, d, plan.encoded);
   } catch (const Error& e) {
     // a row outside bounds the planner had only ASSUMED (assume_range): forget the guesses, never guess about these columns again, and run the query once more --
     // its statistics now come from exact passes.  (Bounds the caller declared are the caller's promise: that error stands.)
@@ -1974,7 +2090,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
       o << "]";
       // a left join's unmatched rows: a group-by program over the probe side whose predicate ends in NOT member(key) -- lookup bitmap `lut` = the build keys that pass the build program
       if (left_join) o << ",\"unmatched\":{\"lut\":" << psemis.size() << ",\"kmin\":\"" << unmatched_keys.kmin << "\",\"range\":\"" << unmatched_keys.range << "\",\"program\":"
-                       << compiled_json("group_by", plan, ca, &akp, agg_nodes, aspecs, gb.exprs, a_len_idx, -1, false) << "}";
+                       << compiled_json("group_by", plan, ca, ScanProgram{ca.shape, ca.args, -1, ""}, &akp, agg_nodes, aspecs, gb.exprs, a_len_idx, -1, false) << "}";
       o << "}";
       t_program_dump->json = o.str();
     }
@@ -2177,7 +2293,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
     FusedAggResult ar;
     std::string ad;
     try {
-      run_fused_groupby(ca, akp, a_len_idx, ar, ad);
+      run_fused_groupby(ca, akp, a_len_idx, ar, ad, plan.encoded);
     } catch (const Error& e) {
       // a row outside bounds the planner had only ASSUMED for the probe key / value columns (lower_keys(ca) and source_ranges run outside fused_groupby's own handler): forget
       // the guesses, never guess about these columns again, and run the whole join once more from exact statistics -- like fused_groupby does

@@ -42,6 +42,7 @@ struct Plan {
   std::vector<AE> ae;
   uint32_t flags = 0;
   std::string desc;  // physical plan description (which kernels / pipelines ran)
+  std::string encoded;  // the inputs the fused aggregate scans of this plan read through their encoded shadows: "encoded{l_shipdate:affine16,l_discount:dict8}; " per scan, empty when none
   std::map<int, FramePtr> memo;  // subtrees already executed for a fusion attempt that then fell back: the per-node path reuses them
   // An upper bound on the number of groups of the group-by about to run that the PLAN knows (0: none): the pair form of a join -> group-by whose keys are functions of the
   // build row has at most as many groups as build rows survive the build side's predicate.  It replaces the planner's sampled estimate -- the joined rows arrive clustered by

@@ -60,7 +60,10 @@ enum OpCode : uint8_t {
   OP_MASKV,
   // dst <- rows where c is valid and true take a, every other row takes b (a null predicate selects b); value AND validity are the chosen side's, the predicate's own
   // validity never reaches dst.  when(c).then(a).otherwise(b): the only op with three source slots (op_src_slots)
-  OP_SELECT
+  OP_SELECT,
+  // dst <- args.dict[c][a], with the validity of a: the value of a dictionary-encoded input (Column::shadow) from its one-byte code.  Every dictionary holds kDictSlots
+  // words, so any code a u8 / u16 load can produce after the mask stays inside it
+  OP_DICT
 };
 
 struct Op {
@@ -151,6 +154,8 @@ struct Input {
   const uint64_t* validity;
 };
 constexpr int kMaxLuts = 2;
+constexpr int kMaxDicts = 4;        // dictionary-encoded inputs of one program (OP_DICT)
+constexpr int kDictSlots = 256;     // words of every dictionary buffer, whatever number of them is in use
 struct Lut {
   const unsigned long long* bits;   // [range / 64 + 1] words
   uint64_t range;
@@ -160,6 +165,7 @@ struct Args {
   Input in[kMaxInputs];
   uint64_t imm[kMaxOps];
   Lut lut[kMaxLuts];
+  const unsigned long long* dict[kMaxDicts];   // OP_DICT: kDictSlots 64-bit patterns each
   int64_t n_rows;
   // generic interpreter only: its register file lives in dynamic LDS behind the sink's own LDS (set by the launcher)
   uint32_t rf_lds_offset;

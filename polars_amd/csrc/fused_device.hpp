@@ -332,6 +332,12 @@ __device__ __forceinline__ void exec_op(const Op op, const Shape& sh, const Args
         }
         vd = (t & va) | (~t & vb);
       } break;
+      case OP_DICT: {   // a per-lane gather from a 2 KB table: a wave's lanes land on the few lines that hold the dictionary's live entries
+        const unsigned long long* dict = args.dict[op.c < kMaxDicts ? op.c : 0];
+#pragma unroll
+        for (int r = 0; r < kRows; r++) d[r] = dict[a[r] & (uint64_t)(kDictSlots - 1)];
+        vd = va;
+      } break;
       default:  // OP_MOV / OP_NOP
 #pragma unroll
         for (int r = 0; r < kRows; r++) d[r] = a[r];

@@ -209,6 +209,7 @@ void fused_lds_agg(const Shape& sh, const Args& args, int n_groups, int static_i
     ProfileScope ps(scope_name("fused_scan_ldsagg_static", "fused_scan_ldsagg_generic", static_id).c_str(), algo_bytes(sh, args), (uint64_t)args.n_rows);
     switch (static_id) {
       case SHAPE_Q1: PLX_LAUNCH_SCAN(StatProg<SHAPE_Q1>, LdsAggSink, grid, lds, sh, args, sp); break;
+      case SHAPE_Q1_ENCODED: PLX_LAUNCH_SCAN(StatProg<SHAPE_Q1_ENCODED>, LdsAggSink, grid, lds, sh, args, sp); break;
       default: if (!jit::launch(sh, args, jit::LDSAGG, &sp, grid, lds)) { const DynLaunch d = dyn_launch(sh, args, lds); PLX_LAUNCH_SCAN(DynProg, LdsAggSink, grid, d.lds, sh, d.args, sp); } break;
     }
     PLX_HIP(hipGetLastError());

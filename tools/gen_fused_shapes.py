@@ -25,6 +25,26 @@ def ph(name, dtype, n=1 << 20, nullable=False, rng=None):
     return pl.Series._from_handle(name, h.value, dtype)
 
 
+def encoded(s, kind, width, base=0, stride=1):
+    """Declares the encoded shadow the column would have ("Encoded shadows"): the program compiled over it reads the codes."""
+    F.check(F.lib().plx_column_placeholder_encoding(s._h, kind, width, base, stride))
+    return s
+
+
+AFFINE, DICT = 1, 2
+DAY_US = 86_400_000_000
+
+
+def lineitem_encoded():
+    """The Q1 columns as the shadows of the generator's data (csrc/datagen_device.hpp) come out: l_shipdate = day 8036 + k days, k < 2647 (two-byte codes, stride and
+    base); l_quantity 1..50 (one-byte codes, base only); l_discount / l_tax 11 and 9 distinct f64 values (one-byte dictionary codes); the rest stay as they are."""
+    flag = pl.Categorical(["A", "N", "R"], pl.UInt8)
+    status = pl.Categorical(["F", "O"], pl.UInt8)
+    return pl.DataFrame([encoded(ph("l_shipdate", pl.Datetime), AFFINE, 2, 8036 * DAY_US, DAY_US), ph("l_returnflag", flag, rng=(0, 2)), ph("l_linestatus", status, rng=(0, 1)),
+                         encoded(ph("l_quantity", pl.Int64), AFFINE, 1, 1, 1), ph("l_extendedprice", pl.Float64), encoded(ph("l_discount", pl.Float64), DICT, 1),
+                         encoded(ph("l_tax", pl.Float64), DICT, 1)])
+
+
 def frames():
     cfg = pl.DataFrame([ph("a", pl.Int64), ph("x", pl.Float64), ph("y", pl.Float64)])
     cfgn = pl.DataFrame([ph("a", pl.Int64), ph("x", pl.Float64, nullable=True), ph("y", pl.Float64)])
@@ -60,6 +80,8 @@ def shapes():
         ("SHAPE_Q3D_BUILD", "lineitem JOIN partsupp (duplicate build keys) build scan: ps_group predicate fused, ps_partkey -> row chains [bench workload q3d]",
          Q.q3_partsupp(pl.DataFrame([ph("l_partkey", pl.Int64, n=1 << 22), ph("l_extendedprice", pl.Float64, n=1 << 22), ph("l_discount", pl.Float64, n=1 << 22), ph("l_shipdate", pl.Datetime, n=1 << 22)]).lazy(),
                        pl.DataFrame([ph("ps_partkey", pl.Int64), ph("ps_suppkey", pl.Int64), ph("ps_group", pl.Int64)]).lazy()), 1),
+        ("SHAPE_Q1_ENCODED", "TPC-H Q1 over the encoded shadows of l_shipdate (u16, stride, base), l_quantity (u8, base), l_discount and l_tax (u8 dictionary codes)",
+         Q.q1(lineitem_encoded().lazy()), 0),
     ]
 
 
