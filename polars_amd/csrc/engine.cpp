@@ -562,7 +562,7 @@ class Compiler {
         input_cols.push_back(d.col); idx = (int)input_cols.size() - 1;
         const ColumnPtr& c = cols[d.col];
         shape.in_dtype[idx] = (uint8_t)c->dtype; shape.in_nullable[idx] = d.nullable ? 1 : 0;
-        args.in[idx].values = c->data(); args.in[idx].validity = c->valid_words();
+        args.in[idx].values = c->data(); args.in[idx].validity = d.nullable ? c->valid_words() : nullptr;      // (the same pointer either way: nullable <=> the column has a bitmap; fused_sinks.hpp trust_nullable relies on it)
       }
       op.a = (uint8_t)idx;
     } else if (d.code == OP_CONST) {

@@ -79,8 +79,10 @@ __device__ __forceinline__ void load2(const void* base_ptr, int64_t row0, int64_
   }
 }
 
+// `may_be_null` false: the caller knows the input has no validity bitmap (Shape::in_nullable == 0 of a compile-time program: the host compiler sets that flag and
+// Input::validity from the same column, engine.cpp Compiler::emit), so the test of in.validity -- a scalar branch between every two column loads -- is not compiled in
 template <bool FULL>
-__device__ __forceinline__ void load_input(const Input& in, int dtype, int64_t row0, int64_t n, uint64_t out[kRows], uint32_t& vbits) {
+__device__ __forceinline__ void load_input(const Input& in, int dtype, int64_t row0, int64_t n, uint64_t out[kRows], uint32_t& vbits, bool may_be_null = true) {
   switch (dtype) {
     case PLX_I64: case PLX_U64: case PLX_F64: load2<uint64_t, FULL>(in.values, row0, n, out); break;
     case PLX_I32: load2<int32_t, FULL>(in.values, row0, n, out); break;
@@ -97,7 +99,7 @@ __device__ __forceinline__ void load_input(const Input& in, int dtype, int64_t r
     default: out[0] = out[1] = 0; break;
   }
   vbits = (1u << kRows) - 1;
-  if (in.validity) {
+  if (may_be_null && in.validity) {
     int64_t i = row0; if (!FULL && i > n - 1) i = n - 1;
     vbits = (uint32_t)(in.validity[i >> 6] >> (i & 63)) & ((1u << kRows) - 1);
     if (!FULL && row0 + 1 > n - 1) vbits &= 1u;  // second row clamped: validity irrelevant (row masked out)
@@ -171,13 +173,41 @@ __device__ __forceinline__ void store_prefetched(const Shape& sh, const Args& ar
   }
 }
 
+// ---- dictionaries in LDS (AOT / JIT programs) ------------------------------------------------------------------
+// The dictionaries of a program's OP_DICT ops are numbered 0 .. n-1 (enc::encode_program) and every buffer holds kDictSlots words, so a kernel whose program is a
+// compile-time constant copies them into LDS once (stage_dicts) and decodes with ds_read_b64: the decode leaves the VMEM queue, where an in-order vmcnt wait for a
+// gather would also wait for every column load issued before it.  A program without OP_DICT never instantiates dict_lds and allocates nothing.
+__host__ __device__ constexpr int dict_count(const Shape& s) {
+  int n = 0;
+  for (int pc = 0; pc < s.n_ops; pc++) if (s.ops[pc].code == OP_DICT && s.ops[pc].c < kMaxDicts && s.ops[pc].c + 1 > n) n = s.ops[pc].c + 1;
+  return n;
+}
+template <int ND>
+__device__ __forceinline__ unsigned long long* dict_lds() {
+  __shared__ unsigned long long d[ND * kDictSlots];
+  return d;
+}
+// called by the whole workgroup (kBlock threads: one word per thread and dictionary); a barrier must follow before the first OP_DICT
+template <int ND>
+__device__ __forceinline__ void stage_dicts(const Args& args) {
+  static_assert(kDictSlots == kBlock, "one dictionary word per thread");
+  unsigned long long* d = dict_lds<ND>();
+  unsigned long long w[ND];
+#pragma unroll
+  for (int j = 0; j < ND; j++) w[j] = args.dict[j][threadIdx.x];
+#pragma unroll
+  for (int j = 0; j < ND; j++) d[j * kDictSlots + threadIdx.x] = w[j];
+}
+
 // ---- one program step ---------------------------------------------------------------
-template <bool FULL, class RF>
+// ND > 0: OP_DICT reads the workgroup's LDS copy of the ND dictionaries (stage_dicts), else args.dict in HBM.  TRUST_NULLABLE: OP_LOAD of an input the shape
+// declares non-nullable does not look for a bitmap (load_input)
+template <bool FULL, int ND = 0, bool TRUST_NULLABLE = false, class RF>
 __device__ __forceinline__ void exec_op(const Op op, const Shape& sh, const Args& args, int pc, int64_t row0, RF& rf) {
   uint64_t a[kRows], b[kRows], d[kRows];
   uint32_t va = (1u << kRows) - 1, vb = (1u << kRows) - 1, vd;
   if (op.code == OP_LOAD) {
-    load_input<FULL>(args.in[op.a], sh.in_dtype[op.a], row0, args.n_rows, d, vd);
+    load_input<FULL>(args.in[op.a], sh.in_dtype[op.a], row0, args.n_rows, d, vd, !TRUST_NULLABLE || sh.in_nullable[op.a] != 0);
   } else if (op.code == OP_CONST) {
 #pragma unroll
     for (int r = 0; r < kRows; r++) d[r] = args.imm[pc];
@@ -333,9 +363,15 @@ __device__ __forceinline__ void exec_op(const Op op, const Shape& sh, const Args
         vd = (t & va) | (~t & vb);
       } break;
       case OP_DICT: {   // a per-lane gather from a 2 KB table: a wave's lanes land on the few lines that hold the dictionary's live entries
-        const unsigned long long* dict = args.dict[op.c < kMaxDicts ? op.c : 0];
+        if constexpr (ND > 0) {
+          const unsigned long long* dict = dict_lds<ND>() + (op.c < ND ? op.c : 0) * kDictSlots;
 #pragma unroll
-        for (int r = 0; r < kRows; r++) d[r] = dict[a[r] & (uint64_t)(kDictSlots - 1)];
+          for (int r = 0; r < kRows; r++) d[r] = dict[a[r] & (uint64_t)(kDictSlots - 1)];
+        } else {
+          const unsigned long long* dict = args.dict[op.c < kMaxDicts ? op.c : 0];
+#pragma unroll
+          for (int r = 0; r < kRows; r++) d[r] = dict[a[r] & (uint64_t)(kDictSlots - 1)];
+        }
         vd = va;
       } break;
       default:  // OP_MOV / OP_NOP
@@ -358,12 +394,12 @@ template <int ID> struct StatProg {
   static constexpr Shape shape() { return static_shape(ID); }
 };
 
-template <class P, bool FULL, class RF>
+template <class P, bool FULL, int ND = 0, bool TRUST_NULLABLE = false, class RF>
 __device__ __forceinline__ void run_program(const Shape& dsh, const Args& args, int64_t row0, RF& rf) {
   if constexpr (P::kStatic) {
     constexpr Shape sh = P::shape();
 #pragma unroll
-    for (int pc = 0; pc < sh.n_ops; pc++) exec_op<FULL>(sh.ops[pc], sh, args, pc, row0, rf);
+    for (int pc = 0; pc < sh.n_ops; pc++) exec_op<FULL, ND, TRUST_NULLABLE>(sh.ops[pc], sh, args, pc, row0, rf);
   } else {
     // generic interpreter: all column loads in flight first, then widen + store into the LDS slots, then the ops
     Prefetched pf;
@@ -383,6 +419,22 @@ __host__ __device__ constexpr int leading_loads(const Shape& s) {
   while (n < s.n_ops && s.ops[n].code == OP_LOAD) n++;
   return n;
 }
+// Rows of at most 16 bytes (TPC-H Q1 over its encoded shadows: 15): such a program issues many one- and two-byte loads per tile, and what sits between them
+// shows.  fused_scan_body compiles the bitmap test out of the loads of its non-nullable inputs for these shapes only; wider rows keep their code as it was.
+__host__ __device__ constexpr int shape_row_bytes(const Shape& s) {
+  int b = 0;
+  for (int i = 0; i < s.n_inputs; i++) {
+    switch (s.in_dtype[i]) {
+      case PLX_I8: case PLX_U8: b += 1; break;
+      case PLX_I16: case PLX_U16: b += 2; break;
+      case PLX_I32: case PLX_U32: case PLX_F32: b += 4; break;
+      case PLX_BOOL: break;      // bit-packed
+      default: b += 8; break;
+    }
+  }
+  return b;
+}
+__host__ __device__ constexpr bool narrow_rows(const Shape& s) { return s.n_inputs > 0 && shape_row_bytes(s) <= 16; }
 template <class P, class RF>
 __device__ __forceinline__ void run_loads_full(const Args& args, int64_t row0, RF& rf) {
   constexpr Shape sh = P::shape();
@@ -531,14 +583,14 @@ __device__ __forceinline__ void atomic_row(const S& sh, const RF& rf, int r, int
 }
 
 // ---- the scan kernels ------------------------------------------------------------------
-template <class P, class RF>
+template <class P, int ND = 0, bool TRUST_NULLABLE = false, class RF>
 __device__ __forceinline__ bool tile_rows(const Shape& dsh, const Args& args, int64_t tile, RF& rf, bool pass[kRows], int64_t& row0) {
   const int lane = lane_id();
   const int64_t base = tile * kTileRows;
   row0 = base + (int64_t)lane * kRows;
   const bool full = base + kTileRows <= args.n_rows;  // wave-uniform
-  if (full) run_program<P, true>(dsh, args, row0, rf);
-  else run_program<P, false>(dsh, args, row0, rf);
+  if (full) run_program<P, true, ND, TRUST_NULLABLE>(dsh, args, row0, rf);
+  else run_program<P, false, ND, TRUST_NULLABLE>(dsh, args, row0, rf);
   uint8_t pred;
   if constexpr (P::kStatic) { constexpr Shape sh = P::shape(); pred = sh.pred; } else pred = dsh.pred;
 #pragma unroll

@@ -550,6 +550,12 @@ __host__ __device__ constexpr bool late_probe() {
   if constexpr (P::kStatic && std::is_same<Sink, DirectProbeAggSink>::value) return split_program(P::shape()).any_late;
   else return false;
 }
+// the two aggregate sinks over a compile-time program with narrow rows: the loads of inputs the shape declares non-nullable do not look for a bitmap (load_input)
+template <class P, class Sink>
+__host__ __device__ constexpr bool trust_nullable() {
+  if constexpr (P::kStatic && (std::is_same<Sink, LdsAggSink>::value || std::is_same<Sink, RegAggSink>::value)) return narrow_rows(P::shape());
+  else return false;
+}
 template <class P, class Sink>
 __device__ __forceinline__ void fused_scan_body(const Shape dsh, const Args args, const typename Sink::Params sp) {   // by value: kernel arguments passed by
                                                                                                               // reference become addressable stack copies (spills)
@@ -566,12 +572,16 @@ __device__ __forceinline__ void fused_scan_body(const Shape dsh, const Args args
     }
   } else if constexpr (P::kStatic) {
     constexpr Shape sh = P::shape();
+    constexpr int ND = dict_count(sh);
+    constexpr bool kTrust = trust_nullable<P, Sink>();
+    if constexpr (ND > 0) { stage_dicts<ND>(args); __syncthreads(); }
     sink.init(sh, sp);
     // (two tiles of a wave evaluated together, so that the second tile's bitmap lookups fly while the first waits, were measured on TPC-H Q3's orders scan with the
-    // customer filter: no change -- that scan was bound by the LINES its lookups pull from the L2, which OP_MASKV halves)
+    // customer filter: no change -- that scan was bound by the LINES its lookups pull from the L2, which OP_MASKV halves.  Two and four tiles per iteration were also
+    // measured on the encoded Q1 scan, profiles/encoded_scan_tiles: no gain beyond the run-to-run spread once the dictionaries are in LDS)
     for (int64_t t = wave; t < ntiles; t += nwaves) {
       bool pass[kRows]; int64_t row0;
-      tile_rows<P>(dsh, args, t, rf, pass, row0);
+      tile_rows<P, ND, kTrust>(dsh, args, t, rf, pass, row0);
       sink.consume(sh, rf, pass, row0, sp);
     }
     sink.finish(sh, sp);

@@ -22,6 +22,12 @@
 //     per workgroup -> tiny finish kernel.  No atomics, deterministic.
 //   * dense / hash sinks: device-scope atomics straight into an HBM-resident table
 //     (hardware f64 atomic add on gfx950); see HashAggSink.
+//   * the dictionaries of OP_DICT are staged into LDS at kernel start when the program
+//     is a compile-time constant (fused_device.hpp stage_dicts): the decode is a
+//     ds_read_b64, not a gather in the VMEM queue behind the column loads of the tile.
+//     The aggregate scans over rows of at most 16 bytes also leave the bitmap test out
+//     of the loads of their non-nullable inputs (trust_nullable): the loads of a tile
+//     are then one basic block.
 #include "fused_sinks.hpp"
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
@@ -113,6 +119,10 @@ static int scan_grid(int64_t n_rows, int blocks_per_cu, const char* knob = nullp
   int64_t ntiles = (n_rows + kTileRows - 1) / kTileRows;
   return grid_for(ntiles, kBlock / 64, blocks_per_cu);
 }
+// which ahead-of-time aggregate scans compile the bitmap test out of their non-nullable loads (fused_sinks.hpp trust_nullable): the wide-row kernels are untouched
+static_assert(!trust_nullable<StatProg<SHAPE_Q1>, LdsAggSink>() && !trust_nullable<StatProg<SHAPE_CFG2>, RegAggSink>() && !trust_nullable<StatProg<SHAPE_CFG2_NULLX>, RegAggSink>(),
+              "rows wider than 16 bytes keep their loads as they were");
+static_assert(trust_nullable<StatProg<SHAPE_Q1_ENCODED>, LdsAggSink>() && dict_count(static_shape(SHAPE_Q1_ENCODED)) == 2, "encoded Q1: 15-byte rows, two dictionaries in LDS");
 int64_t scan_waves(int64_t n_rows) { return (int64_t)scan_grid(n_rows, 8) * (kBlock / 64); }
 static uint64_t algo_bytes(const Shape& sh, const Args& args) {
   uint64_t algo = 0;
