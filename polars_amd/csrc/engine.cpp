@@ -1842,8 +1842,9 @@ struct HashBuild {
     }
     const ColumnPtr& bkey = B.cols[bki];
     if (o.start_chained) { bkey->repeats_as_build_key = true; if (!o.chains_allowed) return false; multi = true; }
-    bool resized = false, pbuild_off = false;
-    for (int attempt = 0; attempt < 4; attempt++) {
+    bool resized = false, pbuild_off = false, built = false;
+    std::string retries;       // every attempt that was thrown away, in order: the plan text names them in front of build_how (resized(..)+ windowed-off+ chained+)
+    for (int attempt = 0; attempt < 4 && !built; attempt++) {
       if (multi && !links) links = dev_alloc(sizeof(uint64_t) * (size_t)std::max<int64_t>(B.height, 1));
       // (the sampled count already carries 25 %: x1.6 keeps the load at or below ~0.6 without doubling a table that x2 would push over the next power of two)
       log2_cap = std::max(o.min_log2_cap, ceil_log2_u64((uint64_t)((double)std::max<uint64_t>(nb, 1) * (sized_by_sample ? 1.6 : 2.0))));
@@ -1852,16 +1853,17 @@ struct HashBuild {
       t.slots = keys->as<unsigned long long>(); t.flags = flags->as<unsigned int>(); t.acc = nullptr;
       t.count = flags->as<unsigned long long>() + 1; t.log2_cap = (uint32_t)log2_cap;
       t.links = multi ? links->as<unsigned long long>() : nullptr;
+      t.slow_step_budget = sized_by_sample ? (uint32_t)std::min<uint64_t>(cap, 0x7fffffffu) : 0u;       // (a sampled size has the exact count behind it: give up early)
       JTRACE("build attempt %d multi=%d cap=2^%d nb=%llu", attempt, (int)multi, log2_cap, (unsigned long long)nb);
       // a large build side with (so far) unique keys: partitioned, the table filled window by window from LDS -- no device atomic per row (k::partitioned_join_build)
       t.log2_window = 0;
-      build_how = o.plain_how;
+      build_how = retries + o.plain_how;
       bool pbuilt = false;
       if (!multi && !pbuild_off && partitioned_build_wanted(B.height, log2_cap)) {
         t.log2_window = kJoinWindowLog2;
         std::string bd;
         pbuilt = k::partitioned_join_build(cb.shape, cb.args, find_static_shape(cb.shape), t, o.want_cells ? &cells : nullptr, &bd);
-        if (pbuilt) build_how = bd; else t.log2_window = 0;
+        if (pbuilt) build_how = retries + bd; else t.log2_window = 0;
       }
       if (!pbuilt) {
         PLX_HIP(hipMemsetAsync(keys->ptr, 0xff, sizeof(uint64_t) * 2 * (cap + 1), stream()));
@@ -1871,24 +1873,29 @@ struct HashBuild {
       uint64_t fl64[2] = {0, 0};
       d2h_sync(fl64, flags->ptr, 16);
       const uint32_t dup = (uint32_t)fl64[0], ovf = (uint32_t)(fl64[0] >> 32);
-      if (dup) {                                       // (raised by a build without links only: JoinBuildSink)
+      // A sample that misjudged and duplicate keys can both show in one attempt (a build that overflowed may or may not have met two rows of a key first): both are
+      // acted on at once, and the markers are written in this fixed order, so the plan text does not depend on which of the two the attempt happened to notice.
+      bool again = false;
+      // the sample misjudged (on whichever attempt: the multi-value rebuild keeps the sampled size): once more, from the exact count.  Only a sampled size can be wrong:
+      // a table sized from an exact count is at most half full, and an overflow there is a crowded window (below) or an error.
+      if (!resized && sized_by_sample && (ovf || fl64[1] * 10 > cap * 7)) {
+        retries += std::string("resized(") + (ovf ? "overflow" : "load") + ",from=2^" + std::to_string(log2_cap) + ")+";
+        nb = ovf ? exact_count() : fl64[1];
+        sized_by_sample = false; resized = true; again = true;
+      }
+      if (dup) {                                       // (raised by a build without links only: JoinBuildSink, join_fill_kernel)
         bkey->repeats_as_build_key = true;
         if (!o.chains_allowed) return false;
-        multi = true;                                  // build once more, chaining the rows of a key (the table's size stays: it was planned for the rows, not the keys)
-        continue;
+        multi = true;                                  // build once more, chaining the rows of a key (the table's size stays unless it was misjudged: it was planned for the rows, not the keys)
+        retries += "chained+"; again = true;
       }
-      // the sample misjudged (on whichever attempt: the multi-value rebuild keeps the sampled size): once more, from the exact count.  (A table sized from an exact count
-      // is at most half full: only a sampled size can be over 0.7.)
-      if (!resized && (ovf || (sized_by_sample && fl64[1] * 10 > cap * 7))) {
-        nb = ovf ? exact_count() : fl64[1];
-        sized_by_sample = false; resized = true;
-        continue;
-      }
-      if (ovf && pbuilt) { pbuild_off = true; continue; }                             // a window filled up although the table is sized right (keys that crowd one window): the plain build probes the whole table
+      if (again) continue;
+      if (ovf && pbuilt) { pbuild_off = true; retries += "windowed-off+"; continue; }   // a window filled up although the table is sized right (keys that crowd one window): the plain build probes the whole table
       PLX_REQUIRE(!ovf, PLX_ERR_OOM, "join build: probe sequence overflow");
       nb = fl64[1];                                                                   // exact from here on
-      break;
+      built = true;
     }
+    PLX_REQUIRE(built, PLX_ERR_OOM, "join build: no finished table after four attempts (" + retries + ")");
     return true;
   }
 };

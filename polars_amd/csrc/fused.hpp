@@ -504,7 +504,7 @@ struct JoinAggTable {
   // [cap + 1] slots of 16 bytes: {key, build row (low 32 bits of the second word)}.  Key and row share a line: an insert is ONE line across the fabric (the CAS on the
   // key; the row store merges into the line the CAS just brought in), and so is a probe.  Slot `cap` = the key whose bits equal kEmptyKey (present iff its row is set).
   unsigned long long* slots;
-  unsigned int* flags;    // [0] = duplicate build key seen, [1] = probe sequence overflow
+  unsigned int* flags;    // [0] = duplicate build key seen, [1] = probe sequence overflow, [4] = slow steps of the build (slow_step_budget; the count sits in [2..3])
   unsigned long long* acc;
   uint32_t log2_cap;
   unsigned long long* count;   // build: [0] += rows inserted (null: not wanted) -- the build side's row count after its predicate, a by-product of the build scan
@@ -519,6 +519,11 @@ struct JoinAggTable {
   // A windowed table numbers its keys densely: the high 32 bits of a slot's second word hold the key's CELL index (jt_cell), so `acc` is [keys + 1][n_aggs] instead of
   // [cap + 1][n_aggs] -- less than half the cells to initialise and to stream through at the output step.
   uint32_t log2_window;
+  // Build into a table that was sized from a SAMPLE (0: sized from an exact count): a row's every 64th probe adds one to flags[4], and the row that brings the sum to
+  // this budget raises flags[1].  A sample that saw none of the rows that pass gives a table of a few thousand slots for millions of rows: it is full before the rows
+  // resident on the device have finished their first probes, and without the budget each of them walks the whole table before the first one can raise the flag.  A table
+  // at the load it was planned for stays orders of magnitude below the budget (one step per slot = 64 wasted probes per slot).
+  uint32_t slow_step_budget;
 };
 PLX_HD inline uint64_t jt_next(const JoinAggTable& t, uint64_t slot) {
   const uint64_t wmask = (1ull << (t.log2_window ? t.log2_window : t.log2_cap)) - 1ull;

@@ -318,8 +318,20 @@ struct JoinBuildSink {
     const uint64_t w = wave_sum_u64(n);
     if (lane_id() == 0 && w) atomicAdd(p.count, (unsigned long long)w);
   }
+  // flags[1] (probe sequence overflow) as another wave may just have raised it: the table is thrown away then, and a row on a long probe sequence stops looking.
+  // Read on the slow path only (every 8th probe of a row: a row that finds its slot within 7 probes never reads it), past the caches -- the waves that raise it and
+  // the waves that poll it run on different compute units.  (Every 64th probe: 2.6e6 rows left after the flag went up still spent 64 probes each, 3 ms.)
+  // Also the slow step of a sampled table (JoinAggTable::slow_step_budget).  true: give the row up.
+  static __device__ __forceinline__ bool overflow_raised(const Params& p, uint32_t probe) {
+    if (__hip_atomic_load(&p.flags[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return true;
+    if ((probe & 63u) == 63u && p.slow_step_budget && atomicAdd(&p.flags[4], 1u) >= p.slow_step_budget) { p.flags[1] = 1u; return true; }
+    return false;
+  }
   template <class S, class RF> __device__ __forceinline__ void consume(const S& sh, const RF& rf, const bool pass[kRows], int64_t row0, const Params& p) {
     const uint64_t cap = 1ull << p.log2_cap;
+    // a probe sequence that has been round its window (the whole table: log2_window 0) has seen every slot of it; 2^16 probes bound the sequence in a larger one.
+    // (wave-uniform: scalar arithmetic on the kernel's arguments)
+    const uint32_t log2_round = p.log2_window ? p.log2_window : p.log2_cap, probe_limit = 1u << (log2_round < 16u ? log2_round : 16u);
 #pragma unroll
     for (int r = 0; r < kRows; r++) {
       if (!pass[r] || !((rf.getv(sh.key) >> r) & 1)) continue;  // null keys never match
@@ -345,7 +357,8 @@ struct JoinBuildSink {
             break;
           }
           slot = jt_next(p, slot);
-          if (probe > (1u << 16)) { p.flags[1] = 1u; break; }
+          if (probe >= probe_limit) { p.flags[1] = 1u; break; }
+          if ((probe & 7u) == 7u && overflow_raised(p, probe)) break;
         }
         continue;
       }
@@ -356,7 +369,8 @@ struct JoinBuildSink {
         if (old == kEmptyKey) { *jt_row(p, slot) = (unsigned int)(row0 + r); break; }
         if (old == key) { p.flags[0] = 1u; break; }
         slot = jt_next(p, slot);
-        if (probe > (1u << 16)) { p.flags[1] = 1u; break; }
+        if (probe >= probe_limit) { p.flags[1] = 1u; break; }
+        if ((probe & 7u) == 7u && overflow_raised(p, probe)) break;
       }
     }
   }

@@ -979,23 +979,32 @@ __global__ __launch_bounds__(kFillBlock) void join_fill_kernel(const ulonglong2*
   unsigned long long* lkeys = fill_lds;            // [W]
   unsigned long long* lvals = fill_lds + W;        // [W] {row, cell index << 32}
   __shared__ unsigned int s_count;
-  const uint64_t w = blockIdx.x;
+  // A window of the bin kernel overflowed (flags[1] is final: the bin kernel has finished): the caller throws the table away whatever is in it, and filling windows
+  // to the last slot is the slowest fill there is -- nothing is filled then.  One read per workgroup (other workgroups of this kernel raise the flag too, and the
+  // barriers need the whole workgroup on one side), in flight while the LDS image is initialised and looked at behind the barrier that follows it.
+  __shared__ unsigned int s_overflowed;
+  if (threadIdx.x == 0) s_overflowed = __hip_atomic_load(&t.flags[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const uint64_t w = blockIdx.x, cap = 1ull << t.log2_cap;
   const uint32_t n = min(uniform_ld(win_fill, w), W);
   const uint64_t cell0 = uniform_ld(win_base, w);  // cells are numbered in record order: window by window
+  // cell_key / cell_row hold cap + 1 entries, and cell0 / total are sums of the UNCLAMPED window counters (every pair the bin kernel saw): on a table that a sample
+  // sized too small they run past cap.  No index above cap is written.  total > cap means that some window counted more than W pairs, so the bin kernel has already
+  // raised flags[1] and the caller throws this table and its cells away; when total <= cap every cell0 + i is below total and nothing is skipped.
   for (uint32_t i = threadIdx.x; i < W; i += blockDim.x) { lkeys[i] = kEmptyKey; lvals[i] = ~0ull; }
   if (threadIdx.x == 0) s_count = 0;
   if (w == 0 && threadIdx.x == 0) {                // the key equal to the EMPTY pattern (slot `cap`): the cell behind every window's
     const uint64_t total = win_base[1ull << (t.log2_cap - t.log2_window)];
     jt_row(t, 1ull << t.log2_cap)[1] = (unsigned int)total;
-    if (cell_key) { cell_key[total] = kEmptyKey; cell_row[total] = *jt_row(t, 1ull << t.log2_cap); }
+    if (cell_key && total <= cap) { cell_key[total] = kEmptyKey; cell_row[total] = *jt_row(t, cap); }
   }
   __syncthreads();
+  if (s_overflowed != 0u) return;
   unsigned int mine = 0;
   const ulonglong2* in = recs + (w << t.log2_window);
   for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
     const ulonglong2 rec = in[i];
     const unsigned long long key = rec.x;
-    if (cell_key) { cell_key[cell0 + i] = key; cell_row[cell0 + i] = (unsigned int)rec.y; }
+    if (cell_key && cell0 + i <= cap) { cell_key[cell0 + i] = key; cell_row[cell0 + i] = (unsigned int)rec.y; }
     uint32_t ls = (uint32_t)((key * kP2HashMult) >> (64 - t.log2_cap)) & (W - 1);
     for (uint32_t probe = 0;; probe++) {
       const unsigned long long old = atomicCAS(&lkeys[ls], (unsigned long long)kEmptyKey, key);
@@ -1046,7 +1055,8 @@ bool partitioned_join_build(const Shape& sh, const Args& args, int static_id, co
   }
   exclusive_scan_u32(win_fill->as<uint32_t>(), win_base->as<uint64_t>(), (int64_t)NW);       // win_base[NW] = records in all windows
   if (cells) {
-    // (at most one record per row that passed; the table was sized for them: cap slots bound the cells whatever the count turns out to be)
+    // (one cell per row that passed, cap + 1 entries: enough whenever the table is kept.  A sampled size can be too small for the rows that pass; join_fill_kernel
+    // writes no cell above cap, and such a build has flags[1] up -- the caller builds again from the exact count)
     cells->key = dev_alloc(sizeof(uint64_t) * (((size_t)1 << t.log2_cap) + 1));
     cells->row = dev_alloc(sizeof(uint32_t) * (((size_t)1 << t.log2_cap) + 1));
   }
