@@ -347,8 +347,12 @@ typedef enum plx_aexpr_kind {
   PLX_AE_IS_NULL = 8,     /* lhs -> Boolean, never null (FunctionExpr::Boolean(IsNull)) */
   PLX_AE_IS_NOT_NULL = 9, /* lhs -> Boolean, never null */
   PLX_AE_FILL_NULL = 10,  /* lhs, rhs = non-null literal of the same dtype (fill_null(literal)); inside fused pipelines only */
-  PLX_AE_TERNARY = 11     /* when(cond).then(lhs).otherwise(rhs): cond Boolean, lhs / rhs of one dtype (type coercion casts upstream).  A row takes lhs where cond is
+  PLX_AE_TERNARY = 11,    /* when(cond).then(lhs).otherwise(rhs): cond Boolean, lhs / rhs of one dtype (type coercion casts upstream).  A row takes lhs where cond is
                            * valid and true and rhs everywhere else (a null cond selects rhs); value and validity are those of the chosen side.  Output name: that of lhs */
+  PLX_AE_BITMAP_LOOKUP = 12 /* lhs = an integer expression, lit.u = a plx_column of dtype PLX_BOOL without nulls (the lookup bitmap; the caller keeps the handle alive until
+                           * the plan has run).  Result: Boolean, bit `value` of the bitmap, false outside [0, len(bitmap)), null where lhs is null: set membership over a
+                           * dense code range.  Fused pipelines test the bit inside their scan (at most 2 bitmaps per program, semi-join membership bitmaps included; a
+                           * plan that needs more runs per node), the per-node path with plx_bitmap_lookup's kernel.  Output name: that of lhs */
 } plx_aexpr_kind;
 
 /* polars_plan::dsl::Operator subset */
@@ -365,7 +369,7 @@ typedef struct plx_aexpr {
   int32_t rhs;  /* arena index of the right input, -1 if none */
   int32_t dtype; /* literal dtype / cast target (plx_dtype) */
   int32_t is_null; /* literal is NULL */
-  plx_scalar lit;
+  plx_scalar lit;   /* PLX_AE_LITERAL: the value; PLX_AE_BITMAP_LOOKUP: lit.u = the lookup bitmap's plx_column handle; read for those kinds only */
   const char* name; /* column name / alias */
   int32_t cond;     /* PLX_AE_TERNARY: arena index of the predicate; read for that kind only (appended last: arenas of earlier callers never carry the kind) */
 } plx_aexpr;
@@ -545,6 +549,29 @@ int plx_strview_stamp_nulls(plx_column views_u64_pairs, plx_column valid_bool);
  * as in the reference (a null is a key: hash_keys.rs:413-452 keeps the validity in the key): that group's code is null, its dictionary entry empty.  Returns PLX_ERR_UNSUPPORTED when the input is outside the fast path (a
  * string longer than 12 bytes, more distinct strings than the LDS tables hold, fewer than ~4096 of them): the caller then encodes (plx_strview_dict_encode_device) and groups on the codes. */
 int plx_strview_groupby(plx_column views_u64_pairs, plx_column value, plx_column* out_codes, plx_strdict* out_dict, plx_column* out_sum, plx_column* out_count, plx_column* out_len);
+/* ---- string predicates: str.starts_with / ends_with / contains(literal) -------------------------------
+ * The pattern is `pattern_len` bytes (the UTF-8 bytes of a string, or any bytes for binary data) of at most PLX_STR_MATCH_MAX_PATTERN = 64; a longer one is
+ * PLX_ERR_UNSUPPORTED.  Comparison is byte-wise, a zero byte is an ordinary byte, the view's length word decides where a string ends.  A string shorter than the
+ * pattern never matches; the empty pattern matches every non-null string.
+ *   plx_strdict_match      the predicate for each of the dictionary's n_strings entries, in code order: a PLX_BOOL column without nulls, decided on the device (the
+ *                          dictionary is not downloaded).  Together with plx_bitmap_lookup / PLX_AE_BITMAP_LOOKUP over the code column this is the predicate on a
+ *                          dictionary-encoded string column: one decision per distinct string, one bit lookup per row.
+ *   plx_strview_match      the predicate for each of n raw views in HBM (views_u64_pairs: PLX_U64, 2 n words; data_u8: the bytes behind views over 12 bytes -- buffer
+ *                          index 0 -- or 0): a PLX_BOOL column of n rows, null where the view is a null stamp (length word 0xFFFFFFFF).  The column is not encoded.
+ *                          A validity bitmap with nulls on views_u64_pairs itself is PLX_ERR_INVALID (it would count words, not views): stamp the nulls.
+ *                          A view that points outside data_u8 is PLX_ERR_INVALID ("a view points outside its buffer"), a decision that needs bytes with data_u8 = 0
+ *                          is PLX_ERR_INVALID ("needs the data buffer"); the kernel reads nothing out of bounds either way.  Strings of <= 12 bytes, and starts_with
+ *                          of <= 4 bytes on any string, are decided from the views alone.
+ *   plx_strview_match_host the same decision function on the CPU over host memory (views: n x 16 bytes, data / data_len may be NULL / 0; out_bits / out_valid:
+ *                          ceil(n / 64) words each, bits past n zero).  Needs no GPU and no plx_init.
+ *   plx_bitmap_lookup      out[i] = lut[codes[i]] for an integer code column (false outside [0, len(lut))); the validity is the codes'.  lut: PLX_BOOL without nulls. */
+#define PLX_STR_MATCH_MAX_PATTERN 64
+typedef enum plx_str_match_kind { PLX_STR_STARTS_WITH = 0, PLX_STR_ENDS_WITH = 1, PLX_STR_CONTAINS = 2 } plx_str_match_kind;
+int plx_strdict_match(plx_strdict dict, int32_t kind, const uint8_t* pattern, int64_t pattern_len, plx_column* out_bool);
+int plx_strview_match(plx_column views_u64_pairs, plx_column data_u8, int32_t kind, const uint8_t* pattern, int64_t pattern_len, plx_column* out_bool);
+int plx_strview_match_host(const void* views, const uint8_t* data, int64_t data_len, int64_t n, int32_t kind, const uint8_t* pattern, int64_t pattern_len,
+                           uint64_t* out_bits, uint64_t* out_valid);
+int plx_bitmap_lookup(plx_column codes, plx_column lut_bool, plx_column* out_bool);
 int plx_strdict_info(plx_strdict dict, int64_t* n_strings, int64_t* total_bytes);
 int plx_strdict_to_host(plx_strdict dict, int64_t* offsets, uint8_t* bytes);
 int plx_strdict_free(plx_strdict dict);

@@ -18,6 +18,7 @@
 #include "ops.hpp"
 #include "scan.hpp"
 #include "sort.hpp"
+#include "strmatch.hpp"
 
 namespace plx {
 void init_device(int ordinal);
@@ -1101,6 +1102,88 @@ int plx_strview_stamp_nulls(plx_column views_u64_pairs, plx_column valid_bool) {
   PLX_HIP(hipStreamSynchronize(stream()));      // (`eff` may be a temporary)
   PLX_CATCH
 }
+// ---- string predicates (kernels_strmatch.hip, strmatch.hpp) ------------------------------------------------------
+extern "C++" {
+namespace {
+void check_match_args(int32_t kind, const uint8_t* pattern, int64_t pattern_len) {
+  PLX_REQUIRE(kind >= PLX_STR_STARTS_WITH && kind <= PLX_STR_CONTAINS, PLX_ERR_INVALID, "string match: kind outside 0..2 (plx_str_match_kind)");
+  PLX_REQUIRE(pattern_len >= 0 && (pattern || pattern_len == 0), PLX_ERR_INVALID, "string match: bad pattern");
+  PLX_REQUIRE(pattern_len <= PLX_STR_MATCH_MAX_PATTERN, PLX_ERR_UNSUPPORTED,
+              "string match: a pattern of " + std::to_string(pattern_len) + " bytes; patterns of more than " + std::to_string(PLX_STR_MATCH_MAX_PATTERN) + " bytes are not on this path");
+}
+void check_match_flags(uint32_t flags) {
+  PLX_REQUIRE(!(flags & strmatch::kFlagOutside), PLX_ERR_INVALID, "string match: a view points outside its buffer");
+  PLX_REQUIRE(!(flags & strmatch::kFlagNoData), PLX_ERR_INVALID, "string match: a string of more than 12 bytes needs the data buffer for this predicate, and none was given");
+}
+ColumnPtr bool_column(int64_t n, Buf values, Buf validity, int64_t null_count) {
+  auto c = std::make_shared<Column>();
+  c->dtype = PLX_BOOL; c->len = n; c->values = std::move(values); c->validity = std::move(validity); c->null_count = null_count;
+  return c;
+}
+}  // namespace
+}  // extern "C++"
+static_assert(PLX_STR_MATCH_MAX_PATTERN == strmatch::kMaxPattern && PLX_STR_STARTS_WITH == strmatch::kStartsWith && PLX_STR_ENDS_WITH == strmatch::kEndsWith && PLX_STR_CONTAINS == strmatch::kContains,
+              "polars_amd.h and strmatch.hpp disagree");
+
+int plx_strdict_match(plx_strdict dict, int32_t kind, const uint8_t* pattern, int64_t pattern_len, plx_column* out_bool) {
+  PLX_TRY
+  PLX_REQUIRE(out_bool, PLX_ERR_INVALID, "null pointer");
+  check_match_args(kind, pattern, pattern_len);
+  StrDict& d = get_strdict(dict);
+  device();
+  Buf bits = dev_alloc(bitmap_bytes(d.n)), valid = dev_alloc(bitmap_bytes(d.n));
+  // the dictionary's views carry the absolute offset of a long string in their second word (StrEncode::dict_views), not {buffer, offset}
+  const uint32_t flags = k::strview_match(d.views->as<uint64_t>(), nullptr, false, d.data ? d.data->as<uint8_t>() : nullptr, d.data ? (uint64_t)d.data->bytes : 0, /*rebased=*/true, d.n,
+                                          kind, pattern, pattern_len, bits->as<uint64_t>(), valid->as<uint64_t>());
+  check_match_flags(flags);
+  *out_bool = register_column(bool_column(d.n, bits, nullptr, 0));
+  PLX_CATCH
+}
+int plx_strview_match(plx_column views_u64_pairs, plx_column data_u8, int32_t kind, const uint8_t* pattern, int64_t pattern_len, plx_column* out_bool) {
+  PLX_TRY
+  PLX_REQUIRE(out_bool, PLX_ERR_INVALID, "null pointer");
+  check_match_args(kind, pattern, pattern_len);
+  ColumnPtr v = get_column(views_u64_pairs);
+  PLX_REQUIRE(v->dtype == PLX_U64 && v->len % 2 == 0, PLX_ERR_INVALID, "views must be a UInt64 column of 2 n words");
+  PLX_REQUIRE(v->values || v->len == 0, PLX_ERR_INVALID, "placeholder column has no data");
+  // a bitmap on the UInt64 column would speak of words, not of views: the nulls of a view column are stamps (plx_strview_stamp_nulls), and nothing else is accepted silently
+  PLX_REQUIRE(!v->validity || column_null_count(v) == 0, PLX_ERR_INVALID, "views column carries a validity bitmap with nulls: the nulls of a raw view column are stamped views (plx_strview_stamp_nulls)");
+  Buf data;
+  uint64_t data_len = 0;
+  if (data_u8) {
+    ColumnPtr d = get_column(data_u8);
+    PLX_REQUIRE(d->dtype == PLX_U8, PLX_ERR_INVALID, "data must be a UInt8 column");
+    PLX_REQUIRE(d->values || d->len == 0, PLX_ERR_INVALID, "placeholder column has no data");
+    data = d->values; data_len = (uint64_t)d->len;
+  }
+  device();
+  const int64_t n = v->len / 2;
+  Buf bits = dev_alloc(bitmap_bytes(n)), valid = dev_alloc(bitmap_bytes(n));
+  const uint32_t flags = k::strview_match(v->values ? v->values->as<uint64_t>() : nullptr, nullptr, /*stamps=*/true, data ? data->as<uint8_t>() : nullptr, data_len, /*rebased=*/false, n,
+                                          kind, pattern, pattern_len, bits->as<uint64_t>(), valid->as<uint64_t>());
+  check_match_flags(flags);
+  const int64_t n_valid = n ? k::bitmap_popcount(valid->as<uint64_t>(), n) : 0;
+  *out_bool = register_column(n_valid == n ? bool_column(n, bits, nullptr, 0) : bool_column(n, bits, valid, n - n_valid));
+  PLX_CATCH
+}
+int plx_strview_match_host(const void* views, const uint8_t* data, int64_t data_len, int64_t n, int32_t kind, const uint8_t* pattern, int64_t pattern_len, uint64_t* out_bits,
+                           uint64_t* out_valid) {
+  PLX_TRY
+  PLX_REQUIRE(n >= 0 && (views || n == 0) && (out_bits && out_valid || n == 0) && data_len >= 0, PLX_ERR_INVALID, "strview_match_host: bad arguments");
+  check_match_args(kind, pattern, pattern_len);
+  const strmatch::Pattern pat = strmatch::make_pattern(pattern, pattern_len);
+  const strmatch::Pool pool{data, data ? (uint64_t)data_len : 0, 0};
+  const uint32_t flags = strmatch::match_views_host(views, pool, n, kind, pat, out_bits, out_valid);
+  check_match_flags(flags);
+  PLX_CATCH
+}
+int plx_bitmap_lookup(plx_column codes, plx_column lut_bool, plx_column* out_bool) {
+  PLX_TRY
+  PLX_REQUIRE(out_bool, PLX_ERR_INVALID, "null pointer");
+  *out_bool = register_column(ops::bitmap_lookup(get_column(codes), get_column(lut_bool)));
+  PLX_CATCH
+}
+
 int plx_strview_groupby(plx_column views_u64_pairs, plx_column value, plx_column* out_codes, plx_strdict* out_dict, plx_column* out_sum, plx_column* out_count, plx_column* out_len) {
   PLX_TRY
   PLX_REQUIRE(out_codes && out_dict && out_sum && out_count && out_len, PLX_ERR_INVALID, "null pointer");

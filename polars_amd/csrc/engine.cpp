@@ -43,6 +43,12 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       e.cond = ae[i].cond;
       PLX_REQUIRE(e.cond >= 0 && e.lhs >= 0 && e.rhs >= 0, PLX_ERR_INVALID, "ternary expression needs a predicate (cond), a then (lhs) and an otherwise (rhs) input");
     }
+    if (e.kind == PLX_AE_BITMAP_LOOKUP) {
+      PLX_REQUIRE(e.lhs >= 0, PLX_ERR_INVALID, "bitmap lookup needs an integer input (lhs)");
+      e.lut = get_column(ae[i].lit.u);
+      PLX_REQUIRE(e.lut->dtype == PLX_BOOL, PLX_ERR_INVALID, "bitmap lookup: the lookup bitmap must be a Boolean column");
+      PLX_REQUIRE(!e.lut->validity || e.lut->null_count == 0 || (e.lut->values && column_null_count(e.lut) == 0), PLX_ERR_INVALID, "bitmap lookup: the lookup bitmap must not hold nulls");
+    }
     PLX_REQUIRE(e.lhs < i && e.rhs < i && e.cond < i, PLX_ERR_INVALID, "AExpr arena must be topologically ordered (children before parents)");
     p.ae.push_back(std::move(e));
   }
@@ -108,6 +114,11 @@ int infer_dtype(const Plan& plan, int e, const Frame& schema) {
     case PLX_AE_CAST: return x.dtype;
     case PLX_AE_NOT: case PLX_AE_IS_NULL: case PLX_AE_IS_NOT_NULL: return PLX_BOOL;
     case PLX_AE_FILL_NULL: return infer_dtype(plan, x.lhs, schema);
+    case PLX_AE_BITMAP_LOOKUP: {
+      const int in = infer_dtype(plan, x.lhs, schema);
+      PLX_REQUIRE(dtype_is_int(in), PLX_ERR_INVALID, std::string("bitmap lookup: the input must be an integer expression, not ") + dtype_name(in));
+      return PLX_BOOL;
+    }
     case PLX_AE_TERNARY: {
       const int l = infer_dtype(plan, x.lhs, schema), r = infer_dtype(plan, x.rhs, schema);
       PLX_REQUIRE(infer_dtype(plan, x.cond, schema) == PLX_BOOL, PLX_ERR_INVALID, "when/then/otherwise: the predicate must be Boolean");
@@ -208,6 +219,10 @@ static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<i
       PLX_REQUIRE(l.kind == PLX_AE_LITERAL && !l.is_null, PLX_ERR_UNSUPPORTED, "fill_null with a non-literal value");
       PLX_REQUIRE(l.dtype == c.col->dtype, PLX_ERR_INVALID, std::string("fill_null literal dtype ") + dtype_name(l.dtype) + " differs from the column's " + dtype_name(c.col->dtype));
       return {ops::fill_null(c.col, l.lit), c.scalar};
+    }
+    case PLX_AE_BITMAP_LOOKUP: {
+      Evaluated c = eval(plan, x.lhs, df, overrides);
+      return {ops::bitmap_lookup(c.col, x.lut), c.scalar};
     }
     case PLX_AE_TERNARY: {
       // a length-1 operand broadcasts inside the kernel (select_kernel's scalar forms); all three scalar: a scalar
@@ -315,6 +330,19 @@ class Compiler {
   int mask_valid(int a, int m) { DNode n; n.code = OP_MASKV; n.a = a; n.b = m; n.ty = nodes[a].ty; n.nullable = true; return add(n); }
   // when(p).then(a).otherwise(b) (OP_SELECT): the chosen side's value and validity
   int select(int p, int a, int b, char ty) { DNode n; n.code = OP_SELECT; n.a = a; n.b = b; n.p = p; n.ty = ty; n.nullable = nodes[a].nullable || nodes[b].nullable; return add(n); }
+  // Lookup bitmaps of one program (args.lut, kMaxLuts of them), one numbering: indices below lut_base belong to the pipeline that owns this compiler (the membership
+  // bitmaps of its semi joins: it fills them in before its launches and says how many it needs BEFORE anything is lowered); the bitmaps of PLX_AE_BITMAP_LOOKUP nodes
+  // follow from lut_base up, handed out and filled in here -- args travels with the compiler to every launch of its program.
+  int lut_base = 0;
+  std::vector<ColumnPtr> static_luts;
+  int static_lut(const ColumnPtr& col) {
+    for (size_t i = 0; i < static_luts.size(); i++) if (static_luts[i].get() == col.get()) return lut_base + (int)i;
+    const int idx = lut_base + (int)static_luts.size();
+    if (idx >= kMaxLuts) throw Unsupported("the program needs more than " + std::to_string(kMaxLuts) + " lookup bitmaps (kMaxLuts: bitmap lookups and the membership bitmaps of semi joins share them)");
+    static_luts.push_back(col);
+    args.lut[idx] = Lut{col->values ? col->values->as<unsigned long long>() : nullptr, (uint64_t)col->len};
+    return idx;
+  }
   int bit_lookup(int a, int lut, int64_t kmin) { DNode n; n.code = OP_BITLOOKUP; n.a = a; n.b = a; n.c = (uint8_t)lut; n.imm = (uint64_t)kmin; n.ty = 'b'; n.nullable = nodes[a].nullable; return add(n); }
   int col_id(const ColumnPtr& c) {
     for (size_t i = 0; i < cols.size(); i++) if (cols[i].get() == c.get()) return (int)i;
@@ -391,6 +419,12 @@ class Compiler {
         if (dt == PLX_F32) throw Unsupported("f32 fill_null");
         int a = lower(x.lhs);
         return nodes[a].nullable ? ifnull(a, widen_literal(l.dtype, l.lit)) : a;
+      }
+      case PLX_AE_BITMAP_LOOKUP: {
+        const int in = infer_dtype(plan, x.lhs, *df);
+        if (!dtype_is_int(in)) fail(PLX_ERR_INVALID, std::string("bitmap lookup: the input must be an integer expression, not ") + dtype_name(in));
+        const int a = lower(x.lhs);
+        return bit_lookup(a, static_lut(x.lut), 0);
       }
       case PLX_AE_TERNARY: {
         const int dt = infer_dtype(plan, e, *df);      // (fails when the branches differ in dtype or the predicate is not Boolean)
@@ -2028,6 +2062,9 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
       }
       return p;
     };
+    cnt.lut_base = cb.lut_base = (int)bsemis.size();
+    cp.lut_base = cs.lut_base = (int)(bsemis.size() + psemis.size());
+    ca.lut_base = (int)psemis.size() + 1;
     cnt.pred = and_preds(cnt, bpreds, bsemis, 0);
     const int bk_cnt = cnt.load(bki);
     cnt.add_agg(cnt.nodes[bk_cnt].nullable ? AGG_COUNT : AGG_LEN, cnt.nodes[bk_cnt].nullable ? bk_cnt : -1);
@@ -2356,6 +2393,7 @@ static bool fused_filter_frame(Plan& plan, const std::vector<int>& preds, const 
                                const MemberTest* member = nullptr) {
   Compiler c(plan, *src);
   try {
+    c.lut_base = member ? 1 : 0;
     int p = and_predicates(c, preds);
     if (member) {
       const int kn = c.load(member->key_col);

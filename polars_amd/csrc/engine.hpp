@@ -26,6 +26,7 @@ struct AE {
   int cond = -1;   // PLX_AE_TERNARY: the predicate (lhs = then, rhs = otherwise)
   plx_scalar lit{};
   std::string name;
+  ColumnPtr lut;   // PLX_AE_BITMAP_LOOKUP: the lookup bitmap (the column behind the handle in lit.u, held for the life of the plan)
 };
 struct IRN {
   int kind = 0, input = -1, input_right = -1, predicate = -1;

@@ -80,6 +80,18 @@ void datagen_id_views(int64_t n, uint64_t seed, uint32_t stream, int64_t lo, int
 // 20-byte strings "id%010d-longkey": views {20, prefix, buffer 0, offset} into out_pool[(hi - lo) * 20], which holds every distinct string once
 void datagen_long_id_views(int64_t n, uint64_t seed, uint32_t stream, int64_t lo, int64_t hi, uint64_t* out_views, uint8_t* out_pool);
 
+// ---- string predicates (kernels_strmatch.hip; the per-string decision: strmatch.hpp) ----------------------
+// str.starts_with (kind 0) / ends_with (1) / contains of a literal (2), decided for n 16-byte views: out_bits = the answers, out_valid = which rows are not null (both
+// sized bitmap_bytes(n); bits past n are zero).  The caller has checked kind and pattern (at most strmatch::kMaxPattern = 64 bytes).  validity (may be null) and / or
+// stamps (a length word of kStrviewNullLen) mark the null rows; no caller passes a bitmap yet -- a dictionary has no nulls, a raw view column carries stamps.
+// data / data_len (may be null / 0): the bytes behind views of more than 12 bytes, ONE buffer; rebased: the second word of such a view is its absolute offset into
+// data (a device dictionary's views), else {buffer index 0, offset}.  No byte outside [data, data + data_len) is read: a view that points outside, or a row that needs
+// bytes when data is null, answers false and sets strmatch::kFlagOutside / kFlagNoData in the returned flags.  Synchronises (the flags).
+uint32_t strview_match(const uint64_t* views, const uint64_t* validity, bool stamps, const uint8_t* data, uint64_t data_len, bool rebased, int64_t n,
+                       int kind, const uint8_t* pattern, int64_t pattern_len, uint64_t* out_bits, uint64_t* out_valid);
+// out bit i = lut bit codes[i] when 0 <= codes[i] < range and row i is valid, else 0 (codes: any integer dtype; out_bits sized bitmap_bytes(n))
+void bitmap_lookup(int dtype, const void* codes, const uint64_t* validity, int64_t n, const uint64_t* lut_bits, uint64_t range, uint64_t* out_bits);
+
 // ---- reductions (kernels_reduce.hip) ------------------------------------------
 struct ReduceResult {
   uint64_t isum;      // wrapping 64-bit sum of sign/zero-extended values (ints)

@@ -362,6 +362,20 @@ plx_scalar scalar_of(const ColumnPtr& c, bool* valid) {
   return s;
 }
 
+// set membership over a dense code range (PLX_AE_BITMAP_LOOKUP per node, plx_bitmap_lookup)
+ColumnPtr bitmap_lookup(const ColumnPtr& codes, const ColumnPtr& lut) {
+  PLX_REQUIRE(dtype_is_int(codes->dtype), PLX_ERR_INVALID, std::string("bitmap lookup: codes must be an integer column, not ") + dtype_name(codes->dtype));
+  PLX_REQUIRE(lut->dtype == PLX_BOOL, PLX_ERR_INVALID, "bitmap lookup: the lookup bitmap must be a Boolean column");
+  PLX_REQUIRE(!lut->validity || column_null_count(lut) == 0, PLX_ERR_INVALID, "bitmap lookup: the lookup bitmap must not hold nulls");
+  PLX_REQUIRE((codes->values || codes->len == 0) && (lut->values || lut->len == 0), PLX_ERR_INVALID, "placeholder column has no data");
+  auto out = std::make_shared<Column>();
+  out->dtype = PLX_BOOL; out->len = codes->len;
+  out->values = dev_alloc(bitmap_bytes(codes->len));
+  k::bitmap_lookup(codes->dtype, codes->data(), codes->valid_words(), codes->len, lut->values ? lut->values->as<uint64_t>() : nullptr, (uint64_t)lut->len, out->values->as<uint64_t>());
+  out->validity = codes->validity; out->null_count = codes->null_count;
+  return out;
+}
+
 // when / then / otherwise per node (reference: TernaryExpr over ChunkZip::zip_with, polars-core/src/chunked_array/ops/zip.rs)
 ColumnPtr if_then_else(const ColumnPtr& mask, const ColumnPtr& a, const ColumnPtr& b) {
   PLX_REQUIRE(mask->dtype == PLX_BOOL, PLX_ERR_INVALID, "if_then_else: the mask must be Boolean");

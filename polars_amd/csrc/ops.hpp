@@ -35,6 +35,9 @@ ColumnPtr fill_null(const ColumnPtr& c, plx_scalar v);                     // va
 // when(mask).then(a).otherwise(b): a where the mask is valid and true, b elsewhere (a null mask row selects b); value and validity of the chosen side.  mask Boolean,
 // a / b of one dtype; a length-1 operand broadcasts.  The result has a validity bitmap only when a side can be null
 ColumnPtr if_then_else(const ColumnPtr& mask, const ColumnPtr& a, const ColumnPtr& b);
+// set membership over a dense code range: out[i] = lut bit codes[i] (false outside [0, len(lut))), null where codes[i] is; codes: any integer dtype (a length-1
+// column stays length 1), lut: Boolean without nulls
+ColumnPtr bitmap_lookup(const ColumnPtr& codes, const ColumnPtr& lut);
 plx_scalar scalar_of(const ColumnPtr& c, bool* valid);         // value and validity of row 0 (a length-1 column), read back to the host
 ColumnPtr concat(const std::vector<ColumnPtr>& chunks);
 ColumnPtr slice_copy(const ColumnPtr& c, int64_t offset, int64_t len);

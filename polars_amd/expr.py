@@ -97,6 +97,11 @@ class Expr:
     def len(self): return Expr("agg", F.AGG_LEN, self)
 
     # -- misc -----------------------------------------------------------------------------
+    @property
+    def str(self) -> "ExprStringNameSpace":
+        """String predicates on a dictionary-encoded (Categorical) column: str.starts_with / ends_with / contains of a literal."""
+        return ExprStringNameSpace(self)
+
     def alias(self, name: str) -> "Expr": return Expr("alias", lhs=self, name=name)
     def cast(self, dtype: T.DataType) -> "Expr": return Expr("cast", lhs=self, dtype=dtype)
 
@@ -110,12 +115,65 @@ class Expr:
         if self.kind == "not": return f"~{self.lhs!r}"
         if self.kind in ("is_null", "is_not_null"): return f"{self.lhs!r}.{self.kind}()"
         if self.kind == "fill_null": return f"{self.lhs!r}.fill_null({self.rhs!r})"
+        if self.kind == "str_match": return f"{self.lhs!r}.str.{STR_MATCH_NAMES[self.op]}({self.value!r})"
         if self.kind == "ternary":
             return f"when({self.cond!r}).then({self.lhs!r})" + (f".otherwise({self.rhs!r})" if self.rhs is not None else "")
         return self.kind
 
     def __bool__(self):
         raise TypeError("the truth value of an Expr is ambiguous; use & / | / ~")
+
+
+STR_MATCH_NAMES = {F.STR_STARTS_WITH: "starts_with", F.STR_ENDS_WITH: "ends_with", F.STR_CONTAINS: "contains"}
+
+
+def str_pattern_bytes(pattern: Any, what: str) -> bytes:
+    """The bytes a string predicate compares with: the UTF-8 bytes of a str, or bytes as they are.  Anything else -- another column, an expression -- is refused:
+    only literal patterns are on this path."""
+    if isinstance(pattern, Expr):
+        if pattern.kind == "lit" and isinstance(pattern.value, (str, bytes)):
+            pattern = pattern.value
+        else:
+            raise TypeError(f"str.{what}: the pattern must be a literal str or bytes; a pattern taken from an expression (another column) is not on this path")
+    if isinstance(pattern, str):
+        return pattern.encode("utf-8")
+    if isinstance(pattern, (bytes, bytearray)):
+        return bytes(pattern)
+    raise TypeError(f"str.{what}: the pattern must be a literal str or bytes, got {type(pattern).__name__}")
+
+
+def str_match_host(kind: int, value, pattern):
+    """The reference semantics on the host, for one string (str or bytes; None stays None): Python's startswith / endswith / in on the UTF-8 bytes."""
+    if value is None:
+        return None
+    b = value.encode("utf-8", errors="surrogateescape") if isinstance(value, str) else bytes(value)
+    p = pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+    return b.startswith(p) if kind == F.STR_STARTS_WITH else b.endswith(p) if kind == F.STR_ENDS_WITH else p in b
+
+
+class ExprStringNameSpace:
+    """pl.col("s").str: the string predicates of py-polars' expr.str that are on the hot path.  The result is an ordinary Boolean expression (null where the
+    string is null): a filter predicate, an operand of ~ & |, the condition of when/then/otherwise, a group key or an output column."""
+
+    def __init__(self, expr: Expr):
+        self._expr = expr
+
+    def _match(self, kind: int, pattern: Any) -> Expr:
+        str_pattern_bytes(pattern, STR_MATCH_NAMES[kind])          # (type check now; the bytes are taken again at lowering)
+        if isinstance(pattern, Expr):
+            pattern = pattern.value
+        return Expr("str_match", op=kind, lhs=self._expr, value=bytes(pattern) if isinstance(pattern, bytearray) else pattern)
+
+    def starts_with(self, prefix: Any) -> Expr:
+        return self._match(F.STR_STARTS_WITH, prefix)
+
+    def ends_with(self, suffix: Any) -> Expr:
+        return self._match(F.STR_ENDS_WITH, suffix)
+
+    def contains(self, pattern: Any, *, literal: bool = True) -> Expr:
+        if not literal:
+            raise TypeError("str.contains(literal=False): regular expressions are not on this path; pass literal=True (the default here) for a substring test")
+        return self._match(F.STR_CONTAINS, pattern)
 
 
 def _as_expr(x: Any) -> Expr:

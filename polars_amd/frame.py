@@ -15,7 +15,7 @@ import numpy as np
 from . import _ffi as F
 from . import datatypes as T
 from . import plan as P
-from .expr import Expr, col as _col
+from .expr import STR_MATCH_NAMES, Expr, col as _col, str_match_host, str_pattern_bytes
 
 
 def _pack_validity(valid: np.ndarray) -> np.ndarray:
@@ -396,8 +396,56 @@ class Series:
     def count(self): return self._reduce(F.AGG_COUNT)
     def len(self): return len(self)
 
+    @property
+    def str(self) -> "SeriesStringNameSpace":
+        """String predicates (starts_with / ends_with / contains of a literal) on a dictionary column or on a column of raw views."""
+        return SeriesStringNameSpace(self)
+
     def __repr__(self) -> str:
         return f"Series({self.name!r}, {self.dtype}, len={len(self)})"
+
+
+class SeriesStringNameSpace:
+    """Series.str: the predicate per row as a Boolean Series, null where the string is null.  A column of raw views (from_device_views(encode="deferred")) is decided
+    view by view on the device (plx_strview_match) and stays a column of views; a dictionary column is decided once per dictionary entry (plx_strdict_match on a device
+    dictionary, in Python on a host list) and every row looks its code up in that bitmap (plx_bitmap_lookup)."""
+
+    def __init__(self, s: "Series"):
+        self._s = s
+
+    def _match(self, kind: int, pattern) -> "Series":
+        s, what = self._s, STR_MATCH_NAMES[kind]
+        pat = str_pattern_bytes(pattern, what)
+        h = C.c_uint64()
+        if s._is_raw_views():
+            views, data = s._raw
+            F.ensure_init()
+            F.check(F.lib().plx_strview_match(views._h, data._h if data is not None else 0, kind, pat, len(pat), C.byref(h)))
+            return Series._from_handle(s.name, h.value, T.Boolean)
+        if not isinstance(s.dtype, T.Categorical):
+            raise TypeError(f"str.{what} needs a string column (dictionary-encoded or raw views), got {s.dtype}")
+        cats = s.dtype.categories
+        if hasattr(cats, "_load") and getattr(cats, "_h", 0) and cats._items is None:
+            F.check(F.lib().plx_strdict_match(cats._h, kind, pat, len(pat), C.byref(h)))
+            lut = Series._from_handle("", h.value, T.Boolean)
+        else:
+            if len(pat) > F.STR_MATCH_MAX_PATTERN:
+                raise F.UnsupportedError(F.ERR_UNSUPPORTED, f"str.{what}: a pattern of {len(pat)} bytes; patterns of more than {F.STR_MATCH_MAX_PATTERN} bytes are not on this path")
+            lut = Series("", np.array([bool(str_match_host(kind, c, pat)) for c in cats], dtype=bool), T.Boolean)
+        out = C.c_uint64()
+        F.check(F.lib().plx_bitmap_lookup(s._h, lut._h, C.byref(out)))
+        return Series._from_handle(s.name, out.value, T.Boolean)
+
+    def starts_with(self, prefix) -> "Series":
+        return self._match(F.STR_STARTS_WITH, prefix)
+
+    def ends_with(self, suffix) -> "Series":
+        return self._match(F.STR_ENDS_WITH, suffix)
+
+    def contains(self, pattern, *, literal: bool = True) -> "Series":
+        if not literal:
+            raise TypeError("str.contains(literal=False): regular expressions are not on this path; pass literal=True (the default here) for a substring test")
+        return self._match(F.STR_CONTAINS, pattern)
 
 
 def logical_arrow(arr, dtype: T.DataType):
@@ -907,6 +955,8 @@ class LazyFrame:
         out = C.c_uint64()
         flags = (F.PLAN_NO_FUSION if no_fusion else 0) | (F.PLAN_NO_DIRECT_JOIN if no_direct_join else 0) | (F.PLAN_NO_PARTITION if no_partition else 0)
         F.check(F.lib().plx_execute_plan(ir, n_ir, ae, n_ae, root, flags, C.byref(out)))
+        if _low.notes:           # what lowering decided before the engine saw the plan: the string predicates and where their bitmaps came from
+            F.set_plan_note("; ".join(_low.notes) + "; " + F.last_plan())
         return DataFrame._from_frame_handle(out.value, schema)
 
     def explain(self) -> str:

@@ -15,7 +15,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 from . import _ffi as F
 from . import datatypes as T
-from .expr import Expr, literal_physical
+from .expr import STR_MATCH_NAMES, Expr, literal_physical, str_match_host, str_pattern_bytes
 
 Schema = Dict[str, T.DataType]
 
@@ -86,10 +86,14 @@ class Lowering:
     def __init__(self):
         self.aexprs: List[dict] = []
         self.irs: List[dict] = []
+        self.luts: List[Any] = []        # lookup bitmaps of the AE_BITMAP_LOOKUP nodes, in order of appearance: host bool arrays (None for one decided on the device)
+        self.lut_columns: List[Any] = [] # ... and their Boolean columns (Series; placeholders without a device), kept alive with the arenas
+        self._lut_memo: Dict[Any, Any] = {}   # (dictionary, kind, pattern) -> its column: the same predicate twice (pred and ~pred of a conditional pair) is one bitmap
+        self.notes: List[str] = []       # what lowering itself decided, for pl.last_plan(): "str.starts_with('PROMO') over 150 categories [device]"
 
     # -- expressions ---------------------------------------------------------------------
     def _push(self, **kw) -> int:
-        node = dict(kind=0, op=0, lhs=-1, rhs=-1, dtype=0, is_null=0, lit=None, name=None, cond=-1)
+        node = dict(kind=0, op=0, lhs=-1, rhs=-1, dtype=0, is_null=0, lit=None, name=None, cond=-1, lut=None)
         node.update(kw)
         self.aexprs.append(node)
         return len(self.aexprs) - 1
@@ -194,6 +198,8 @@ class Lowering:
             return self._lower_binary(e, schema)
         if k == "ternary":
             return self._lower_ternary(e, schema)
+        if k == "str_match":
+            return self._lower_str_match(e, schema)
         raise TypeError(f"unsupported expression {e!r}")
 
     def _lower_string_compare(self, e: Expr, schema: Schema):
@@ -216,6 +222,43 @@ class Lowering:
                 lit = self._lit_node(code, phys)
                 return self._push(kind=F.AE_BINARY, op=e.op, lhs=ci, rhs=lit), T.Boolean
         return None
+
+    def _lower_str_match(self, e: Expr, schema: Schema):
+        """str.starts_with / ends_with / contains(literal) on a Categorical column: the predicate is decided once per dictionary entry -- on the device for a
+        dictionary that lives there (plx_strdict_match: nothing is downloaded), in Python for a host list -- and the rows look their code up in the resulting
+        bitmap (AE_BITMAP_LOOKUP; null code -> null, a code beyond the dictionary -> false)."""
+        from . import frame as _frame
+        what = STR_MATCH_NAMES[e.op]
+        pattern = str_pattern_bytes(e.value, what)
+        ci, cdt = self._lower_maybe_dyn(e.lhs, schema)
+        if isinstance(ci, tuple) or not isinstance(cdt, T.Categorical):
+            raise TypeError(f"str.{what} needs a dictionary-encoded (Categorical) column on this path, got {'a literal' if isinstance(ci, tuple) else cdt}")
+        if len(pattern) > F.STR_MATCH_MAX_PATTERN:
+            raise F.UnsupportedError(F.ERR_UNSUPPORTED, f"str.{what}: a pattern of {len(pattern)} bytes; patterns of more than {F.STR_MATCH_MAX_PATTERN} bytes are not on this path")
+        cats = cdt.categories
+        memo, key = self._lut_memo, (id(cats), e.op, pattern)
+        if key in memo:
+            return self._push(kind=F.AE_BITMAP_LOOKUP, lhs=ci, lut=memo[key]), T.Boolean
+        host = None
+        if hasattr(cats, "_load") and getattr(cats, "_h", 0) and cats._items is None:       # a device dictionary nobody has downloaded
+            h = C.c_uint64()
+            F.check(F.lib().plx_strdict_match(cats._h, e.op, pattern, len(pattern), C.byref(h)))
+            lut, where = _frame.Series._from_handle("", h.value, T.Boolean), "device"
+        else:
+            import numpy as np
+            host = np.array([bool(str_match_host(e.op, c, pattern)) for c in cats], dtype=bool)
+            where = "host"
+            if F._initialised:
+                lut = _frame.Series("", host, T.Boolean)
+            else:                                   # planning without a device (explain, describe_fusion, debug_program on placeholder frames)
+                h = C.c_uint64()
+                F.check(F.lib().plx_column_placeholder(F.BOOL, len(host), 0, 0, 0, 0, C.byref(h)))
+                lut = _frame.Series._from_handle("", h.value, T.Boolean)
+        memo[key] = lut
+        self.luts.append(host)
+        self.lut_columns.append(lut)
+        self.notes.append(f"str.{what}({e.value!r}) over {len(cats)} categories [{where}]")
+        return self._push(kind=F.AE_BITMAP_LOOKUP, lhs=ci, lut=lut), T.Boolean
 
     def _lower_mixed_time_units(self, op: int, li: int, ldt, ri: int, rdt):
         """Datetime column <cmp> Datetime literal of another time unit (a python datetime is "us").  The reference coerces both sides to
@@ -433,6 +476,9 @@ class Lowering:
                     a.lit.u = int(d["lit"]) & 0xFFFFFFFFFFFFFFFF
                 else:
                     a.lit.i = int(d["lit"])
+            if d["kind"] == F.AE_BITMAP_LOOKUP:
+                a.lit.u = d["lut"]._h              # the lookup bitmap's column handle rides in the literal slot (plx_aexpr.lit)
+                keep.append(d["lut"])
             if d["name"] is not None:
                 b = d["name"].encode()
                 keep.append(b)
