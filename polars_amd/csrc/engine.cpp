@@ -7,6 +7,7 @@
 #include <functional>
 #include <memory>
 #include <numeric>
+#include <optional>
 #include <set>
 #include <sstream>
 
@@ -1414,6 +1415,19 @@ static ColumnPtr finalize_column(const FusedAggResult& r, const FinalSpec& fs, F
   j.is_key = 0; j.fs = f; j.out = out->values->ptr; j.out_valid = nullable ? out->validity->as<uint64_t>() : nullptr;
   return out;
 }
+// The end of every fused aggregation: a column per aggregate of `r`, the ONE finalize_batch launch of the result set (the caller has put its key columns into `batch`
+// already; no groups: no launch), then the output expressions over those columns, appended to `frame`.
+static void append_aggregate_columns(const Plan& plan, const FusedAggResult& r, const std::vector<int>& agg_nodes, const std::vector<FinalSpec>& specs, const std::vector<int>& out_exprs, FinBatch& batch, Frame& frame) {
+  std::map<int, ColumnPtr> overrides;
+  for (size_t i = 0; i < agg_nodes.size(); i++) overrides[agg_nodes[i]] = finalize_column(r, specs[i], batch);
+  k::finalize_batch(r.acc->as<uint64_t>(), r.n_aggs, r.n_groups, batch);
+  Frame groups; groups.height = r.n_groups;
+  for (int e : out_exprs) {
+    Evaluated ev = eval(plan, e, groups, &overrides);
+    frame.names.push_back(output_name(plan, e));
+    frame.cols.push_back(broadcast(ev, r.n_groups));      // (a column of r.n_groups rows already, unless the expression is a scalar)
+  }
+}
 
 static ColumnPtr decode_key_column(const FusedAggResult& r, const KeyPart& part, int key_index, FinBatch& batch) {
   const int64_t G = r.n_groups;
@@ -1552,18 +1566,10 @@ static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& pr
   PLX_HIP(hipStreamSynchronize(stream()));
   plan.desc += std::string("FusedFilterAgg{fused_scan[") + jit::program_mode(static_id, c.args.n_rows) + "]+register_sink, inputs=" + std::to_string(c.shape.n_inputs) + ", ops=" + std::to_string(c.shape.n_ops) + ", aggs=" + std::to_string(c.shape.n_aggs) + "}; ";
   if (!sp.note.empty()) plan.encoded += sp.note + "; ";
-  std::map<int, ColumnPtr> overrides;
-  FinBatch batch{};
-  for (size_t i = 0; i < agg_nodes.size(); i++) overrides[agg_nodes[i]] = finalize_column(r, specs[i], batch);
-  k::finalize_batch(r.acc->as<uint64_t>(), r.n_aggs, r.n_groups, batch);
   out = std::make_shared<Frame>();
   out->height = 1;
-  Frame one; one.height = 1;
-  for (int e : node.exprs) {
-    Evaluated ev = eval(plan, e, one, &overrides);
-    out->names.push_back(output_name(plan, e));
-    out->cols.push_back(ev.col);
-  }
+  FinBatch batch{};
+  append_aggregate_columns(plan, r, agg_nodes, specs, node.exprs, batch, *out);
   return true;
 }
 
@@ -1617,15 +1623,7 @@ static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& p
   out->height = r.n_groups;
   FinBatch batch{};
   for (size_t pi = 0; pi < kp.parts.size(); pi++) { out->names.push_back(output_name(plan, kp.parts[pi].expr)); out->cols.push_back(decode_key_column(r, kp.parts[pi], (int)pi, batch)); }
-  std::map<int, ColumnPtr> overrides;
-  for (size_t i = 0; i < agg_nodes.size(); i++) overrides[agg_nodes[i]] = finalize_column(r, specs[i], batch);
-  k::finalize_batch(r.acc->as<uint64_t>(), r.n_aggs, r.n_groups, batch);
-  Frame gframe; gframe.height = r.n_groups;
-  for (int e : node.exprs) {
-    Evaluated ev = eval(plan, e, gframe, &overrides);
-    out->names.push_back(output_name(plan, e));
-    out->cols.push_back(broadcast(ev, r.n_groups));
-  }
+  append_aggregate_columns(plan, r, agg_nodes, specs, node.exprs, batch, *out);
   if (node.maintain_order && r.n_groups > 1) {
     ColumnPtr perm = first_row_permutation(r, first_idx);
     for (auto& col : out->cols) col = ops::gather(col, perm);
@@ -1679,6 +1677,17 @@ static const char* join_takes_per_node_route(const IRN& jn) {
   if (jn.how == PLX_JOIN_FULL || jn.how == PLX_JOIN_RIGHT) return "full and right joins take the per-node route";
   if (jn.coalesce == 2) return "coalesce=false (both key columns kept) takes the per-node route";
   return nullptr;
+}
+// What every fused join pipeline checks first: the join is not the per-node route's, the caller has no reason of its own against it (`own`, or null), it has one key pair and
+// is of a kind the pipeline runs (semi_anti: semi / anti; else inner / left), and both keys are plain columns.  The reason, or null and the two keys.
+static const char* single_key_join(const Plan& plan, const IRN& jn, bool semi_anti, const char* own, const AE*& lkx, const AE*& rkx) {
+  if (const char* per_node = join_takes_per_node_route(jn)) return per_node;
+  if (own) return own;
+  const bool kind = semi_anti ? jn.how == PLX_JOIN_SEMI || jn.how == PLX_JOIN_ANTI : jn.how == PLX_JOIN_INNER || jn.how == PLX_JOIN_LEFT;
+  if (!kind || jn.keys.size() != 1 || jn.keys_right.size() != 1) return semi_anti ? "not a single-key semi or anti join" : "not a single-key inner or left join";
+  lkx = plain_column(plan, jn.keys[0]);
+  rkx = plain_column(plan, jn.keys_right[0]);
+  return lkx && rkx ? nullptr : "join keys are expressions";
 }
 static int resolve_join_side(const Plan& plan, int node, std::set<std::string> used, std::vector<int>& preds, std::vector<SemiFilter>& semis, std::string* why) {
   auto no = [&](const char* m) { if (why) *why = m; return -1; };
@@ -1960,21 +1969,111 @@ template <class Launch> static std::vector<ColumnPtr> probe_gathered(const Compi
 }
 }  // namespace
 
-static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::string* why, std::vector<Shape>* shapes_out = nullptr, bool compile_only = false) {
+// ------------------------------------------------ fused Join -> GroupBy pipeline ----
+// GroupBy(keys incl. the join key, aggregates over the probe side) over Join(inner | left; one plain integer key pair) over two `[Filter]* Scan` inputs, each possibly
+// behind a nested filter join (SemiFilter): a group is a build row, the probe scan adds into its cells.  plan_join_groupby decides everything, then one function per stage.
+struct GroupKey { bool is_join_key; int build_col; int expr; int dtype; };
+// One nested filter join: the side it restricts (0 = build, 1 = probe), its index among that side's filters, its lookup bitmap's number in that side's programs (build
+// side: index; probe side: behind the build side's), and the scan of its filter side
+struct SemiUse { const SemiFilter* sf; int side; int index; int lut; std::unique_ptr<Compiler> scan; };
+// Everything decided before anything runs.  Stays where it is: cp.df, cs.df and ca.df point at pview, the uses at the filters.
+struct JoinGroupBy {
+  JoinGroupBy& operator=(JoinGroupBy&&) = delete;       // (neither copied nor moved)
+  bool left_join = false;
+  JoinSides sides;
+  std::vector<SemiFilter> bsemis, psemis;
+  std::vector<SemiUse> semis;                           // the build side's, then the probe side's
+  std::vector<GroupKey> gkeys;
+  Frame pview;                                          // the probe side under the joined frame's names: what the aggregates read
+  std::optional<Compiler> cnt, cb, cp, cs, ca;          // count, build, probe, the partitioned probe's scatter; ca: the left join's unmatched rows (group-by over the probe side)
+  std::vector<int> agg_nodes;
+  std::vector<FinalSpec> specs, aspecs;
+  KeyPlan akp;
+  int len_idx = -1, a_len_idx = -1;
+  MemberBitmap unmatched_keys;                          // left join: the build keys that pass the build side's predicate
+};
+
+// the programs of `j` (throws Unsupported)
+static void compile_join_programs(const Plan& plan, const IRN& gb, JoinGroupBy& j) {
+  const JoinSides& s = j.sides;
+  const int nbs = (int)j.bsemis.size(), nps = (int)j.psemis.size();
+  // conjunction of the side's predicates and of the membership tests of its semi filters (lookup bitmap i = args.lut[lut0 + i])
+  auto and_preds = [&](Compiler& c, const std::vector<int>& preds, const std::vector<SemiFilter>& semis, int lut0) {
+    int p = and_predicates(c, preds);
+    for (size_t i = 0; i < semis.size(); i++) {
+      int64_t mn = 0, mx = 0;
+      if (!semi_key_range(semis[i], &mn, &mx)) mn = mx = 0;      // empty filter side: the bitmap is empty, nothing matches
+      // (rows the cheaper conjuncts already rejected do not look the bitmap up: OP_MASKV; the conjunction is the same either way)
+      const int kn = c.load(semis[i].pkey);
+      const int n = c.bit_lookup(p < 0 ? kn : c.mask_valid(kn, p), lut0 + (int)i, mn);
+      p = p < 0 ? n : c.mk(OP_AND, p, n, 'b');
+    }
+    return p;
+  };
+  Compiler &cnt = j.cnt.emplace(plan, *s.B), &cb = j.cb.emplace(plan, *s.B), &cp = j.cp.emplace(plan, *s.P), &cs = j.cs.emplace(plan, *s.P), &ca = j.ca.emplace(plan, *s.P);
+  cnt.lut_base = cb.lut_base = nbs;
+  cp.lut_base = cs.lut_base = nbs + nps;
+  ca.lut_base = nps + 1;
+  cnt.pred = and_preds(cnt, s.bpreds, j.bsemis, 0);
+  const int bk_cnt = cnt.load(s.bki);
+  cnt.add_agg(cnt.nodes[bk_cnt].nullable ? AGG_COUNT : AGG_LEN, cnt.nodes[bk_cnt].nullable ? bk_cnt : -1);
+  cnt.finish();
+  cb.pred = and_preds(cb, s.bpreds, j.bsemis, 0);
+  cb.key = cb.load(s.bki);
+  cb.finish();
+  cp.pred = and_preds(cp, s.ppreds, j.psemis, nbs);
+  cp.key = cp.load(s.pki);
+  cp.df = &j.pview;
+  j.len_idx = cp.add_agg(AGG_LEN, -1);
+  for (int e : gb.exprs) collect_aggs(plan, e, j.agg_nodes);
+  for (int a : j.agg_nodes) j.specs.push_back(cp.lower_agg(a));
+  cp.finish();
+  // the probe side's predicate + key alone, row id as payload: the program of the partitioned probe's scatter (k::partitioned_probe_hits)
+  cs.pred = and_preds(cs, s.ppreds, j.psemis, nbs);
+  cs.key = cs.load(s.pki);
+  cs.df = &j.pview;
+  cs.add_agg(AGG_FIRST_ROW, -1);
+  cs.finish();
+  if (j.left_join) {
+    int p = and_preds(ca, s.ppreds, j.psemis, 0);                                  // (its own lookup numbering: the probe side's semi filters, then the membership bitmap)
+    const int kn = ca.load(s.pki);
+    ca.df = &j.pview;                                                              // (after the loads by column index, which are the probe frame's: pview orders its columns by name)
+    const int member = ca.ifnull(ca.bit_lookup(p < 0 ? kn : ca.mask_valid(kn, p), nps, j.unmatched_keys.kmin), 0);      // a null key is among nobody's keys
+    const int unmatched = ca.mk(OP_NOT, member, member, 'b');
+    ca.pred = p < 0 ? unmatched : ca.mk(OP_AND, p, unmatched, 'b');
+    int jk_expr = -1;
+    for (auto& gk : j.gkeys) if (gk.is_join_key) jk_expr = gk.expr;
+    j.akp = lower_keys(ca, std::vector<int>{jk_expr});
+    j.a_len_idx = ca.add_agg(AGG_LEN, -1);
+    for (int a : j.agg_nodes) j.aspecs.push_back(ca.lower_agg(a));
+    ca.finish();
+  }
+  // one program per semi filter: build-side filters first, then probe-side
+  for (int side = 0; side < 2; side++) {
+    const std::vector<SemiFilter>& sv = side == 0 ? j.bsemis : j.psemis;
+    for (size_t i = 0; i < sv.size(); i++) {
+      j.semis.push_back(SemiUse{&sv[i], side, (int)i, side == 0 ? (int)i : nbs + (int)i, std::make_unique<Compiler>(plan, *sv[i].F)});
+      Compiler& cf = *j.semis.back().scan;
+      cf.pred = and_preds(cf, sv[i].fpreds, {}, 0);
+      cf.key = cf.load(sv[i].fkey);
+      cf.finish();
+    }
+  }
+}
+
+// The checks, the two sides, the group keys and the programs.  false + why: the pipeline does not take this plan (nothing has run)
+static bool plan_join_groupby(const Plan& plan, const IRN& gb, JoinGroupBy& j, std::string* why) {
   auto no = [&](const char* m) { if (why) *why = m; return false; };
   if (gb.input < 0 || plan.ir[gb.input].kind != PLX_IR_JOIN) return no("input is not a join");
   const IRN& jn = plan.ir[gb.input];
-  if (const char* per_node = join_takes_per_node_route(jn)) return no(per_node);
-  if ((jn.how != PLX_JOIN_INNER && jn.how != PLX_JOIN_LEFT) || jn.keys.size() != 1 || jn.keys_right.size() != 1) return no("not a single-key inner or left join");
+  const AE *lkx = nullptr, *rkx = nullptr;
+  if (const char* bad = single_key_join(plan, jn, false, nullptr, lkx, rkx)) return no(bad);
   // LEFT join (single_keys_left.rs:106-195: every left row survives; rows without a match carry nulls in the right table's columns): the matched rows are the inner join's
   // -- the same pipeline with the RIGHT table as the build side -- and the unmatched ones are a group-by of their own over the left table, keyed by the join key, behind
   // the predicate "key not among the build keys" (a membership bitmap over the build key range, tested inside the scan: OP_BITLOOKUP); their groups carry nulls in the
   // build-side group columns.  Needs a build key range a bitmap can cover; otherwise the per-node path runs the join.
-  const bool left_join = jn.how == PLX_JOIN_LEFT;
+  j.left_join = jn.how == PLX_JOIN_LEFT;
   if (gb.maintain_order) return no("maintain_order");
-  const AE* lkx = plain_column(plan, jn.keys[0]);
-  const AE* rkx = plain_column(plan, jn.keys_right[0]);
-  if (!lkx || !rkx) return no("join keys are expressions");
   std::vector<int> lpreds, rpreds;
   std::vector<SemiFilter> lsemis, rsemis;
   std::set<std::string> used;                       // column names referenced above the join inputs
@@ -1986,23 +2085,18 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   const int rsrc = resolve_join_side(plan, jn.input_right, used, rpreds, rsemis, why);
   if (rsrc < 0) return false;
   if (lsemis.size() + rsemis.size() > (size_t)kMaxLuts) return no("more nested filter joins than lookup bitmaps");
-  JoinSides sides;
+  JoinSides& s = j.sides;
   const char* bad = nullptr;
-  if (!resolve_join_sides(sides, get_frame(plan.ir[lsrc].frame), get_frame(plan.ir[rsrc].frame), lkx, rkx, left_join, lpreds, rpreds, &bad)) return no(bad);
-  const FramePtr &B = sides.B, &P = sides.P;
-  const int lki = sides.lki, bki = sides.bki, pki = sides.pki, kdt = sides.kdt;
-  const bool build_right = sides.build_right;
-  const std::vector<int> &bpreds = sides.bpreds, &ppreds = sides.ppreds;
-  const std::vector<SemiFilter>& bsemis = build_right ? rsemis : lsemis;
-  const std::vector<SemiFilter>& psemis = build_right ? lsemis : rsemis;
+  if (!resolve_join_sides(s, get_frame(plan.ir[lsrc].frame), get_frame(plan.ir[rsrc].frame), lkx, rkx, j.left_join, lpreds, rpreds, &bad)) return no(bad);
+  const FramePtr &B = s.B, &P = s.P;
+  j.bsemis = s.build_right ? rsemis : lsemis;
+  j.psemis = s.build_right ? lsemis : rsemis;
   std::vector<JoinedCol> jcols;
-  if (!joined_columns(*sides.L, *sides.R, sides.rki, jn.suffix, jcols, &bad)) return no(bad);
+  if (!joined_columns(*s.L, *s.R, s.rki, jn.suffix, jcols, &bad)) return no(bad);
   std::map<std::string, const JoinedCol*> joined;      // by name
   for (const JoinedCol& jc : jcols) joined[jc.name] = &jc;
-  const int build_side = build_right ? 1 : 0;
+  const int build_side = s.build_right ? 1 : 0;
   // group keys
-  struct GKey { bool is_join_key; int build_col; int expr; int dtype; };
-  std::vector<GKey> gkeys;
   bool has_join_key = false;
   for (int e : gb.keys) {
     const AE* x = plain_column(plan, e);
@@ -2010,16 +2104,17 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
     auto it = joined.find(x->name);
     if (it == joined.end()) fail(PLX_ERR_NOT_FOUND, "column not found: " + x->name);
     const JoinedCol& sc = *it->second;
-    const bool is_key = (sc.side == 0 && sc.idx == lki);   // the coalesced key column carries the left name
-    if (is_key) { has_join_key = true; gkeys.push_back({true, -1, e, kdt}); }
-    else if (sc.side == build_side) gkeys.push_back({false, sc.idx, e, B->cols[sc.idx]->dtype});
+    const bool is_key = (sc.side == 0 && sc.idx == s.lki);   // the coalesced key column carries the left name
+    if (is_key) { has_join_key = true; j.gkeys.push_back({true, -1, e, s.kdt}); }
+    else if (sc.side == build_side) j.gkeys.push_back({false, sc.idx, e, B->cols[sc.idx]->dtype});
     else return no("group key from the probe side that is not the join key");
   }
   if (!has_join_key) return no("group keys do not include the join key");
   // aggregates: probe-side columns only, resolved through the joined names
-  Frame pview; pview.height = P->height;
+  Frame& pview = j.pview;
+  pview.height = P->height;
   for (auto& kv : joined) if (kv.second->side != build_side) { pview.names.push_back(kv.first); pview.cols.push_back(P->cols[kv.second->idx]); }
-  if (!build_right) { pview.names.push_back(lkx->name); pview.cols.push_back(P->cols[pki]); }  // coalesced key: probe values == build values on matches
+  if (!s.build_right) { pview.names.push_back(lkx->name); pview.cols.push_back(P->cols[s.pki]); }  // coalesced key: probe values == build values on matches
   std::function<bool(int)> probe_only = [&](int e) -> bool {
     if (e < 0) return true;
     const AE& x = plan.ae[e];
@@ -2030,227 +2125,166 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
     if (!contains_agg(plan, e) || contains_column_outside_agg(plan, e)) return no("aggregation list contains a non-aggregated column");
     if (!probe_only(e)) return no("aggregate reads a build-side column");
   }
-  // ---- compile the three programs
-  Compiler cnt(plan, *B), cb(plan, *B), cp(plan, *P), cs(plan, *P), ca(plan, *P);      // ca: the left join's unmatched rows (group-by over the probe side)
-  KeyPlan akp;
-  std::vector<FinalSpec> aspecs;
-  int a_len_idx = -1;
-  MemberBitmap unmatched_keys;                                  // left join: the build keys that pass the build side's predicate
-  if (left_join) {
-    if (psemis.size() + 1 > (size_t)kMaxLuts) return no("left join: no lookup bitmap left for the membership test");
-    if (kdt == PLX_U64) return no("left join on UInt64 keys");
+  if (j.left_join) {
+    if (j.psemis.size() + 1 > (size_t)kMaxLuts) return no("left join: no lookup bitmap left for the membership test");
+    if (s.kdt == PLX_U64) return no("left join on UInt64 keys");
     int64_t a_kmn = 0, a_kmx = 0;
     bool have = false;                                          // (a placeholder column -- compile-only callers -- has its declared range or none)
-    if (B->height > 0 && B->cols[bki]->values) have = ops::int_range(B->cols[bki], &a_kmn, &a_kmx);
-    else if (B->height > 0 && B->cols[bki]->range_state == 1) { a_kmn = B->cols[bki]->range_min; a_kmx = B->cols[bki]->range_max; have = true; }
-    if (!unmatched_keys.cover(have, a_kmn, a_kmx, B->height)) return no("left join: build key range too wide for the membership bitmap");
+    if (B->height > 0 && B->cols[s.bki]->values) have = ops::int_range(B->cols[s.bki], &a_kmn, &a_kmx);
+    else if (B->height > 0 && B->cols[s.bki]->range_state == 1) { a_kmn = B->cols[s.bki]->range_min; a_kmx = B->cols[s.bki]->range_max; have = true; }
+    if (!j.unmatched_keys.cover(have, a_kmn, a_kmx, B->height)) return no("left join: build key range too wide for the membership bitmap");
   }
-  std::vector<std::unique_ptr<Compiler>> csemi;      // one program per semi filter: build-side filters first, then probe-side
-  std::vector<int> agg_nodes; std::vector<FinalSpec> specs;
-  int len_idx = -1;
-  try {
-    // conjunction of the side's predicates and of the membership tests of its semi filters (lookup bitmap i = args.lut[lut0 + i])
-    auto and_preds = [&](Compiler& c, const std::vector<int>& preds, const std::vector<SemiFilter>& semis, int lut0) {
-      int p = and_predicates(c, preds);
-      for (size_t i = 0; i < semis.size(); i++) {
-        int64_t mn = 0, mx = 0;
-        if (!semi_key_range(semis[i], &mn, &mx)) mn = mx = 0;      // empty filter side: the bitmap is empty, nothing matches
-        // (rows the cheaper conjuncts already rejected do not look the bitmap up: OP_MASKV; the conjunction is the same either way)
-        const int kn = c.load(semis[i].pkey);
-        const int n = c.bit_lookup(p < 0 ? kn : c.mask_valid(kn, p), lut0 + (int)i, mn);
-        p = p < 0 ? n : c.mk(OP_AND, p, n, 'b');
-      }
-      return p;
-    };
-    cnt.lut_base = cb.lut_base = (int)bsemis.size();
-    cp.lut_base = cs.lut_base = (int)(bsemis.size() + psemis.size());
-    ca.lut_base = (int)psemis.size() + 1;
-    cnt.pred = and_preds(cnt, bpreds, bsemis, 0);
-    const int bk_cnt = cnt.load(bki);
-    cnt.add_agg(cnt.nodes[bk_cnt].nullable ? AGG_COUNT : AGG_LEN, cnt.nodes[bk_cnt].nullable ? bk_cnt : -1);
-    cnt.finish();
-    cb.pred = and_preds(cb, bpreds, bsemis, 0);
-    cb.key = cb.load(bki);
-    cb.finish();
-    cp.pred = and_preds(cp, ppreds, psemis, (int)bsemis.size());
-    cp.key = cp.load(pki);
-    cp.df = &pview;
-    len_idx = cp.add_agg(AGG_LEN, -1);
-    for (int e : gb.exprs) collect_aggs(plan, e, agg_nodes);
-    for (int a : agg_nodes) specs.push_back(cp.lower_agg(a));
-    cp.finish();
-    // the probe side's predicate + key alone, row id as payload: the program of the partitioned probe's scatter (k::partitioned_probe_hits)
-    cs.pred = and_preds(cs, ppreds, psemis, (int)bsemis.size());
-    cs.key = cs.load(pki);
-    cs.df = &pview;
-    cs.add_agg(AGG_FIRST_ROW, -1);
-    cs.finish();
-    if (left_join) {
-      ca.df = &pview;
-      int p = and_preds(ca, ppreds, psemis, 0);                                  // (its own lookup numbering: the probe side's semi filters, then the membership bitmap)
-      const int kn = ca.load(pki);
-      const int member = ca.ifnull(ca.bit_lookup(p < 0 ? kn : ca.mask_valid(kn, p), (int)psemis.size(), unmatched_keys.kmin), 0);      // a null key is among nobody's keys
-      const int unmatched = ca.mk(OP_NOT, member, member, 'b');
-      ca.pred = p < 0 ? unmatched : ca.mk(OP_AND, p, unmatched, 'b');
-      int jk_expr = -1;
-      for (auto& gk : gkeys) if (gk.is_join_key) jk_expr = gk.expr;
-      akp = lower_keys(ca, std::vector<int>{jk_expr});
-      a_len_idx = ca.add_agg(AGG_LEN, -1);
-      for (int a : agg_nodes) aspecs.push_back(ca.lower_agg(a));
-      ca.finish();
-    }
-    for (const std::vector<SemiFilter>* sv : {&bsemis, &psemis}) {
-      for (const SemiFilter& sf : *sv) {
-        csemi.emplace_back(new Compiler(plan, *sf.F));
-        Compiler& cf = *csemi.back();
-        cf.pred = and_preds(cf, sf.fpreds, {}, 0);
-        cf.key = cf.load(sf.fkey);
-        cf.finish();
-      }
-    }
-  } catch (const Unsupported& u) { if (why) *why = u.why; return false; }
-  // count, build, probe, the semi filters' scans, and LAST the probe side's predicate + key program of the partitioned probe's scatter
-  if (shapes_out) { shapes_out->push_back(cnt.shape); shapes_out->push_back(cb.shape); shapes_out->push_back(cp.shape); for (auto& cf : csemi) shapes_out->push_back(cf->shape); shapes_out->push_back(cs.shape); }
-  if (compile_only) {
-    if (t_program_dump) {   // the three scans + how groups, group keys and outputs are derived from them (tests/program_eval.py evaluate_join)
-      std::ostringstream o;
-      o << "{\"kind\":\"join_group_by\",\"how\":\"" << (left_join ? "left" : "inner") << "\",\"build_side\":\"" << (build_right ? "right" : "left") << "\",\"build_key\":" << jstr(B->names[bki]) << ",\"probe_key\":" << jstr(P->names[pki])
-        << ",\"count\":{" << program_fields(cnt, *B) << "},\"build\":{" << program_fields(cb, *B) << "},\"probe\":{" << program_fields(cp, *P) << "},\"len_idx\":" << len_idx << ",\"group_keys\":[";
-      for (size_t i = 0; i < gkeys.size(); i++)
-        o << (i ? "," : "") << "{\"name\":" << jstr(output_name(plan, gkeys[i].expr)) << ",\"is_join_key\":" << (gkeys[i].is_join_key ? 1 : 0) << ",\"build_col\":"
-          << (gkeys[i].is_join_key ? std::string("null") : jstr(B->names[gkeys[i].build_col])) << ",\"dtype\":" << gkeys[i].dtype << "}";
-      o << "]," << finals_outputs_fields(plan, agg_nodes, specs, gb.exprs) << ",\"semis\":[";
-      {
-        size_t ci = 0;
-        for (int side = 0; side < 2; side++) {
-          const std::vector<SemiFilter>& sv = side == 0 ? bsemis : psemis;
-          for (size_t i = 0; i < sv.size(); i++, ci++) {
-            int64_t mn = 0, mx = 0; semi_key_range(sv[i], &mn, &mx);
-            o << (ci ? "," : "") << "{\"side\":\"" << (side == 0 ? "build" : "probe") << "\",\"lut\":" << (side == 0 ? i : bsemis.size() + i) << ",\"kmin\":\"" << mn << "\",\"kmax\":\"" << mx
-              << "\",\"filter_key\":" << jstr(sv[i].F->names[sv[i].fkey]) << ",\"payload_key\":" << jstr((side == 0 ? B : P)->names[sv[i].pkey]) << ",\"filter\":{" << program_fields(*csemi[ci], *sv[i].F) << "}}";
-          }
-        }
-      }
-      o << "]";
-      // a left join's unmatched rows: a group-by program over the probe side whose predicate ends in NOT member(key) -- lookup bitmap `lut` = the build keys that pass the build program
-      if (left_join) o << ",\"unmatched\":{\"lut\":" << psemis.size() << ",\"kmin\":\"" << unmatched_keys.kmin << "\",\"range\":\"" << unmatched_keys.range << "\",\"program\":"
-                       << compiled_json("group_by", plan, ca, ScanProgram{ca.shape, ca.args, -1, ""}, &akp, agg_nodes, aspecs, gb.exprs, a_len_idx, -1, false) << "}";
-      o << "}";
-      t_program_dump->json = o.str();
-    }
-    return true;
+  try { compile_join_programs(plan, gb, j); } catch (const Unsupported& u) { if (why) *why = u.why; return false; }
+  return true;
+}
+
+// the three scans + how groups, group keys and outputs are derived from them (tests/program_eval.py evaluate_join)
+static std::string dump_join_groupby(const Plan& plan, const IRN& gb, const JoinGroupBy& j) {
+  const Frame &B = *j.sides.B, &P = *j.sides.P;
+  std::ostringstream o;
+  o << "{\"kind\":\"join_group_by\",\"how\":\"" << (j.left_join ? "left" : "inner") << "\",\"build_side\":\"" << (j.sides.build_right ? "right" : "left") << "\",\"build_key\":" << jstr(B.names[j.sides.bki]) << ",\"probe_key\":" << jstr(P.names[j.sides.pki])
+    << ",\"count\":{" << program_fields(*j.cnt, B) << "},\"build\":{" << program_fields(*j.cb, B) << "},\"probe\":{" << program_fields(*j.cp, P) << "},\"len_idx\":" << j.len_idx << ",\"group_keys\":[";
+  for (size_t i = 0; i < j.gkeys.size(); i++)
+    o << (i ? "," : "") << "{\"name\":" << jstr(output_name(plan, j.gkeys[i].expr)) << ",\"is_join_key\":" << (j.gkeys[i].is_join_key ? 1 : 0) << ",\"build_col\":"
+      << (j.gkeys[i].is_join_key ? std::string("null") : jstr(B.names[j.gkeys[i].build_col])) << ",\"dtype\":" << j.gkeys[i].dtype << "}";
+  o << "]," << finals_outputs_fields(plan, j.agg_nodes, j.specs, gb.exprs) << ",\"semis\":[";
+  for (const SemiUse& u : j.semis) {
+    int64_t mn = 0, mx = 0; semi_key_range(*u.sf, &mn, &mx);
+    o << (&u != &j.semis[0] ? "," : "") << "{\"side\":\"" << (u.side == 0 ? "build" : "probe") << "\",\"lut\":" << u.lut << ",\"kmin\":\"" << mn << "\",\"kmax\":\"" << mx
+      << "\",\"filter_key\":" << jstr(u.sf->F->names[u.sf->fkey]) << ",\"payload_key\":" << jstr((u.side == 0 ? B : P).names[u.sf->pkey]) << ",\"filter\":{" << program_fields(*u.scan, *u.sf->F) << "}}";
   }
-  // ---- run
-  // semi filters first: one fused scan of each filter side -> membership bitmap; its set bits must equal the rows that passed
-  // (unique filter keys), otherwise the nested join multiplies rows and the per-node path has to run it
-  std::vector<MemberBitmap> semi_bits(csemi.size());
-  {
-    size_t ci = 0;
-    for (int side = 0; side < 2; side++) {
-      const std::vector<SemiFilter>& sv = side == 0 ? bsemis : psemis;
-      for (size_t i = 0; i < sv.size(); i++, ci++) {
-        const SemiFilter& sf = sv[i];
-        int64_t mn = 0, mx = 0;
-        const bool have = sf.F->height > 0 && semi_key_range(sf, &mn, &mx);
-        MemberBitmap& mb = semi_bits[ci];
-        if (!mb.cover(have, mn, mx, sf.F->height)) return no("nested filter join: key range too wide for a bitmap");
-        mb.build(have ? csemi[ci].get() : nullptr);
-        if (have) {
-          const uint64_t rows_in = mb.rows_in();
-          if ((uint64_t)k::bitmap_popcount(mb.bits->as<uint64_t>(), (int64_t)mb.range) != rows_in) return no("nested filter join: the filter side's keys are not unique");
-          plan.desc += "SemiFilter{" + sf.F->names[sf.fkey] + " -> bitmap range=" + std::to_string(mb.range) + " rows=" + std::to_string(rows_in) + "/" + std::to_string(sf.F->height) + "}; ";
-        }
-        const Lut lut = mb.lut();
-        const int li = side == 0 ? (int)i : (int)(bsemis.size() + i);
-        if (side == 0) { cnt.args.lut[li] = lut; cb.args.lut[li] = lut; } else { cp.args.lut[li] = lut; cs.args.lut[li] = lut; if (left_join) ca.args.lut[i] = lut; }
-      }
+  o << "]";
+  // a left join's unmatched rows: a group-by program over the probe side whose predicate ends in NOT member(key) -- lookup bitmap `lut` = the build keys that pass the build program
+  if (j.left_join) o << ",\"unmatched\":{\"lut\":" << j.psemis.size() << ",\"kmin\":\"" << j.unmatched_keys.kmin << "\",\"range\":\"" << j.unmatched_keys.range << "\",\"program\":"
+                     << compiled_json("group_by", plan, *j.ca, ScanProgram{j.ca->shape, j.ca->args, -1, ""}, &j.akp, j.agg_nodes, j.aspecs, gb.exprs, j.a_len_idx, -1, false) << "}";
+  o << "}";
+  return o.str();
+}
+
+// The semi filters: one fused scan of each filter side -> membership bitmap, handed to the programs of the side it restricts.  Its set bits must equal the rows that passed
+// (unique filter keys), otherwise the nested join multiplies rows and the per-node path has to run it (false + why)
+static bool build_semi_bitmaps(Plan& plan, JoinGroupBy& j, std::vector<MemberBitmap>& semi_bits, std::string* why) {
+  auto no = [&](const char* m) { if (why) *why = m; return false; };
+  for (size_t ci = 0; ci < j.semis.size(); ci++) {
+    const SemiUse& u = j.semis[ci];
+    const SemiFilter& sf = *u.sf;
+    int64_t mn = 0, mx = 0;
+    const bool have = sf.F->height > 0 && semi_key_range(sf, &mn, &mx);
+    MemberBitmap& mb = semi_bits[ci];
+    if (!mb.cover(have, mn, mx, sf.F->height)) return no("nested filter join: key range too wide for a bitmap");
+    mb.build(have ? u.scan.get() : nullptr);
+    if (have) {
+      const uint64_t rows_in = mb.rows_in();
+      if ((uint64_t)k::bitmap_popcount(mb.bits->as<uint64_t>(), (int64_t)mb.range) != rows_in) return no("nested filter join: the filter side's keys are not unique");
+      plan.desc += "SemiFilter{" + sf.F->names[sf.fkey] + " -> bitmap range=" + std::to_string(mb.range) + " rows=" + std::to_string(rows_in) + "/" + std::to_string(sf.F->height) + "}; ";
     }
+    const Lut lut = mb.lut();
+    if (u.side == 0) { j.cnt->args.lut[u.lut] = lut; j.cb->args.lut[u.lut] = lut; }
+    else { j.cp->args.lut[u.lut] = lut; j.cs->args.lut[u.lut] = lut; if (j.left_join) j.ca->args.lut[u.index] = lut; }      // (the left tail numbers the probe side's filters from 0)
   }
-  uint64_t nb = 0;
-  // Duplicate build keys (the reference's tables map a key to a LIST of build rows: single_keys.rs:16-167, probe_inner emits one pair per entry, single_keys_inner.rs:11-38):
-  // the hash-table pipeline then runs in multi-value mode -- chains of build rows per key, a group = a build ROW (or the rows of a key that agree on the build-side group
-  // columns: canonicalise_chains), every probe row adds to the cells of each row of its key's chain.  Possible when those group columns are integer-typed (compared bitwise).
-  bool known_dups = B->height > 0 && B->cols[bki]->repeats_as_build_key, multi = false;
-  uint32_t merged_rows = 0;      // multi-value mode: build rows that share their group with an earlier row of their key
-  RepCols rep_cols{};
-  bool multi_ok = !(getenv("PLX_JOIN_MULTI") && getenv("PLX_JOIN_MULTI")[0] == '0');
-  for (auto& gk : gkeys) {
-    if (gk.is_join_key) continue;
-    const ColumnPtr& col = B->cols[gk.build_col];
-    const int w = col->dtype == PLX_BOOL || col->dtype == PLX_F32 || col->dtype == PLX_F64 ? 0 : dtype_width(col->dtype);
-    if (!w || rep_cols.n >= kMaxRepCols) { multi_ok = false; break; }
-    rep_cols.vals[rep_cols.n] = col->data(); rep_cols.valid[rep_cols.n] = (const unsigned long long*)col->valid_words(); rep_cols.width[rep_cols.n] = w; rep_cols.n++;
+  return true;
+}
+
+// What a route leaves: the groups' cells and packed keys, compacted, the build row of every group, and whether a group is a build ROW (multi-value mode) rather than a key
+struct JoinGroups {
+  FusedAggResult r;
+  ColumnPtr rows = std::make_shared<Column>();
+  bool multi = false;
+};
+
+// The partitioned probe of either table: `hits_of(&rows, &how)` scatters the probe side by key and lists the rows that can match (false: it does not take this table, nothing
+// was probed), `probe(args)` is the ordinary probe kernel, run over those rows only (gathered).  `gathered(columns, n)`: what else the route does with them before they go.
+template <class Hits, class Probe, class Gathered>
+static bool probe_through_partitions(const Compiler& cp, Hits&& hits_of, Probe&& probe, Gathered&& gathered, std::string& how) {
+  ColumnPtr hits;
+  std::string pd;
+  if (!hits_of(&hits, &pd)) return false;
+  if (hits->len > 0) {
+    std::vector<ColumnPtr> keep = probe_gathered(cp, hits, probe);
+    gathered(keep, hits->len);
+    PLX_HIP(hipStreamSynchronize(stream()));       // the gathered columns live until the kernels have read them
   }
+  how = pd + "+gather+probe_agg";
+  return true;
+}
+
+// Direct-address table when the build key range is small (cached column statistics); needs no count pass.  false: not taken -- the range is too wide, or the build keys
+// repeat (known_dups is then set: the hash-table route runs them in multi-value mode)
+static bool direct_table_route(Plan& plan, const JoinGroupBy& j, bool& known_dups, JoinGroups& g) {
+  const Frame &B = *j.sides.B, &P = *j.sides.P;
+  const Compiler &cp = *j.cp, &cs = *j.cs;
+  DirectBuild direct;
+  direct.dt.opts = probe_late_loads() ? kDirectLateLoads : 0u;
+  const DirectBuild::Result built = direct.try_build(plan, *j.cb, B, j.sides.bki, known_dups);
+  if (built == DirectBuild::kDuplicateKeys) known_dups = true;
+  if (built != DirectBuild::kBuilt) return false;
+  DirectJoinTable& dt = direct.dt;
+  const uint64_t range = direct.range, nb = direct.nb;
   const int probe_static_id = find_static_shape(cp.shape);
-  FusedAggResult r; r.n_aggs = cp.shape.n_aggs;
-  auto rows = std::make_shared<Column>();
-  rows->dtype = PLX_U32; rows->null_count = 0;
-  int64_t G = 0;
-  bool done = false;
-  // -- direct-address table when the build key range is small (cached column statistics); needs no count pass
-  {
-    DirectBuild direct;
-    direct.dt.opts = probe_late_loads() ? kDirectLateLoads : 0u;
-    const DirectBuild::Result built = direct.try_build(plan, cb, *B, bki, known_dups);
-    if (built == DirectBuild::kDuplicateKeys) known_dups = true;   // the hash-table pipeline below runs them in multi-value mode
-    else if (built == DirectBuild::kBuilt) {
-      DirectJoinTable& dt = direct.dt;
-      const uint64_t range = direct.range;
-      nb = direct.nb;
-      const int64_t n_slots = (int64_t)nb, s1 = std::max<int64_t>(n_slots, 1);
-      Buf acc2 = dev_alloc(sizeof(uint64_t) * (size_t)s1 * cp.shape.n_aggs);
-      k::init_agg_cells(acc2->as<uint64_t>(), s1, cp.shape);   // LEN = 0: build rows no probe row matched never show up
-      dt.acc = acc2->as<unsigned long long>();
-      // Probe.  Keys in (rough) key order walk the bitmap out of the L2; keys in no order fetch one line per row across the fabric: those
-      // are partitioned by key range first and probed against LDS-resident bitmap slices, and the ordinary probe kernel then runs over
-      // the matching rows only (gathered).  Worth it when the bitmap is far larger than an L2 (4 MB) and few rows can match.
-      std::string probe_how = "probe_agg";
-      bool probed = false;
-      Buf touch;
-      if (partition_direct_probe(partitioned_probe_mode(), *P, pki, range, nb)) {
-        ColumnPtr hits;
-        std::string pd;
-        if (k::partitioned_probe_hits(cs.shape, cs.args, dt, nb, find_static_shape(cs.shape), &hits, &pd)) {
-          if (hits->len > 0) {
-            std::vector<ColumnPtr> keep = probe_gathered(cp, hits, [&](const Args& a2) { k::fused_direct_probe_agg(cp.shape, a2, dt, probe_static_id); });
-            // the pair-list compaction below looks every build pair up in bitmap, rank and LEN cells -- random lines for a shuffled build side.  Only keys
-            // among the candidates can have been matched: a 2^26-bit filter of their hashes (8 MB: cache-resident) lets the compaction skip the rest
-            const int key_in = slot_input(cp.shape, cp.shape.key);
-            if (key_in >= 0 && (size_t)key_in < keep.size()) {
-              constexpr unsigned int kLog2TouchBits = 26;
-              touch = dev_alloc_zero(sizeof(uint64_t) * ((size_t)1 << (kLog2TouchBits - 6)));
-              ColumnPtr k64 = keep[key_in]->dtype == PLX_I64 ? keep[key_in] : ops::cast(keep[key_in], PLX_I64);
-              k::touch_filter_set(k64->values->as<int64_t>(), k64->valid_words(), hits->len, kLog2TouchBits, touch->as<uint64_t>());
-              dt.touch_filter = touch->as<unsigned long long>(); dt.log2_touch_bits = kLog2TouchBits;
-            }
-            PLX_HIP(hipStreamSynchronize(stream()));       // the gathered columns live until the kernels have read them
-          }
-          probe_how = pd + "+gather+probe_agg";
-          probed = true;
-        }
-      }
-      if (!probed) k::fused_direct_probe_agg(cp.shape, cp.args, dt, probe_static_id);
-      // one pass over the pair list into buffers sized for every slot (G <= n_slots)
-      r.packed_keys = dev_alloc(sizeof(uint64_t) * (size_t)s1);
-      r.acc = dev_alloc(sizeof(uint64_t) * (size_t)s1 * r.n_aggs);
-      rows->values = dev_alloc(values_bytes(PLX_U32, s1));
-      G = n_slots ? k::direct_agg_compact(dt, direct.n_ord, r.n_aggs, len_idx, r.packed_keys->as<uint64_t>(), rows->values->as<uint32_t>(), r.acc->as<uint64_t>()) : 0;
-      r.n_groups = G;
-      rows->len = G;
-      plan.desc += std::string("FusedJoinGroupBy{build=") + (build_right ? "right" : "left") + " rows=" + std::to_string(nb) + "/" + std::to_string(B->height) + " direct-address table range=" +
-                   std::to_string(range) + " (bitmap + rank) unique-keys, probe rows=" + std::to_string(P->height) + ", fused_scan[" + jit::program_mode(probe_static_id, cp.args.n_rows) + "]+" + probe_how + ", aggs=" +
-                   std::to_string(r.n_aggs) + ", groups=" + std::to_string(G) + "}; ";
-      done = true;
-    }  // unique build keys
+  FusedAggResult& r = g.r;
+  const int64_t n_slots = (int64_t)nb, s1 = std::max<int64_t>(n_slots, 1);
+  Buf acc2 = dev_alloc(sizeof(uint64_t) * (size_t)s1 * cp.shape.n_aggs);
+  k::init_agg_cells(acc2->as<uint64_t>(), s1, cp.shape);   // LEN = 0: build rows no probe row matched never show up
+  dt.acc = acc2->as<unsigned long long>();
+  // Probe.  Keys in (rough) key order walk the bitmap out of the L2; keys in no order fetch one line per row across the fabric: those
+  // are partitioned by key range first and probed against LDS-resident bitmap slices, and the ordinary probe kernel then runs over
+  // the matching rows only (gathered).  Worth it when the bitmap is far larger than an L2 (4 MB) and few rows can match.
+  std::string probe_how = "probe_agg";
+  Buf touch;
+  // the pair-list compaction below looks every build pair up in bitmap, rank and LEN cells -- random lines for a shuffled build side.  Only keys
+  // among the candidates can have been matched: a 2^26-bit filter of their hashes (8 MB: cache-resident) lets the compaction skip the rest
+  auto touch_filter = [&](const std::vector<ColumnPtr>& keep, int64_t n_hits) {
+    const int key_in = slot_input(cp.shape, cp.shape.key);
+    if (key_in < 0 || (size_t)key_in >= keep.size()) return;
+    constexpr unsigned int kLog2TouchBits = 26;
+    touch = dev_alloc_zero(sizeof(uint64_t) * ((size_t)1 << (kLog2TouchBits - 6)));
+    ColumnPtr k64 = keep[key_in]->dtype == PLX_I64 ? keep[key_in] : ops::cast(keep[key_in], PLX_I64);
+    k::touch_filter_set(k64->values->as<int64_t>(), k64->valid_words(), n_hits, kLog2TouchBits, touch->as<uint64_t>());
+    dt.touch_filter = touch->as<unsigned long long>(); dt.log2_touch_bits = kLog2TouchBits;
+  };
+  if (!(partition_direct_probe(partitioned_probe_mode(), P, j.sides.pki, range, nb) &&
+        probe_through_partitions(cp, [&](ColumnPtr* hits, std::string* pd) { return k::partitioned_probe_hits(cs.shape, cs.args, dt, nb, find_static_shape(cs.shape), hits, pd); },
+                                 [&](const Args& a2) { k::fused_direct_probe_agg(cp.shape, a2, dt, probe_static_id); }, touch_filter, probe_how)))
+    k::fused_direct_probe_agg(cp.shape, cp.args, dt, probe_static_id);
+  // one pass over the pair list into buffers sized for every slot (G <= n_slots)
+  r.packed_keys = dev_alloc(sizeof(uint64_t) * (size_t)s1);
+  r.acc = dev_alloc(sizeof(uint64_t) * (size_t)s1 * r.n_aggs);
+  g.rows->values = dev_alloc(values_bytes(PLX_U32, s1));
+  r.n_groups = n_slots ? k::direct_agg_compact(dt, direct.n_ord, r.n_aggs, j.len_idx, r.packed_keys->as<uint64_t>(), g.rows->values->as<uint32_t>(), r.acc->as<uint64_t>()) : 0;
+  g.rows->len = r.n_groups;
+  plan.desc += std::string("FusedJoinGroupBy{build=") + (j.sides.build_right ? "right" : "left") + " rows=" + std::to_string(nb) + "/" + std::to_string(B.height) + " direct-address table range=" +
+               std::to_string(range) + " (bitmap + rank) unique-keys, probe rows=" + std::to_string(P.height) + ", fused_scan[" + jit::program_mode(probe_static_id, cp.args.n_rows) + "]+" + probe_how + ", aggs=" +
+               std::to_string(r.n_aggs) + ", groups=" + std::to_string(r.n_groups) + "}; ";
+  return true;
+}
+
+// Duplicate build keys (the reference's tables map a key to a LIST of build rows: single_keys.rs:16-167, probe_inner emits one pair per entry, single_keys_inner.rs:11-38):
+// the hash-table pipeline then runs in multi-value mode -- chains of build rows per key, a group = a build ROW (or the rows of a key that agree on the build-side group
+// columns: canonicalise_chains), every probe row adds to the cells of each row of its key's chain.  Possible when those group columns are integer-typed (compared bitwise):
+// `rep` lists them; false: one of them is not, or PLX_JOIN_MULTI=0.
+static bool chain_group_columns(const JoinGroupBy& j, RepCols& rep) {
+  bool multi_ok = !(getenv("PLX_JOIN_MULTI") && getenv("PLX_JOIN_MULTI")[0] == '0');
+  for (auto& gk : j.gkeys) {
+    if (gk.is_join_key) continue;
+    const ColumnPtr& col = j.sides.B->cols[gk.build_col];
+    const int w = col->dtype == PLX_BOOL || col->dtype == PLX_F32 || col->dtype == PLX_F64 ? 0 : dtype_width(col->dtype);
+    if (!w || rep.n >= kMaxRepCols) { multi_ok = false; break; }
+    rep.vals[rep.n] = col->data(); rep.valid[rep.n] = (const unsigned long long*)col->valid_words(); rep.width[rep.n] = w; rep.n++;
   }
-  if (!done) {
+  return multi_ok;
+}
+
+// Hash table of the build side, unique keys or (known_dups, or found by the build) chains of rows.  false + why: the build keys repeat in a way the chains do not take
+static bool hash_table_route(Plan& plan, const JoinGroupBy& j, bool known_dups, bool multi_ok, const RepCols& rep_cols, JoinGroups& g, std::string* why) {
+  auto no = [&](const char* m) { if (why) *why = m; return false; };
+  const Frame &B = *j.sides.B, &P = *j.sides.P;
+  const Compiler &cp = *j.cp, &cs = *j.cs;
   HashBuild hb;
-  if (!hb.run(cnt, cb, *B, bki, HashBuildOptions{4, known_dups, multi_ok, true, "join_build"})) return no("build keys are not unique (and a build-side group column is not integer-typed)");
+  if (!hb.run(*j.cnt, *j.cb, B, j.sides.bki, HashBuildOptions{4, known_dups, multi_ok, true, "join_build"})) return no("build keys are not unique (and a build-side group column is not integer-typed)");
   JoinAggTable& t = hb.t;
-  const k::JoinCells& jcells = hb.cells;
-  const uint64_t cap = hb.cap;
-  nb = hb.nb; multi = hb.multi;
-  Buf acc;
+  const uint64_t nb = hb.nb;
+  const bool multi = g.multi = hb.multi;
+  uint32_t merged_rows = 0;      // multi-value mode: build rows that share their group with an earlier row of their key
   if (multi) {
     Buf cflags = dev_alloc_zero(8);
     constexpr unsigned int kMaxChain = 1024;
@@ -2264,115 +2298,121 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   }
   // one cell set per KEY, also in multi-value mode (the groups are expanded from the key's cells by chains_agg_compact): a slot's cells, or -- a windowed table numbers
   // its keys -- the key's
-  const int64_t n_cells = t.log2_window ? (int64_t)nb + 1 : (int64_t)cap + 1;
-  acc = dev_alloc(sizeof(uint64_t) * (size_t)n_cells * cp.shape.n_aggs);
+  const int probe_static_id = find_static_shape(cp.shape);
+  FusedAggResult& r = g.r;
+  const int64_t n_cells = t.log2_window ? (int64_t)nb + 1 : (int64_t)hb.cap + 1;
+  Buf acc = dev_alloc(sizeof(uint64_t) * (size_t)n_cells * cp.shape.n_aggs);
   t.acc = acc->as<unsigned long long>();
   k::init_agg_cells(acc->as<uint64_t>(), n_cells, cp.shape);
   // Probe.  A table beyond the caches (64 MB) probed by a much longer relation: every probe row would fetch a line across the fabric (SF100 Q3 on keys without
   // a dense range: 3.2e8 random probes of a 400 MB table).  The probe side is partitioned by the key's HASH instead and each partition is tested against an
   // LDS Bloom filter of the table's keys in it (k::partitioned_hash_probe_hits: the radix-partitioned probe of single_keys_inner.rs:11-149 with the partition's
   // filter in LDS); the hash probe below then runs over the surviving candidates only and compares whole keys.
-  std::string hprobe_how = "probe_agg";
-  bool hprobed = false;
-  if (partition_hash_probe(partitioned_probe_mode(), *P, cap, nb)) {
-    ColumnPtr hits;
-    std::string pd;
-    if (k::partitioned_hash_probe_hits(cs.shape, cs.args, t, nb, find_static_shape(cs.shape), &hits, &pd)) {
-      if (hits->len > 0) {
-        std::vector<ColumnPtr> keep = probe_gathered(cp, hits, [&](const Args& a2) { k::fused_probe_agg(cp.shape, a2, t, probe_static_id); });
-        PLX_HIP(hipStreamSynchronize(stream()));       // the gathered columns live until the kernels have read them
-      }
-      hprobe_how = pd + "+gather+probe_agg";
-      hprobed = true;
-    }
-  }
-  JTRACE("probe (partitioned: %d)", (int)hprobed);
-  if (!hprobed) k::fused_probe_agg(cp.shape, cp.args, t, probe_static_id);
+  std::string probe_how = "probe_agg";
+  const bool partitioned = partition_hash_probe(partitioned_probe_mode(), P, hb.cap, nb) &&
+      probe_through_partitions(cp, [&](ColumnPtr* hits, std::string* pd) { return k::partitioned_hash_probe_hits(cs.shape, cs.args, t, nb, find_static_shape(cs.shape), hits, pd); },
+                               [&](const Args& a2) { k::fused_probe_agg(cp.shape, a2, t, probe_static_id); }, [](const std::vector<ColumnPtr>&, int64_t) {}, probe_how);
+  JTRACE("probe (partitioned: %d)", (int)partitioned);
+  if (!partitioned) k::fused_probe_agg(cp.shape, cp.args, t, probe_static_id);
   JTRACE("probe done");
   // ONE compaction pass into buffers sized for every build row (G <= nb): no counting pass over the table first
   const int64_t g1 = std::max<int64_t>((int64_t)nb, 1);
   if (!multi) {
     r.packed_keys = dev_alloc(sizeof(uint64_t) * (size_t)g1);
     r.acc = dev_alloc(sizeof(uint64_t) * (size_t)g1 * r.n_aggs);
-    rows->values = dev_alloc(values_bytes(PLX_U32, g1));
+    g.rows->values = dev_alloc(values_bytes(PLX_U32, g1));
   }
   // (measured on SF100 Q3 with hashed keys: listing the touched slots from the candidates' probe -- one returning atomic per row -- costs that probe 0.5 ms, a
   // candidates' filter in front of the LEN cells 0.2 ms; streaming the LEN cells is 0.37 ms)
-  if (multi) G = k::chains_agg_compact(t, cp.shape, acc->as<uint64_t>(), len_idx, &rows->values, &r.acc);
-  else if (t.log2_window) G = k::cells_agg_compact(jcells, acc->as<uint64_t>(), n_cells, r.n_aggs, len_idx, r.packed_keys->as<uint64_t>(), rows->values->as<uint32_t>(), r.acc->as<uint64_t>());
-  else G = k::join_agg_compact(t, r.n_aggs, len_idx, r.packed_keys->as<uint64_t>(), rows->values->as<uint32_t>(), r.acc->as<uint64_t>());
+  int64_t G;
+  if (multi) G = k::chains_agg_compact(t, cp.shape, acc->as<uint64_t>(), j.len_idx, &g.rows->values, &r.acc);
+  else if (t.log2_window) G = k::cells_agg_compact(hb.cells, acc->as<uint64_t>(), n_cells, r.n_aggs, j.len_idx, r.packed_keys->as<uint64_t>(), g.rows->values->as<uint32_t>(), r.acc->as<uint64_t>());
+  else G = k::join_agg_compact(t, r.n_aggs, j.len_idx, r.packed_keys->as<uint64_t>(), g.rows->values->as<uint32_t>(), r.acc->as<uint64_t>());
   JTRACE("compacted: %lld groups", (long long)G);
   PLX_REQUIRE(multi || G <= g1, PLX_ERR_INVALID, "join: more groups than build rows");
-  r.n_groups = G;
-  rows->len = G;
-  plan.desc += std::string("FusedJoinGroupBy{build=") + (build_right ? "right" : "left") + " rows=" + std::to_string(nb) + "/" + std::to_string(B->height) + " hash table cap=2^" + std::to_string(hb.log2_cap) + " [" + hb.build_how + "]" +
-               (multi ? " multi-value (row chains, a group = a build row; " + std::to_string(merged_rows) + " rows share another row's group), probe rows=" : " unique-keys, probe rows=") + std::to_string(P->height) + ", fused_scan[" + jit::program_mode(probe_static_id, cp.args.n_rows) + "]+" + hprobe_how + ", aggs=" + std::to_string(r.n_aggs) + ", groups=" + std::to_string(G) + "}; ";
-  }  // hash-table path
-  // ---- output frame: keys, then aggregates
-  out = std::make_shared<Frame>();
-  out->height = G;
+  r.n_groups = g.rows->len = G;
+  plan.desc += std::string("FusedJoinGroupBy{build=") + (j.sides.build_right ? "right" : "left") + " rows=" + std::to_string(nb) + "/" + std::to_string(B.height) + " hash table cap=2^" + std::to_string(hb.log2_cap) + " [" + hb.build_how + "]" +
+               (multi ? " multi-value (row chains, a group = a build row; " + std::to_string(merged_rows) + " rows share another row's group), probe rows=" : " unique-keys, probe rows=") + std::to_string(P.height) + ", fused_scan[" + jit::program_mode(probe_static_id, cp.args.n_rows) + "]+" + probe_how + ", aggs=" + std::to_string(r.n_aggs) + ", groups=" + std::to_string(G) + "}; ";
+  return true;
+}
+
+// the matched groups' frame: keys, then aggregates
+static FramePtr matched_groups_frame(const Plan& plan, const IRN& gb, const JoinGroupBy& j, const JoinGroups& g) {
+  const Frame& B = *j.sides.B;
+  auto out = std::make_shared<Frame>();
+  out->height = g.r.n_groups;
   FinBatch batch{};
-  for (auto& gk : gkeys) {
+  for (auto& gk : j.gkeys) {
     out->names.push_back(output_name(plan, gk.expr));
-    if (gk.is_join_key && multi) out->cols.push_back(ops::gather(B->cols[bki], rows));      // (inner join: the build row's key IS the group's key)
+    if (gk.is_join_key && g.multi) out->cols.push_back(ops::gather(B.cols[j.sides.bki], g.rows));      // (inner join: the build row's key IS the group's key)
     else if (gk.is_join_key) {
       KeyPart part; part.expr = gk.expr; part.dtype = gk.dtype;
       part.dec.shift = 0; part.dec.mask = ~0ull; part.dec.min = 0; part.dec.null_code = ~0ull; part.dec.dtype = gk.dtype;
-      out->cols.push_back(decode_key_column(r, part, 0, batch));
-    } else out->cols.push_back(ops::gather(B->cols[gk.build_col], rows));
+      out->cols.push_back(decode_key_column(g.r, part, 0, batch));
+    } else out->cols.push_back(ops::gather(B.cols[gk.build_col], g.rows));
   }
-  std::map<int, ColumnPtr> overrides;
-  for (size_t i = 0; i < agg_nodes.size(); i++) overrides[agg_nodes[i]] = finalize_column(r, specs[i], batch);
-  k::finalize_batch(r.acc->as<uint64_t>(), r.n_aggs, G, batch);
-  Frame gframe; gframe.height = G;
-  for (int e : gb.exprs) {
-    Evaluated ev = eval(plan, e, gframe, &overrides);
-    out->names.push_back(output_name(plan, e));
-    out->cols.push_back(broadcast(ev, G));
+  append_aggregate_columns(plan, g.r, j.agg_nodes, j.specs, gb.exprs, batch, *out);
+  return out;
+}
+
+// A left join's unmatched left rows, appended to `out`: membership bitmap of the build keys that pass the build side's predicate, then a fused group-by over the left table
+// behind "key not a member"; their groups carry nulls in the build-side group columns.  false: a row outside bounds the planner had only ASSUMED for the probe key / value
+// columns (lower_keys(ca) and source_ranges run outside fused_groupby's own handler) -- the guesses are forgotten, never made again, and the caller runs the whole join once more
+static bool unmatched_left_groups(Plan& plan, const IRN& gb, JoinGroupBy& j, Frame& out) {
+  const Frame& B = *j.sides.B;
+  Compiler& ca = *j.ca;
+  j.unmatched_keys.build(B.height > 0 ? &*j.cb : nullptr);
+  ca.args.lut[j.psemis.size()] = j.unmatched_keys.lut();
+  FusedAggResult ar;
+  std::string ad;
+  try {
+    run_fused_groupby(ca, j.akp, j.a_len_idx, ar, ad, plan.encoded);
+  } catch (const Error& e) {
+    if (!forget_assumed_bounds(ca.cols) || e.code != PLX_ERR_INVALID) throw;
+    plan.desc += "AssumedBoundsViolated{exact statistics, second run}; ";
+    return false;
   }
-  if (left_join) {
-    // the unmatched left rows: membership bitmap of the build keys that pass the build side's predicate, then a fused group-by over the left table
-    unmatched_keys.build(B->height > 0 ? &cb : nullptr);
-    ca.args.lut[psemis.size()] = unmatched_keys.lut();
-    FusedAggResult ar;
-    std::string ad;
-    try {
-      run_fused_groupby(ca, akp, a_len_idx, ar, ad, plan.encoded);
-    } catch (const Error& e) {
-      // a row outside bounds the planner had only ASSUMED for the probe key / value columns (lower_keys(ca) and source_ranges run outside fused_groupby's own handler): forget
-      // the guesses, never guess about these columns again, and run the whole join once more from exact statistics -- like fused_groupby does
-      if (!forget_assumed_bounds(ca.cols) || e.code != PLX_ERR_INVALID) throw;
-      plan.desc += "AssumedBoundsViolated{exact statistics, second run}; ";
-      return fused_join_groupby(plan, gb, out, why, shapes_out, compile_only);
-    }
-    plan.desc += "LeftJoinUnmatched{membership bitmap range=" + std::to_string(unmatched_keys.range) + ", " + akp.note + "FusedFilterGroupBy{" + ad + ", groups=" + std::to_string(ar.n_groups) + "}}; ";
-    const int64_t U = ar.n_groups;
-    auto tail = std::make_shared<Frame>();
-    tail->height = U;
-    FinBatch abatch{};
-    for (auto& gk : gkeys) {
-      tail->names.push_back(output_name(plan, gk.expr));
-      if (gk.is_join_key) tail->cols.push_back(decode_key_column(ar, akp.parts[0], 0, abatch));
-      else tail->cols.push_back(ops::full_column(B->cols[gk.build_col]->dtype, plx_scalar{0}, false, U));       // no build row: null
-    }
-    std::map<int, ColumnPtr> aover;
-    for (size_t i = 0; i < agg_nodes.size(); i++) aover[agg_nodes[i]] = finalize_column(ar, aspecs[i], abatch);
-    if (U > 0) k::finalize_batch(ar.acc->as<uint64_t>(), ar.n_aggs, U, abatch);
-    Frame aframe; aframe.height = U;
-    for (int e : gb.exprs) {
-      Evaluated ev = eval(plan, e, aframe, &aover);
-      tail->names.push_back(output_name(plan, e));
-      tail->cols.push_back(broadcast(ev, U));
-    }
-    if (U > 0) {
-      for (size_t i = 0; i < out->cols.size(); i++) {
-        ColumnPtr b = tail->cols[i];
-        if (b->dtype != out->cols[i]->dtype) b = ops::cast(b, out->cols[i]->dtype);
-        out->cols[i] = G > 0 ? ops::concat({out->cols[i], b}) : b;
-      }
-      out->height = G + U;
-    }
+  plan.desc += "LeftJoinUnmatched{membership bitmap range=" + std::to_string(j.unmatched_keys.range) + ", " + j.akp.note + "FusedFilterGroupBy{" + ad + ", groups=" + std::to_string(ar.n_groups) + "}}; ";
+  const int64_t G = out.height, U = ar.n_groups;
+  Frame tail;
+  FinBatch batch{};
+  for (auto& gk : j.gkeys) {
+    tail.names.push_back(output_name(plan, gk.expr));
+    if (gk.is_join_key) tail.cols.push_back(decode_key_column(ar, j.akp.parts[0], 0, batch));
+    else tail.cols.push_back(ops::full_column(B.cols[gk.build_col]->dtype, plx_scalar{0}, false, U));       // no build row: null
   }
+  append_aggregate_columns(plan, ar, j.agg_nodes, j.aspecs, gb.exprs, batch, tail);
+  if (U == 0) return true;
+  for (size_t i = 0; i < out.cols.size(); i++) {
+    ColumnPtr b = tail.cols[i];
+    if (b->dtype != out.cols[i]->dtype) b = ops::cast(b, out.cols[i]->dtype);
+    out.cols[i] = G > 0 ? ops::concat({out.cols[i], b}) : b;
+  }
+  out.height = G + U;
+  return true;
+}
+
+static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::string* why, std::vector<Shape>* shapes_out = nullptr, bool compile_only = false) {
+  JoinGroupBy j;
+  if (!plan_join_groupby(plan, gb, j, why)) return false;
+  // count, build, probe, the semi filters' scans, and LAST the probe side's predicate + key program of the partitioned probe's scatter
+  if (shapes_out) { shapes_out->push_back(j.cnt->shape); shapes_out->push_back(j.cb->shape); shapes_out->push_back(j.cp->shape); for (auto& u : j.semis) shapes_out->push_back(u.scan->shape); shapes_out->push_back(j.cs->shape); }
+  if (compile_only) {
+    if (t_program_dump) t_program_dump->json = dump_join_groupby(plan, gb, j);
+    return true;
+  }
+  // ---- run.  The semi bitmaps live until the last scan that tests them (the left tail's); what a table route allocates, until it has compacted its groups
+  std::vector<MemberBitmap> semi_bits(j.semis.size());
+  if (!build_semi_bitmaps(plan, j, semi_bits, why)) return false;
+  bool known_dups = j.sides.B->height > 0 && j.sides.B->cols[j.sides.bki]->repeats_as_build_key;
+  RepCols rep_cols{};
+  const bool multi_ok = chain_group_columns(j, rep_cols);
+  JoinGroups g;
+  g.r.n_aggs = j.cp->shape.n_aggs;
+  g.rows->dtype = PLX_U32; g.rows->null_count = 0;
+  if (!direct_table_route(plan, j, known_dups, g) && !hash_table_route(plan, j, known_dups, multi_ok, rep_cols, g, why)) return false;
+  out = matched_groups_frame(plan, gb, j, g);
+  if (j.left_join && !unmatched_left_groups(plan, gb, j, *out)) return fused_join_groupby(plan, gb, out, why, shapes_out, compile_only);
   return true;
 }
 
@@ -2491,6 +2531,16 @@ static bool fused_filter_frame(Plan& plan, const std::vector<int>& preds, const 
                ", kept=" + std::to_string(m) + "/" + std::to_string(n) + "}; ";
   return true;
 }
+// fused_filter_frame as a step of a join pipeline: the kept rows only (`rows`), or the filtered frame behind a membership test; what it would add to the plan text comes
+// back in `phrase`, behind `lead` and without the closing "; ", for the pipeline's own entry.
+static bool filter_phrase(Plan& plan, const std::vector<int>& preds, const FramePtr& src, FramePtr& out, std::string* why, ColumnPtr* rows, const MemberTest* member, const char* lead, std::string& phrase) {
+  const size_t mark = plan.desc.size();
+  if (!fused_filter_frame(plan, preds, src, out, why, rows, rows != nullptr, member)) return false;
+  phrase = lead + plan.desc.substr(mark);
+  plan.desc.resize(mark);
+  while (!phrase.empty() && (phrase.back() == ' ' || phrase.back() == ';')) phrase.pop_back();
+  return true;
+}
 
 static FramePtr exec_filter(Plan& plan, const IRN& n) {
   if (!(plan.flags & PLX_PLAN_NO_FUSION)) {
@@ -2585,13 +2635,9 @@ static int join_materialise_mode() { const char* e = getenv("PLX_JOIN_MATERIALIS
 static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::string>* want, FramePtr& out, std::string* why, uint64_t* build_rows_out = nullptr, int* build_side_out = nullptr) {
   auto no = [&](const char* m) { if (why) *why = m; return false; };
   const int mode = join_materialise_mode();
-  if (const char* per_node = join_takes_per_node_route(jn)) return no(per_node);
-  if (mode == 0) return no("disabled (PLX_JOIN_MATERIALISE=0)");
-  if ((jn.how != PLX_JOIN_INNER && jn.how != PLX_JOIN_LEFT) || jn.keys.size() != 1 || jn.keys_right.size() != 1) return no("not a single-key inner or left join");
+  const AE *lkx = nullptr, *rkx = nullptr;
+  if (const char* bad = single_key_join(plan, jn, false, mode == 0 ? "disabled (PLX_JOIN_MATERIALISE=0)" : nullptr, lkx, rkx)) return no(bad);
   const bool left_join = jn.how == PLX_JOIN_LEFT;
-  const AE* lkx = plain_column(plan, jn.keys[0]);
-  const AE* rkx = plain_column(plan, jn.keys_right[0]);
-  if (!lkx || !rkx) return no("join keys are expressions");
   std::vector<int> lpreds, rpreds;
   const int lsrc = peel_filters(plan, jn.input, lpreds), rsrc = peel_filters(plan, jn.input_right, rpreds);
   // (cheap checks on scans first: a join this path does not take must not have executed its inputs twice)
@@ -2675,11 +2721,7 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
         }
       } else if (!ppreds.empty()) {
         FramePtr none; std::string fwhy;
-        const size_t mark = plan.desc.size();
-        if (!fused_filter_frame(plan, ppreds, P, none, &fwhy, &cand, true)) { if (why) *why = "probe-side predicate: " + fwhy; return false; }
-        cand_how = "probe rows by " + plan.desc.substr(mark);
-        plan.desc.resize(mark);
-        while (!cand_how.empty() && (cand_how.back() == ' ' || cand_how.back() == ';')) cand_how.pop_back();
+        if (!filter_phrase(plan, ppreds, P, none, &fwhy, &cand, nullptr, "probe rows by ", cand_how)) { if (why) *why = "probe-side predicate: " + fwhy; return false; }
       } else cand_how = "every probe row";
       join::join_pairs_direct(jn.how, P->cols[pki], cand, dt, slot_row->as<uint32_t>(), pidx, bidx, &pd);
       PLX_HIP(hipStreamSynchronize(stream()));
@@ -2705,11 +2747,7 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
   }
   if (!cand && !ppreds.empty()) {
     FramePtr none; std::string fwhy;
-    const size_t mark = plan.desc.size();
-    if (!fused_filter_frame(plan, ppreds, P, none, &fwhy, &cand, true)) { if (why) *why = "probe-side predicate: " + fwhy; return false; }
-    cand_how = "probe rows by " + plan.desc.substr(mark);
-    plan.desc.resize(mark);
-    while (!cand_how.empty() && (cand_how.back() == ' ' || cand_how.back() == ';')) cand_how.pop_back();
+    if (!filter_phrase(plan, ppreds, P, none, &fwhy, &cand, nullptr, "probe rows by ", cand_how)) { if (why) *why = "probe-side predicate: " + fwhy; return false; }
   }
   if (!cand && cand_how.empty()) cand_how = "every probe row";
   // ---- pairs
@@ -2761,12 +2799,8 @@ static bool fused_join_frame(Plan& plan, const IRN& jn, const std::set<std::stri
 // No pairs, no gathers.  Needs a right key range a bitmap can cover (<= 2^34 keys and <= 256 x the right rows); otherwise the per-node join runs.
 static bool fused_semi_anti_frame(Plan& plan, const IRN& jn, FramePtr& out, std::string* why) {
   auto no = [&](const char* m) { if (why) *why = m; return false; };
-  if (const char* per_node = join_takes_per_node_route(jn)) return no(per_node);
-  if (join_materialise_mode() == 0) return no("disabled (PLX_JOIN_MATERIALISE=0)");
-  if ((jn.how != PLX_JOIN_SEMI && jn.how != PLX_JOIN_ANTI) || jn.keys.size() != 1 || jn.keys_right.size() != 1) return no("not a single-key semi or anti join");
-  const AE* lkx = plain_column(plan, jn.keys[0]);
-  const AE* rkx = plain_column(plan, jn.keys_right[0]);
-  if (!lkx || !rkx) return no("join keys are expressions");
+  const AE *lkx = nullptr, *rkx = nullptr;
+  if (const char* bad = single_key_join(plan, jn, true, join_materialise_mode() == 0 ? "disabled (PLX_JOIN_MATERIALISE=0)" : nullptr, lkx, rkx)) return no(bad);
   std::vector<int> lpreds, rpreds;
   const int lsrc = peel_filters(plan, jn.input, lpreds), rsrc = peel_filters(plan, jn.input_right, rpreds);
   FramePtr L = exec_node(plan, lsrc), R = exec_node(plan, rsrc);
@@ -2792,12 +2826,8 @@ static bool fused_semi_anti_frame(Plan& plan, const IRN& jn, FramePtr& out, std:
     rows_in = members.rows_in();
   } else members.build(nullptr);
   const MemberTest mt{lki, members.bits->as<unsigned long long>(), mn, range, jn.how == PLX_JOIN_ANTI};
-  const size_t mark = plan.desc.size();
-  std::string fwhy;
-  if (!fused_filter_frame(plan, lpreds, L, out, &fwhy, nullptr, false, &mt)) { if (why) *why = "left side: " + fwhy; return false; }
-  std::string fd = plan.desc.substr(mark);
-  plan.desc.resize(mark);
-  while (!fd.empty() && (fd.back() == ' ' || fd.back() == ';')) fd.pop_back();
+  std::string fwhy, fd;
+  if (!filter_phrase(plan, lpreds, L, out, &fwhy, nullptr, &mt, "", fd)) { if (why) *why = "left side: " + fwhy; return false; }
   plan.desc += std::string("FusedSemiAntiJoin{") + (jn.how == PLX_JOIN_ANTI ? "anti" : "semi") + ", right rows=" + std::to_string(rows_in) + "/" + std::to_string(R->height) + " -> membership bitmap range=" +
                std::to_string(range) + ", left rows=" + std::to_string(L->height) + " filtered by " + fd + "}; ";
   return true;

@@ -197,3 +197,112 @@ def test_left_join_with_predicates_on_both_sides_and_every_row_unmatched(pl):
         bk = battr < cut
         exp = _expected_left(pkey[keep], np.ones(int(keep.sum()), bool), x[keep], w[keep], bkey[bk], battr[bk], None, True)
         _check(out, exp, True)
+
+
+# ---- the stages of the driver (plan_join_groupby ... unmatched_left_groups) at the shapes the cases above leave out: small sides (2^16 + 3 probe rows: no multiple of the
+# 128-row tile; 1000 build keys), nested filter joins on either side, result sets without a group ----
+N_SMALL, KEYS_SMALL = (1 << 16) + 3, 1000
+
+
+def _filter_side(pl, rng, name, n_keys, cut=70):
+    """a nested join's filter side: unique keys 0..n_keys-1 in no order, a predicate column; -> (frame, the keys that pass `f < cut`)"""
+    keys = rng.permutation(n_keys).astype(np.int64)
+    f = rng.integers(0, 100, n_keys).astype(np.int64)
+    return pl.DataFrame({name: keys, "f_" + name: f}), keys[f < cut]
+
+
+def test_left_join_group_by_with_a_nested_filter_join_on_each_side(pl):
+    """(P join FP) LEFT JOIN (B join FB) -> group_by: the filter on the left DROPS left rows, the one on the right only decides which build rows can match.  Three programs
+    number their lookup bitmaps differently here: build (FB = 0), probe (FP = 1), and the unmatched rows' own (FP = 0, the build keys' membership bitmap = 1)."""
+    rng = np.random.default_rng(611)
+    B, P, host = _frames(pl, rng, N_SMALL, KEYS_SMALL, hashed=False, dense=True)
+    pkey, pvalid, x, w, bkey, battr, _ = host
+    bkey, first = np.unique(bkey, return_index=True)      # one row per key
+    battr = battr[first]
+    bf = rng.integers(0, 400, len(bkey)).astype(np.int64)
+    pf = rng.integers(0, 600, N_SMALL).astype(np.int64)   # a third of them beyond FP's keys
+    FB, fb_keys = _filter_side(pl, rng, "bf", 400)
+    FP, fp_keys = _filter_side(pl, rng, "pf", 500)
+    B = pl.DataFrame({"k": bkey, "a": battr, "bf": bf})
+    P = pl.DataFrame([pl.Series("k", pkey, validity=pvalid), pl.Series("x", x), pl.Series("w", w), pl.Series("pf", pf)])
+    c = pl.col
+    q = (P.lazy().join(FP.lazy().filter(c("f_pf") < 70), on="pf").join(B.lazy().join(FB.lazy().filter(c("f_bf") < 70), on="bf"), on="k", how="left")
+         .group_by("k", "a").agg(c("x").sum().alias("sx"), c("w").sum().alias("sw"), pl.len().alias("n")))
+    keep, bk = np.isin(pf, fp_keys), np.isin(bf, fb_keys)
+    exp = _expected_left(pkey[keep], pvalid[keep], x[keep], w[keep], bkey[bk], battr[bk], None, True)
+    out = q.collect()
+    plan = pl.last_plan()
+    assert plan.count("SemiFilter{") == 2 and "FusedJoinGroupBy{" in plan and "LeftJoinUnmatched{" in plan, plan
+    _check(out, exp, True)
+    ref = q.collect(no_fusion=True)
+    assert "FusedJoinGroupBy" not in pl.last_plan() and "SemiFilter" not in pl.last_plan()
+    _check(ref, exp, True)
+
+
+def test_left_join_whose_every_left_row_has_a_partner_appends_no_group(pl):
+    """The unmatched rows' group-by finds no group: nothing is appended, the height is the matched groups'.  The same frames with a few keys beyond the build side: groups."""
+    rng = np.random.default_rng(612)
+    bkey = (rng.permutation(KEYS_SMALL) + 5).astype(np.int64)
+    battr = np.arange(KEYS_SMALL, dtype=np.int64) * 7 + 3
+    x = rng.integers(-100, 100, N_SMALL).astype(np.int64)
+    w = rng.normal(size=N_SMALL)
+    B = pl.DataFrame({"k": bkey, "a": battr})
+    every = np.ones(N_SMALL, bool)
+    for beyond, tail_groups in ((0, 0), (40, 40)):
+        pkey = rng.integers(5, KEYS_SMALL + 5, N_SMALL).astype(np.int64)
+        pkey[:KEYS_SMALL + beyond] = np.arange(5, KEYS_SMALL + 5 + beyond)      # every build key, and `beyond` keys past them
+        P = pl.DataFrame({"k": pkey, "x": x, "w": w})
+        out = _query_left(pl, P, B, True)
+        plan = pl.last_plan()
+        assert "FusedJoinGroupBy{" in plan and "LeftJoinUnmatched{" in plan, plan
+        assert ("groups=%d}}" % tail_groups) in plan[plan.index("LeftJoinUnmatched{"):], plan
+        assert out.height == KEYS_SMALL + tail_groups
+        exp = _expected_left(pkey, every, x, w, bkey, battr, None, True)
+        _check(out, exp, True)
+        _check(_query_left(pl, P, B, True, no_fusion=True), exp, True)
+
+
+@pytest.mark.parametrize("hashed", [False, True])
+def test_inner_join_group_by_without_a_matching_row_is_empty(pl, hashed):
+    """No probe key is among the build keys, on the direct-address table and (hashed keys) on the hash table: no group, and the columns are still those of the query."""
+    rng = np.random.default_rng(613 + hashed)
+    B, P, host = _frames(pl, rng, N_SMALL, KEYS_SMALL, hashed=hashed, dense=True)
+    pkey, pvalid, x, w, bkey, battr, _ = host
+    bkey, first = np.unique(bkey, return_index=True)
+    battr = battr[first]
+    n = 30_001
+    pkey = pkey[~np.isin(pkey, bkey)][:n]      # (half the probe keys of _frames match nothing: those)
+    assert len(pkey) == n
+    B = pl.DataFrame({"k": bkey, "a": battr})
+    P = pl.DataFrame([pl.Series("k", pkey, validity=pvalid[:n]), pl.Series("x", x[:n]), pl.Series("w", w[:n])])
+    out = _query(pl, P, B, True)
+    plan = pl.last_plan()
+    assert "FusedJoinGroupBy{" in plan and "groups=0}" in plan and ("hash table" if hashed else "direct-address table") in plan, plan
+    ref = _query(pl, P, B, True, no_fusion=True)
+    assert "FusedJoinGroupBy" not in pl.last_plan()
+    assert out.height == 0 and ref.height == 0 and out.columns == ["k", "a", "sx", "sw", "n"] and out.schema == ref.schema, (out.schema, ref.schema)
+    exp = _expected(pkey, pvalid[:n], x[:n], w[:n], bkey, battr, None, True)
+    assert len(exp) == 0
+    _check(out, exp, True)
+
+
+def test_duplicate_build_keys_behind_a_nested_filter_join_through_the_partitioned_probe(pl, monkeypatch):
+    """Chains of build rows, a build-side nested filter join (its bitmap is tested by the count and build scans) and the partitioned hash probe (forced) in one query."""
+    rng = np.random.default_rng(614)
+    n = (1 << 22) + 5
+    B, P, host = _frames(pl, rng, n, KEYS_SMALL, hashed=True)
+    pkey, pvalid, x, w, bkey, battr, _ = host
+    bf = rng.integers(0, 400, len(bkey)).astype(np.int64)
+    FB, fb_keys = _filter_side(pl, rng, "bf", 400)
+    B = pl.DataFrame({"k": bkey, "a": battr, "bf": bf})
+    c = pl.col
+    q = (P.lazy().join(B.lazy().join(FB.lazy().filter(c("f_bf") < 70), on="bf"), on="k")
+         .group_by("k", "a").agg(c("x").sum().alias("sx"), c("w").sum().alias("sw"), pl.len().alias("n")))
+    bk = np.isin(bf, fb_keys)
+    exp = _expected(pkey, pvalid, x, w, bkey[bk], battr[bk], None, True)
+    monkeypatch.setenv("PLX_PROBE_PARTITIONED", "2")
+    out = q.collect()
+    plan = pl.last_plan()
+    assert "SemiFilter{bf -> bitmap" in plan and "multi-value (row chains" in plan and "partitioned_hash_probe(" in plan, plan
+    _check(out, exp, True)
+    _check(q.collect(no_fusion=True), exp, True)
