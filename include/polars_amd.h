@@ -31,6 +31,8 @@
  *       crates/polars-expr/src/expressions/cast.rs (numeric casts only)
  *   plx_if_then_else
  *       crates/polars-expr/src/expressions/ternary.rs (TernaryExpr), crates/polars-core/src/chunked_array/ops/zip.rs (zip_with)
+ *   plx_temporal_part
+ *       crates/polars-time/src/chunkedarray/date.rs, datetime.rs (DateMethods / DatetimeMethods: year, month, day, quarter, weekday, ordinal, hour, minute, second)
  *   plx_filter
  *       crates/polars-compute/src/filter/mod.rs:18-28 (filter)
  *   plx_gather
@@ -349,10 +351,15 @@ typedef enum plx_aexpr_kind {
   PLX_AE_FILL_NULL = 10,  /* lhs, rhs = non-null literal of the same dtype (fill_null(literal)); inside fused pipelines only */
   PLX_AE_TERNARY = 11,    /* when(cond).then(lhs).otherwise(rhs): cond Boolean, lhs / rhs of one dtype (type coercion casts upstream).  A row takes lhs where cond is
                            * valid and true and rhs everywhere else (a null cond selects rhs); value and validity are those of the chosen side.  Output name: that of lhs */
-  PLX_AE_BITMAP_LOOKUP = 12 /* lhs = an integer expression, lit.u = a plx_column of dtype PLX_BOOL without nulls (the lookup bitmap; the caller keeps the handle alive until
+  PLX_AE_BITMAP_LOOKUP = 12, /* lhs = an integer expression, lit.u = a plx_column of dtype PLX_BOOL without nulls (the lookup bitmap; the caller keeps the handle alive until
                            * the plan has run).  Result: Boolean, bit `value` of the bitmap, false outside [0, len(bitmap)), null where lhs is null: set membership over a
                            * dense code range.  Fused pipelines test the bit inside their scan (at most 2 bitmaps per program, semi-join membership bitmaps included; a
                            * plan that needs more runs per node), the per-node path with plx_bitmap_lookup's kernel.  Output name: that of lhs */
+  PLX_AE_TEMPORAL = 13    /* lhs = a Date (PLX_I32 days) or Datetime (PLX_I64 ticks) expression, op = the part (plx_temporal_part), lit.u = the unit (plx_time_unit).
+                           * Result: the part in its own dtype (plx_temporal_part), null exactly where lhs is null.  Fused pipelines compute it inside their scan
+                           * (OP_DATEPART), the per-node path with plx_temporal_part's kernel.  As a group key month, day, quarter, weekday, ordinal_day, hour, minute and
+                           * second have a range known without a pass over the data; year and date take theirs from the operand column's range, which costs one min / max
+                           * pass over that column (cached on it) when nobody knows it yet.  Output name: that of lhs */
 } plx_aexpr_kind;
 
 /* polars_plan::dsl::Operator subset */
@@ -369,7 +376,8 @@ typedef struct plx_aexpr {
   int32_t rhs;  /* arena index of the right input, -1 if none */
   int32_t dtype; /* literal dtype / cast target (plx_dtype) */
   int32_t is_null; /* literal is NULL */
-  plx_scalar lit;   /* PLX_AE_LITERAL: the value; PLX_AE_BITMAP_LOOKUP: lit.u = the lookup bitmap's plx_column handle; read for those kinds only */
+  plx_scalar lit;   /* PLX_AE_LITERAL: the value; PLX_AE_BITMAP_LOOKUP: lit.u = the lookup bitmap's plx_column handle; PLX_AE_TEMPORAL: lit.u = the plx_time_unit;
+                     * read for those kinds only */
   const char* name; /* column name / alias */
   int32_t cond;     /* PLX_AE_TERNARY: arena index of the predicate; read for that kind only (appended last: arenas of earlier callers never carry the kind) */
 } plx_aexpr;
@@ -573,6 +581,31 @@ int plx_strview_match_host(const void* views, const uint8_t* data, int64_t data_
                            uint64_t* out_bits, uint64_t* out_valid);
 int plx_bitmap_lookup(plx_column codes, plx_column lut_bool, plx_column* out_bool);
 int plx_strdict_info(plx_strdict dict, int64_t* n_strings, int64_t* total_bytes);
+
+/* ---- date parts (the reference's dt namespace: crates/polars-time/src/chunkedarray/{date,datetime}.rs) ----
+ * A Date is PLX_I32 days since 1970-01-01, a Datetime PLX_I64 ticks since 1970-01-01T00:00 in the unit given; the calendar is the proleptic Gregorian one and the
+ * day of an instant is floor(ticks / ticks per day), so instants before the epoch land on their own day.  Defined for every i32 day count and every i64 tick count.
+ *   part            output dtype   values
+ *   YEAR            PLX_I32
+ *   MONTH           PLX_I8         1..12
+ *   DAY             PLX_I8         1..31
+ *   QUARTER         PLX_I8         1..4
+ *   WEEKDAY         PLX_I8         ISO: Monday = 1 .. Sunday = 7
+ *   ORDINAL_DAY     PLX_I16        1..366
+ *   HOUR MINUTE SECOND  PLX_I8     0..23, 0..59, 0..59; a Datetime only
+ *   DATE            PLX_I32        the day count (a Date); a Datetime only.  (A ms Datetime beyond +-5.8e6 years keeps the low 32 bits, as the cast does.)
+ *   plx_temporal_part       one kernel over the column (PLX_I32 with PLX_UNIT_DATE, PLX_I64 with a Datetime unit; anything else is PLX_ERR_INVALID); the result shares
+ *                           the input's validity bitmap: null exactly where the input is null.
+ *   plx_temporal_part_host  the same arithmetic on the CPU over host memory (values: n x i32 for PLX_UNIT_DATE, n x i64 otherwise; out: n values of the part's
+ *                           dtype).  Needs no GPU and no plx_init. */
+typedef enum plx_time_unit { PLX_UNIT_DATE = 0, PLX_UNIT_MS = 1, PLX_UNIT_US = 2, PLX_UNIT_NS = 3 } plx_time_unit;
+typedef enum plx_temporal_part_kind {
+  PLX_PART_YEAR = 0, PLX_PART_MONTH = 1, PLX_PART_DAY = 2, PLX_PART_QUARTER = 3, PLX_PART_WEEKDAY = 4, PLX_PART_ORDINAL_DAY = 5,
+  PLX_PART_HOUR = 6, PLX_PART_MINUTE = 7, PLX_PART_SECOND = 8, PLX_PART_DATE = 9
+} plx_temporal_part_kind;
+int plx_temporal_part(plx_column col, int part, int unit, plx_column* out);
+int plx_temporal_part_host(const void* values, int unit, int part, int64_t n, void* out);
+
 int plx_strdict_to_host(plx_strdict dict, int64_t* offsets, uint8_t* bytes);
 int plx_strdict_free(plx_strdict dict);
 /* synthetic Utf8View column (benchmark support, BASELINE config 5 from raw strings): 2 n PLX_U64 words = the inline views of
@@ -706,7 +739,7 @@ int plx_profile_clear(void);
  *   _polars_plugin_field_<name>(fields, n, out, kwargs, kwargs_len)   output field (minor 1 signature, plugin.rs:186-207)
  * Functions: plx_cmp / plx_arith (kwargs {"op": "gt" | ... | "add" | ...}) and one symbol per operator for callers
  * without kwargs: plx_eq ne lt le gt ge, plx_add sub mul truediv floordiv mod, plx_filter(values, mask),
- * plx_when_then_otherwise(mask, then, otherwise), plx_sum mean min max (length-1 result).  Python side: polars.plugins.register_plugin_function(
+ * plx_when_then_otherwise(mask, then, otherwise), plx_dt_part(values; kwargs part, unit), plx_sum mean min max (length-1 result).  Python side: polars.plugins.register_plugin_function(
  *     plugin_path=".../libpolars_amd.so", function_name="plx_gt", args=[pl.col("a"), pl.lit(3)]).           */
 typedef struct plx_caller_context { uint64_t bitflags; } plx_caller_context;
 uint32_t _polars_plugin_get_version(void);
@@ -721,6 +754,7 @@ PLX_DECLARE_PLUGIN(plx_eq) PLX_DECLARE_PLUGIN(plx_ne) PLX_DECLARE_PLUGIN(plx_lt)
 PLX_DECLARE_PLUGIN(plx_add) PLX_DECLARE_PLUGIN(plx_sub) PLX_DECLARE_PLUGIN(plx_mul) PLX_DECLARE_PLUGIN(plx_truediv) PLX_DECLARE_PLUGIN(plx_floordiv) PLX_DECLARE_PLUGIN(plx_mod)
 PLX_DECLARE_PLUGIN(plx_sum) PLX_DECLARE_PLUGIN(plx_mean) PLX_DECLARE_PLUGIN(plx_min) PLX_DECLARE_PLUGIN(plx_max)
 PLX_DECLARE_PLUGIN(plx_when_then_otherwise)   /* (mask, then, otherwise): plx_if_then_else; the field is the `then` input's */
+PLX_DECLARE_PLUGIN(plx_dt_part)               /* (values): plx_temporal_part; kwargs {"part": "year" | ..., "unit": "date" | "ms" | "us" | "ns"}; the field is the part's dtype */
 
 #ifdef __cplusplus
 }

@@ -28,9 +28,12 @@ AGG_SUM, AGG_MEAN, AGG_MIN, AGG_MAX, AGG_COUNT, AGG_LEN, AGG_FIRST = range(7)
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI, JOIN_FULL, JOIN_RIGHT = range(6)
 JOIN_COALESCE_DEFAULT, JOIN_COALESCE, JOIN_KEEP_BOTH = range(3)          # plx_ir.coalesce
 JOIN_ORDER_NONE, JOIN_ORDER_LEFT, JOIN_ORDER_RIGHT, JOIN_ORDER_LEFT_RIGHT, JOIN_ORDER_RIGHT_LEFT = range(5)   # plx_join_order
-AE_COLUMN, AE_LITERAL, AE_BINARY, AE_CAST, AE_AGG, AE_LEN, AE_ALIAS, AE_NOT, AE_IS_NULL, AE_IS_NOT_NULL, AE_FILL_NULL, AE_TERNARY, AE_BITMAP_LOOKUP = range(13)
+AE_COLUMN, AE_LITERAL, AE_BINARY, AE_CAST, AE_AGG, AE_LEN, AE_ALIAS, AE_NOT, AE_IS_NULL, AE_IS_NOT_NULL, AE_FILL_NULL, AE_TERNARY, AE_BITMAP_LOOKUP, AE_TEMPORAL = range(14)
 STR_STARTS_WITH, STR_ENDS_WITH, STR_CONTAINS = range(3)                 # plx_str_match_kind
 STR_MATCH_MAX_PATTERN = 64
+UNIT_DATE, UNIT_MS, UNIT_US, UNIT_NS = range(4)                          # plx_time_unit
+(PART_YEAR, PART_MONTH, PART_DAY, PART_QUARTER, PART_WEEKDAY, PART_ORDINAL_DAY, PART_HOUR, PART_MINUTE, PART_SECOND,
+ PART_DATE) = range(10)                                                  # plx_temporal_part_kind
 (OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_PLUS, OP_MINUS, OP_MULTIPLY, OP_TRUE_DIVIDE,
  OP_FLOOR_DIVIDE, OP_MODULUS, OP_AND, OP_OR, OP_XOR) = range(15)
 IR_SCAN, IR_FILTER, IR_SELECT, IR_HSTACK, IR_GROUPBY, IR_JOIN, IR_SORT, IR_SLICE = range(8)
@@ -134,6 +137,8 @@ SIGNATURES = {
     "plx_strview_match": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int32, C.c_char_p, C.c_int64, _u64p]),
     "plx_strview_match_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "plx_bitmap_lookup": (C.c_int, [C.c_uint64, C.c_uint64, _u64p]),
+    "plx_temporal_part": (C.c_int, [C.c_uint64, C.c_int, C.c_int, _u64p]),
+    "plx_temporal_part_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "plx_strdict_info": (C.c_int, [C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "plx_strdict_to_host": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p]),
     "plx_strdict_free": (C.c_int, [C.c_uint64]),

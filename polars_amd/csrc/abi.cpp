@@ -19,6 +19,7 @@
 #include "scan.hpp"
 #include "sort.hpp"
 #include "strmatch.hpp"
+#include "temporal.hpp"
 
 namespace plx {
 void init_device(int ordinal);
@@ -717,6 +718,51 @@ void _polars_plugin_field_plx_when_then_otherwise(PLX_FIELD_SIG) {
   if (fields && n_fields == 3) plugin_field(fields + 1, 2, out, FIELD_SAME, 0); else plugin_field(nullptr, 0, out, FIELD_SAME, 0);
 }
 void _polars_plugin_field_plx_filter(PLX_FIELD_SIG) { (void)kwargs; (void)kwargs_len; plugin_field(fields, n_fields, out, FIELD_SAME, 0); }
+// dt.<part>() of a Date / Datetime input: kwargs {"part": "year" | "month" | "day" | "quarter" | "weekday" | "ordinal_day" | "hour" | "minute" | "second" | "date",
+// "unit": "date" | "ms" | "us" | "ns"}.  Without "unit" the input's Arrow format says it (tdD, tsm: / tsu: / tsn:).  The output keeps the input's name.
+extern "C++" {
+namespace {
+int dt_part_of(const std::string& s) {
+  static const char* n[] = {"year", "month", "day", "quarter", "weekday", "ordinal_day", "hour", "minute", "second", "date"};
+  for (int i = 0; i < temporal::kNumParts; i++) if (s == n[i]) return i;
+  return -1;
+}
+int dt_unit_of(const std::string& s, const char* format) {
+  static const char* n[] = {"date", "ms", "us", "ns"};
+  for (int i = 0; i < temporal::kNumUnits; i++) if (s == n[i]) return i;
+  if (!s.empty() || !format) return -1;
+  if (!strncmp(format, "tdD", 3)) return temporal::kUnitDate;
+  if (!strncmp(format, "tsm", 3)) return temporal::kUnitMs;
+  if (!strncmp(format, "tsu", 3)) return temporal::kUnitUs;
+  if (!strncmp(format, "tsn", 3)) return temporal::kUnitNs;
+  return -1;
+}
+}  // namespace
+}  // extern "C++"
+void _polars_plugin_plx_dt_part(PLX_PLUGIN_SIG) {
+  const int part = dt_part_of(pickle_str_value(kwargs, kwargs_len, "part"));
+  const int unit = dt_unit_of(pickle_str_value(kwargs, kwargs_len, "unit"), inputs && n_inputs >= 1 && inputs[0].field ? inputs[0].field->format : nullptr);
+  plugin_call(inputs, n_inputs, out, ctx, 1, [&](std::vector<PluginInput>& in) {
+    PLX_REQUIRE(part >= 0, PLX_ERR_INVALID, "plx_dt_part: kwargs must carry part in {year, month, day, quarter, weekday, ordinal_day, hour, minute, second, date}");
+    PLX_REQUIRE(unit >= 0, PLX_ERR_INVALID, "plx_dt_part: kwargs must carry unit in {date, ms, us, ns} (or the input must be a Date / Datetime series)");
+    return ops::temporal_part(in[0].col, part, unit);
+  });
+  if (out && out->private_data && out->field && part == temporal::kDatePart) out->field->format = "tdD";      // the day count leaves as a Date (a static string: release_schema frees the name only)
+}
+void _polars_plugin_field_plx_dt_part(PLX_FIELD_SIG) {
+  const int part = dt_part_of(pickle_str_value(kwargs, kwargs_len, "part"));
+  try {
+    PLX_REQUIRE(fields && n_fields == 1 && out, PLX_ERR_INVALID, "plugin field: bad arguments");
+    PLX_REQUIRE(part >= 0, PLX_ERR_INVALID, "plx_dt_part: kwargs must carry part in {year, month, day, quarter, weekday, ordinal_day, hour, minute, second, date}");
+    memset(out, 0, sizeof(*out));
+    auto* nm = new std::string(fields[0].name ? fields[0].name : "");
+    out->format = part == temporal::kDatePart ? "tdD" : format_of_dtype(ops::temporal_part_dtype(part));
+    out->name = nm->c_str(); out->flags = 2; out->private_data = nm; out->release = release_schema;
+    return;
+  } catch (const plx::Error& e) { t_plugin_error = e.msg; }
+  catch (...) { t_plugin_error = "PANIC"; }
+  if (out) out->release = nullptr;
+}
 
 // ---- synthetic benchmark data --------------------------------------------------------
 int plx_datagen_lineitem_q1(int64_t n_rows, uint64_t seed, plx_column* out_cols) {
@@ -1181,6 +1227,34 @@ int plx_bitmap_lookup(plx_column codes, plx_column lut_bool, plx_column* out_boo
   PLX_TRY
   PLX_REQUIRE(out_bool, PLX_ERR_INVALID, "null pointer");
   *out_bool = register_column(ops::bitmap_lookup(get_column(codes), get_column(lut_bool)));
+  PLX_CATCH
+}
+
+// ---- date parts (kernels_temporal.hip, temporal.hpp) ---------------------------------------------------------------
+static_assert(PLX_UNIT_DATE == temporal::kUnitDate && PLX_UNIT_MS == temporal::kUnitMs && PLX_UNIT_US == temporal::kUnitUs && PLX_UNIT_NS == temporal::kUnitNs &&
+              PLX_PART_YEAR == temporal::kYear && PLX_PART_MONTH == temporal::kMonth && PLX_PART_DAY == temporal::kDay && PLX_PART_QUARTER == temporal::kQuarter &&
+              PLX_PART_WEEKDAY == temporal::kWeekday && PLX_PART_ORDINAL_DAY == temporal::kOrdinalDay && PLX_PART_HOUR == temporal::kHour &&
+              PLX_PART_MINUTE == temporal::kMinute && PLX_PART_SECOND == temporal::kSecond && PLX_PART_DATE == temporal::kDatePart,
+              "polars_amd.h and temporal.hpp disagree");
+int plx_temporal_part(plx_column col, int part, int unit, plx_column* out) {
+  PLX_TRY
+  PLX_REQUIRE(out, PLX_ERR_INVALID, "null pointer");
+  *out = register_column(ops::temporal_part(get_column(col), part, unit));
+  PLX_CATCH
+}
+int plx_temporal_part_host(const void* values, int unit, int part, int64_t n, void* out) {
+  PLX_TRY
+  PLX_REQUIRE(n >= 0 && ((values && out) || n == 0), PLX_ERR_INVALID, "temporal_part_host: bad arguments");
+  PLX_REQUIRE(temporal::part_ok(part, unit), PLX_ERR_INVALID, "temporal_part_host: part " + std::to_string(part) + " of unit " + std::to_string(unit) + " (the time of day and date() exist for a Datetime only)");
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t v = unit == temporal::kUnitDate ? (int64_t)((const int32_t*)values)[i] : ((const int64_t*)values)[i];
+    const int64_t r = temporal::part(v, unit, part);
+    switch (temporal::part_width(part)) {
+      case 4: ((int32_t*)out)[i] = (int32_t)r; break;
+      case 2: ((int16_t*)out)[i] = (int16_t)r; break;
+      default: ((int8_t*)out)[i] = (int8_t)r; break;
+    }
+  }
   PLX_CATCH
 }
 

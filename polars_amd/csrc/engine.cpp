@@ -19,6 +19,7 @@
 #include "kernels_fused.hpp"
 #include "ops.hpp"
 #include "sort.hpp"
+#include "temporal.hpp"
 
 namespace plx {
 namespace engine {
@@ -49,6 +50,11 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       e.lut = get_column(ae[i].lit.u);
       PLX_REQUIRE(e.lut->dtype == PLX_BOOL, PLX_ERR_INVALID, "bitmap lookup: the lookup bitmap must be a Boolean column");
       PLX_REQUIRE(!e.lut->validity || e.lut->null_count == 0 || (e.lut->values && column_null_count(e.lut) == 0), PLX_ERR_INVALID, "bitmap lookup: the lookup bitmap must not hold nulls");
+    }
+    if (e.kind == PLX_AE_TEMPORAL) {
+      PLX_REQUIRE(e.lhs >= 0, PLX_ERR_INVALID, "date part needs a Date / Datetime input (lhs)");
+      PLX_REQUIRE(e.lit.u < (uint64_t)temporal::kNumUnits && temporal::part_ok(e.op, (int)e.lit.u), PLX_ERR_INVALID,
+                  "date part: part " + std::to_string(e.op) + " of unit " + std::to_string((long long)e.lit.i) + " (plx_temporal_part_kind 0..9, plx_time_unit 0..3; the time of day and date() exist for a Datetime only)");
     }
     PLX_REQUIRE(e.lhs < i && e.rhs < i && e.cond < i, PLX_ERR_INVALID, "AExpr arena must be topologically ordered (children before parents)");
     p.ae.push_back(std::move(e));
@@ -102,6 +108,9 @@ static bool is_cmp_op(int op) { return op >= PLX_OP_EQ && op <= PLX_OP_GE; }
 static bool is_arith_op(int op) { return op >= PLX_OP_PLUS && op <= PLX_OP_MODULUS; }
 static bool is_logic_op(int op) { return op >= PLX_OP_AND && op <= PLX_OP_XOR; }
 
+// the physical dtype a PLX_AE_TEMPORAL node's unit asks of its operand
+static int temporal_input_dtype(const AE& x) { return (int)x.lit.u == temporal::kUnitDate ? PLX_I32 : PLX_I64; }
+
 int infer_dtype(const Plan& plan, int e, const Frame& schema) {
   const AE& x = plan.ae.at(e);
   switch (x.kind) {
@@ -119,6 +128,11 @@ int infer_dtype(const Plan& plan, int e, const Frame& schema) {
       const int in = infer_dtype(plan, x.lhs, schema);
       PLX_REQUIRE(dtype_is_int(in), PLX_ERR_INVALID, std::string("bitmap lookup: the input must be an integer expression, not ") + dtype_name(in));
       return PLX_BOOL;
+    }
+    case PLX_AE_TEMPORAL: {
+      const int in = infer_dtype(plan, x.lhs, schema);
+      PLX_REQUIRE(in == temporal_input_dtype(x), PLX_ERR_INVALID, std::string("date part: a Date is an Int32 expression and a Datetime an Int64 expression, not ") + dtype_name(in) + " (unit " + std::to_string((int)x.lit.u) + ")");
+      return ops::temporal_part_dtype(x.op);
     }
     case PLX_AE_TERNARY: {
       const int l = infer_dtype(plan, x.lhs, schema), r = infer_dtype(plan, x.rhs, schema);
@@ -224,6 +238,10 @@ static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<i
     case PLX_AE_BITMAP_LOOKUP: {
       Evaluated c = eval(plan, x.lhs, df, overrides);
       return {ops::bitmap_lookup(c.col, x.lut), c.scalar};
+    }
+    case PLX_AE_TEMPORAL: {
+      Evaluated c = eval(plan, x.lhs, df, overrides);
+      return {ops::temporal_part(c.col, x.op, (int)x.lit.u), c.scalar};
     }
     case PLX_AE_TERNARY: {
       // a length-1 operand broadcasts inside the kernel (select_kernel's scalar forms); all three scalar: a scalar
@@ -426,6 +444,13 @@ class Compiler {
         if (!dtype_is_int(in)) fail(PLX_ERR_INVALID, std::string("bitmap lookup: the input must be an integer expression, not ") + dtype_name(in));
         const int a = lower(x.lhs);
         return bit_lookup(a, static_lut(x.lut), 0);
+      }
+      case PLX_AE_TEMPORAL: {
+        infer_dtype(plan, e, *df);      // (fails when the operand is not I32 with unit Date / I64 with a Datetime unit)
+        const int a = lower(x.lhs);
+        // one source, no immediate; part and unit ride in Op::c, i.e. in the Shape: the compiled kernels fold the switch.  The result is the 64-bit widening of the
+        // part's dtype, nullable exactly when the operand is
+        return mk(OP_DATEPART, a, a, 'i', temporal::pack(x.op, (int)x.lit.u));
       }
       case PLX_AE_TERNARY: {
         const int dt = infer_dtype(plan, e, *df);      // (fails when the branches differ in dtype or the predicate is not Boolean)
@@ -713,6 +738,13 @@ static const AE* plain_column(const Plan& plan, int e) {
   while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs];
   return x->kind == PLX_AE_COLUMN ? x : nullptr;
 }
+// the date-part node behind any aliases of expression `e`, or null
+static const AE* temporal_node(const Plan& plan, int e) {
+  const AE* x = &plan.ae[e];
+  while (x->kind == PLX_AE_ALIAS) x = &plan.ae[x->lhs];
+  return x->kind == PLX_AE_TEMPORAL ? x : nullptr;
+}
+static bool temporal_key_ranges() { const char* e = getenv("PLX_TEMPORAL_KEY_RANGES"); return !(e && e[0] == '0'); }   // (measurement: 0 = a date part is a raw 64-bit key, as any expression)
 static KeyPlan lower_keys(Compiler& c, const std::vector<int>& key_exprs) {
   KeyPlan kp;
   const Plan& plan = c.plan;
@@ -728,7 +760,32 @@ static KeyPlan lower_keys(Compiler& c, const std::vector<int>& key_exprs) {
     info[i].nullable = c.nodes[knodes[i]].nullable;
     part.nullable = info[i].nullable;
     const AE* x = plain_column(plan, e);
+    const AE* tp = temporal_key_ranges() ? temporal_node(plan, e) : nullptr;
     if (part.dtype == PLX_BOOL) { info[i].have_range = true; info[i].mn = 0; info[i].mx = 1; }
+    else if (tp) {
+      // A date part's range is known without looking at the data: month 1..12, weekday 1..7, ... -- exact by construction, so nothing here is a guess and nothing
+      // needs the per-row check.  year and date are monotone in the value: year(min) .. year(max) of a plain column's own range, taken under the rules a column key's
+      // range is (exact statistics, one pass cached on the immutable column; bounds the planner only guessed count when every row has been checked against them since;
+      // bounds the caller declared make the table sinks check every row, as they do for the column itself: untrusted_key_bounds looks at the program's inputs).
+      // Anything else under the part (an expression, a ms Datetime whose days leave i32) stays a raw 64-bit key.
+      const int tpart = tp->op, tunit = (int)tp->lit.u;
+      if (tpart != temporal::kYear && tpart != temporal::kDatePart) { info[i].have_range = true; info[i].mn = temporal::part_min(tpart); info[i].mx = temporal::part_max(tpart); }
+      else if (const AE* cx = plain_column(plan, tp->lhs)) {
+        ColumnPtr col = c.df->cols[c.df->find(cx->name)];
+        int64_t cmn = 0, cmx = 0;
+        bool have = false;
+        if (col->values && ops::int_range(col, &cmn, &cmx, col->range_verified)) have = true;
+        else if (col->range_state == 1) { have = true; cmn = col->range_min; cmx = col->range_max; }
+        else if (col->range_state == 2) have = true;      // no valid row: any range will do
+        const int64_t tpd = temporal::ticks_per_day(tunit);
+        auto day_of = [&](int64_t v) { return tunit == temporal::kUnitDate ? (int64_t)(int32_t)v : (v / tpd - ((v % tpd) < 0 ? 1 : 0)); };
+        if (have && tpart == temporal::kDatePart && (day_of(cmn) < temporal::kI32Min || day_of(cmx) > temporal::kI32Max)) have = false;      // (the low 32 bits of such a day count are not monotone)
+        if (have) {
+          info[i].have_range = true; info[i].mn = temporal::part(cmn, tunit, tpart); info[i].mx = temporal::part(cmx, tunit, tpart);
+          kp.note += "KeyRange{" + std::string(cx->name) + (tpart == temporal::kYear ? ".dt.year" : ".dt.date") + ": " + std::to_string(info[i].mn) + ".." + std::to_string(info[i].mx) + " from the column's range}; ";
+        } else all_packable = false;
+      } else all_packable = false;
+    }
     else if (dtype_is_int(part.dtype) && x) {
       ColumnPtr col = c.df->cols[c.df->find(x->name)];
       bool cheap = dtype_width(part.dtype) <= 2 || nk > 1 || col->range_state != 0;

@@ -63,7 +63,10 @@ enum OpCode : uint8_t {
   OP_SELECT,
   // dst <- args.dict[c][a], with the validity of a: the value of a dictionary-encoded input (Column::shadow) from its one-byte code.  Every dictionary holds kDictSlots
   // words, so any code a u8 / u16 load can produce after the mask stays inside it
-  OP_DICT
+  OP_DICT,
+  // dst <- a part (year, month, ..., temporal.hpp) of the Date / Datetime value a, with the validity of a.  c = temporal::pack(part, unit): both are part of the Shape,
+  // so the compiled kernels carry one part's arithmetic with constant divisors.  One source slot (a == b), no immediate
+  OP_DATEPART
 };
 
 struct Op {

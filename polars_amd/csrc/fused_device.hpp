@@ -7,6 +7,7 @@
 #include "fused.hpp"
 #include "fused_shapes.hpp"
 #include "kconfig.hpp"
+#include "temporal.hpp"
 
 namespace plx {
 namespace k {
@@ -374,6 +375,12 @@ __device__ __forceinline__ void exec_op(const Op op, const Shape& sh, const Args
         }
         vd = va;
       } break;
+      case OP_DATEPART:   // unit and part are constants of a compiled program (op.c comes from the Shape): one part's multiply-high chain is left of temporal::part; in the
+                          // interpreter its branches are wave-uniform (and it holds every division once: see there)
+#pragma unroll
+        for (int r = 0; r < kRows; r++) d[r] = (uint64_t)temporal::part((int64_t)a[r], temporal::unit_of(op.c), temporal::part_of(op.c));
+        vd = va;
+        break;
       default:  // OP_MOV / OP_NOP
 #pragma unroll
         for (int r = 0; r < kRows; r++) d[r] = a[r];

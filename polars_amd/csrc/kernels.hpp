@@ -80,6 +80,11 @@ void datagen_id_views(int64_t n, uint64_t seed, uint32_t stream, int64_t lo, int
 // 20-byte strings "id%010d-longkey": views {20, prefix, buffer 0, offset} into out_pool[(hi - lo) * 20], which holds every distinct string once
 void datagen_long_id_views(int64_t n, uint64_t seed, uint32_t stream, int64_t lo, int64_t hi, uint64_t* out_views, uint8_t* out_pool);
 
+// ---- date parts (kernels_temporal.hip; the arithmetic: temporal.hpp) ----------------------------------------
+// out[i] = part `part` (plx_temporal_part_kind) of in[i], a Date (i32 days, unit 0) or a Datetime (i64 ticks, unit 1 ms / 2 us / 3 ns); out has the part's width
+// (temporal::part_width).  Every row is computed, null or not: the caller shares the input's validity with the result
+void temporal_part(int unit, int part, const void* in, int64_t n, void* out);
+
 // ---- string predicates (kernels_strmatch.hip; the per-string decision: strmatch.hpp) ----------------------
 // str.starts_with (kind 0) / ends_with (1) / contains of a literal (2), decided for n 16-byte views: out_bits = the answers, out_valid = which rows are not null (both
 // sized bitmap_bytes(n); bits past n are zero).  The caller has checked kind and pattern (at most strmatch::kMaxPattern = 64 bytes).  validity (may be null) and / or

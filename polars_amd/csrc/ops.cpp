@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "temporal.hpp"
 
 namespace plx {
 
@@ -373,6 +374,22 @@ ColumnPtr bitmap_lookup(const ColumnPtr& codes, const ColumnPtr& lut) {
   out->values = dev_alloc(bitmap_bytes(codes->len));
   k::bitmap_lookup(codes->dtype, codes->data(), codes->valid_words(), codes->len, lut->values ? lut->values->as<uint64_t>() : nullptr, (uint64_t)lut->len, out->values->as<uint64_t>());
   out->validity = codes->validity; out->null_count = codes->null_count;
+  return out;
+}
+
+// dt.year() ... dt.date() per node (reference: crates/polars-time/src/chunkedarray/{date,datetime}.rs over the arrow temporal kernels)
+int temporal_part_dtype(int part) { return temporal::part_width(part) == 4 ? PLX_I32 : temporal::part_width(part) == 2 ? PLX_I16 : PLX_I8; }
+ColumnPtr temporal_part(const ColumnPtr& c, int part, int unit) {
+  PLX_REQUIRE(temporal::unit_ok(unit) && part >= 0 && part < temporal::kNumParts, PLX_ERR_INVALID, "temporal part: part " + std::to_string(part) + " / unit " + std::to_string(unit) + " out of range");
+  PLX_REQUIRE(c->dtype == (unit == temporal::kUnitDate ? PLX_I32 : PLX_I64), PLX_ERR_INVALID,
+              std::string("temporal part: a Date is an Int32 column and a Datetime an Int64 column, got ") + dtype_name(c->dtype) + " with unit " + std::to_string(unit));
+  PLX_REQUIRE(temporal::part_ok(part, unit), PLX_ERR_INVALID, "temporal part: the time of day and date() exist for a Datetime only");
+  PLX_REQUIRE(c->values || c->len == 0, PLX_ERR_INVALID, "placeholder column has no data");
+  auto out = std::make_shared<Column>();
+  out->dtype = temporal_part_dtype(part); out->len = c->len;
+  out->values = dev_alloc(values_bytes(out->dtype, c->len));
+  k::temporal_part(unit, part, c->data(), c->len, out->values->ptr);
+  out->validity = c->validity; out->null_count = c->null_count;
   return out;
 }
 

@@ -38,6 +38,10 @@ ColumnPtr if_then_else(const ColumnPtr& mask, const ColumnPtr& a, const ColumnPt
 // set membership over a dense code range: out[i] = lut bit codes[i] (false outside [0, len(lut))), null where codes[i] is; codes: any integer dtype (a length-1
 // column stays length 1), lut: Boolean without nulls
 ColumnPtr bitmap_lookup(const ColumnPtr& codes, const ColumnPtr& lut);
+// dt.<part>(): the part (plx_temporal_part_kind) of a Date (PLX_I32, unit PLX_UNIT_DATE) or Datetime (PLX_I64, a Datetime unit) column in the part's own dtype
+// (part_dtype); the result shares the input's validity bitmap
+ColumnPtr temporal_part(const ColumnPtr& c, int part, int unit);
+int temporal_part_dtype(int part);
 plx_scalar scalar_of(const ColumnPtr& c, bool* valid);         // value and validity of row 0 (a length-1 column), read back to the host
 ColumnPtr concat(const std::vector<ColumnPtr>& chunks);
 ColumnPtr slice_copy(const ColumnPtr& c, int64_t offset, int64_t len);

@@ -102,6 +102,11 @@ class Expr:
         """String predicates on a dictionary-encoded (Categorical) column: str.starts_with / ends_with / contains of a literal."""
         return ExprStringNameSpace(self)
 
+    @property
+    def dt(self) -> "ExprDateTimeNameSpace":
+        """The parts of a Date / Datetime column: dt.year / month / day / quarter / weekday / ordinal_day / hour / minute / second / date."""
+        return ExprDateTimeNameSpace(self)
+
     def alias(self, name: str) -> "Expr": return Expr("alias", lhs=self, name=name)
     def cast(self, dtype: T.DataType) -> "Expr": return Expr("cast", lhs=self, dtype=dtype)
 
@@ -116,6 +121,7 @@ class Expr:
         if self.kind in ("is_null", "is_not_null"): return f"{self.lhs!r}.{self.kind}()"
         if self.kind == "fill_null": return f"{self.lhs!r}.fill_null({self.rhs!r})"
         if self.kind == "str_match": return f"{self.lhs!r}.str.{STR_MATCH_NAMES[self.op]}({self.value!r})"
+        if self.kind == "dt_part": return f"{self.lhs!r}.dt.{DT_PART_NAMES[self.op]}()"
         if self.kind == "ternary":
             return f"when({self.cond!r}).then({self.lhs!r})" + (f".otherwise({self.rhs!r})" if self.rhs is not None else "")
         return self.kind
@@ -174,6 +180,51 @@ class ExprStringNameSpace:
         if not literal:
             raise TypeError("str.contains(literal=False): regular expressions are not on this path; pass literal=True (the default here) for a substring test")
         return self._match(F.STR_CONTAINS, pattern)
+
+
+DT_PART_NAMES = {F.PART_YEAR: "year", F.PART_MONTH: "month", F.PART_DAY: "day", F.PART_QUARTER: "quarter", F.PART_WEEKDAY: "weekday",
+                 F.PART_ORDINAL_DAY: "ordinal_day", F.PART_HOUR: "hour", F.PART_MINUTE: "minute", F.PART_SECOND: "second", F.PART_DATE: "date"}
+DT_DATETIME_ONLY = (F.PART_HOUR, F.PART_MINUTE, F.PART_SECOND, F.PART_DATE)      # the time of day, and the day of an instant: a Date has neither
+
+
+def dt_part_dtype(part: int) -> T.DataType:
+    """Output dtype of a date part, as the reference's: year Int32, ordinal_day Int16, date Date, every other part Int8."""
+    return T.Int32 if part == F.PART_YEAR else T.Int16 if part == F.PART_ORDINAL_DAY else T.Date if part == F.PART_DATE else T.Int8
+
+
+def dt_unit(dtype: T.DataType, part: int) -> int:
+    """plx_time_unit of a logical dtype for dt.<part>(); TypeError for a dtype that is not temporal, and for the time of day or date() of a Date."""
+    name = DT_PART_NAMES[part]
+    if isinstance(dtype, T.DatetimeType):
+        return {"ms": F.UNIT_MS, "us": F.UNIT_US, "ns": F.UNIT_NS}[dtype.time_unit]
+    if dtype == T.Date:
+        if part in DT_DATETIME_ONLY:
+            raise TypeError(f"dt.{name}() needs a Datetime column, got Date" + (" (a Date has no time of day)" if part != F.PART_DATE else " (it is a date already)"))
+        return F.UNIT_DATE
+    raise TypeError(f"dt.{name}() needs a Date or Datetime column, got {'a literal' if dtype is None else dtype}")
+
+
+class ExprDateTimeNameSpace:
+    """pl.col("d").dt: the date parts of py-polars' expr.dt that are on the hot path.  The result is an ordinary integer expression (Date for dt.date()), null where
+    the value is null, named like the column: a filter operand, a group key (its range is known without a pass over the data; year and date take it from the column's range), an aggregate source, a branch of
+    when/then/otherwise or an output column.  Proleptic Gregorian calendar; weekday is ISO (Monday = 1 .. Sunday = 7)."""
+
+    def __init__(self, expr: Expr):
+        self._expr = expr
+
+    def _part(self, part: int) -> Expr:
+        return Expr("dt_part", op=part, lhs=self._expr)
+
+    def year(self) -> Expr: return self._part(F.PART_YEAR)
+    def month(self) -> Expr: return self._part(F.PART_MONTH)
+    def day(self) -> Expr: return self._part(F.PART_DAY)
+    def quarter(self) -> Expr: return self._part(F.PART_QUARTER)
+    def weekday(self) -> Expr: return self._part(F.PART_WEEKDAY)
+    def ordinal_day(self) -> Expr: return self._part(F.PART_ORDINAL_DAY)
+    def hour(self) -> Expr: return self._part(F.PART_HOUR)
+    def minute(self) -> Expr: return self._part(F.PART_MINUTE)
+    def second(self) -> Expr: return self._part(F.PART_SECOND)
+    def date(self) -> Expr: return self._part(F.PART_DATE)
 
 
 def _as_expr(x: Any) -> Expr:

@@ -15,7 +15,7 @@ import numpy as np
 from . import _ffi as F
 from . import datatypes as T
 from . import plan as P
-from .expr import STR_MATCH_NAMES, Expr, col as _col, str_match_host, str_pattern_bytes
+from .expr import STR_MATCH_NAMES, Expr, col as _col, dt_part_dtype, dt_unit, str_match_host, str_pattern_bytes
 
 
 def _pack_validity(valid: np.ndarray) -> np.ndarray:
@@ -401,8 +401,39 @@ class Series:
         """String predicates (starts_with / ends_with / contains of a literal) on a dictionary column or on a column of raw views."""
         return SeriesStringNameSpace(self)
 
+    @property
+    def dt(self) -> "SeriesDateTimeNameSpace":
+        """The parts of a Date / Datetime column (year, month, day, quarter, weekday, ordinal_day, hour, minute, second, date), one kernel each."""
+        return SeriesDateTimeNameSpace(self)
+
     def __repr__(self) -> str:
         return f"Series({self.name!r}, {self.dtype}, len={len(self)})"
+
+
+class SeriesDateTimeNameSpace:
+    """Series.dt: a date part per row (plx_temporal_part), in the part's own dtype, null where the value is null, named like the column."""
+
+    def __init__(self, s: "Series"):
+        self._s = s
+
+    def _part(self, part: int) -> "Series":
+        s = self._s
+        unit = dt_unit(s.dtype, part)          # TypeError: not temporal, or the time of day / date() of a Date
+        F.ensure_init()
+        h = C.c_uint64()
+        F.check(F.lib().plx_temporal_part(s._h, part, unit, C.byref(h)))
+        return Series._from_handle(s.name, h.value, dt_part_dtype(part))
+
+    def year(self) -> "Series": return self._part(F.PART_YEAR)
+    def month(self) -> "Series": return self._part(F.PART_MONTH)
+    def day(self) -> "Series": return self._part(F.PART_DAY)
+    def quarter(self) -> "Series": return self._part(F.PART_QUARTER)
+    def weekday(self) -> "Series": return self._part(F.PART_WEEKDAY)
+    def ordinal_day(self) -> "Series": return self._part(F.PART_ORDINAL_DAY)
+    def hour(self) -> "Series": return self._part(F.PART_HOUR)
+    def minute(self) -> "Series": return self._part(F.PART_MINUTE)
+    def second(self) -> "Series": return self._part(F.PART_SECOND)
+    def date(self) -> "Series": return self._part(F.PART_DATE)
 
 
 class SeriesStringNameSpace:

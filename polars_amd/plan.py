@@ -15,7 +15,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 from . import _ffi as F
 from . import datatypes as T
-from .expr import STR_MATCH_NAMES, Expr, literal_physical, str_match_host, str_pattern_bytes
+from .expr import STR_MATCH_NAMES, Expr, dt_part_dtype, dt_unit, literal_physical, str_match_host, str_pattern_bytes
 
 Schema = Dict[str, T.DataType]
 
@@ -200,6 +200,8 @@ class Lowering:
             return self._lower_ternary(e, schema)
         if k == "str_match":
             return self._lower_str_match(e, schema)
+        if k == "dt_part":
+            return self._lower_dt_part(e, schema)
         raise TypeError(f"unsupported expression {e!r}")
 
     def _lower_string_compare(self, e: Expr, schema: Schema):
@@ -259,6 +261,16 @@ class Lowering:
         self.lut_columns.append(lut)
         self.notes.append(f"str.{what}({e.value!r}) over {len(cats)} categories [{where}]")
         return self._push(kind=F.AE_BITMAP_LOOKUP, lhs=ci, lut=lut), T.Boolean
+
+    def _lower_dt_part(self, e: Expr, schema: Schema):
+        """dt.<part>() of a Date / Datetime expression: AE_TEMPORAL with the part in `op` and the operand's unit (plx_time_unit) in the literal slot -- the engine sees
+        physical Int32 / Int64 values and cannot tell a Date from a count, or microseconds from nanoseconds, any other way."""
+        ci, cdt = self._lower_maybe_dyn(e.lhs, schema)
+        unit = dt_unit(None if isinstance(ci, tuple) else cdt, e.op)          # TypeError: not temporal, or the time of day / date() of a Date
+        note = f"{e!r} [{'Date' if unit == F.UNIT_DATE else 'Datetime[' + cdt.time_unit + ']'}]"              # the expression as written, for pl.last_plan() / explain()
+        if note not in self.notes:
+            self.notes.append(note)
+        return self._push(kind=F.AE_TEMPORAL, op=e.op, lhs=ci, lit=unit), dt_part_dtype(e.op)
 
     def _lower_mixed_time_units(self, op: int, li: int, ldt, ri: int, rdt):
         """Datetime column <cmp> Datetime literal of another time unit (a python datetime is "us").  The reference coerces both sides to
@@ -476,6 +488,8 @@ class Lowering:
                     a.lit.u = int(d["lit"]) & 0xFFFFFFFFFFFFFFFF
                 else:
                     a.lit.i = int(d["lit"])
+            if d["kind"] == F.AE_TEMPORAL:
+                a.lit.u = int(d["lit"])            # the operand's time unit rides in the literal slot, like a lookup bitmap's handle
             if d["kind"] == F.AE_BITMAP_LOOKUP:
                 a.lit.u = d["lut"]._h              # the lookup bitmap's column handle rides in the literal slot (plx_aexpr.lit)
                 keep.append(d["lut"])

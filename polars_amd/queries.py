@@ -62,6 +62,24 @@ def q6(lineitem, year: int = 1994, discount: float = 0.06, quantity: int = 24):
             .select((c("l_extendedprice") * c("l_discount")).sum().alias("revenue")))
 
 
+def q6_year(lineitem, year: int = 1994, discount: float = 0.06, quantity: int = 24):
+    """TPC-H Q6 with the year as the query states it: l_shipdate.dt.year() == year instead of q6's two date literals.  The year is computed inside the scan."""
+    c = E.col
+    return (lineitem.filter((c("l_shipdate").dt.year() == year) & c("l_discount").is_between(round(discount - 0.01, 2), round(discount + 0.01, 2))
+                            & (c("l_quantity") < quantity))
+            .select((c("l_extendedprice") * c("l_discount")).sum().alias("revenue")))
+
+
+def revenue_by_ship_month(lineitem, cutoff=Q1_CUTOFF):
+    """Revenue per calendar month: lineitem[l_shipdate <= cutoff] grouped by (year, month) of l_shipdate -- the grouping of TPC-H Q7 / Q8 / Q9 (extract(year from ...))
+    and of every "per month" report.  Both keys are computed inside the scan; their ranges are known without a pass over the data (month) or from the column's own
+    range (year), so the pair packs into a few bits and takes the dense table routes."""
+    c = E.col
+    return (lineitem.filter(c("l_shipdate") <= cutoff)
+            .group_by(c("l_shipdate").dt.year().alias("year"), c("l_shipdate").dt.month().alias("month"))
+            .agg((c("l_extendedprice") * (1 - c("l_discount"))).sum().alias("revenue"), E.len().alias("n")))
+
+
 def q3(lineitem, orders, date=Q3_DATE, seg_mod=5):
     """TPC-H Q3 restated on the two big tables (SURVEY.md 8(d) cfg 4): the customer
     market-segment filter is approximated by o_custkey % seg_mod == 0."""
