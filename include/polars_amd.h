@@ -230,6 +230,19 @@ int plx_column_placeholder_encoding(plx_column col, int32_t kind, int32_t width,
 /* The affine chooser of the encoded shadows, a pure function: from the exact minimum / maximum of a column's valid rows and gcd = gcd(v - min) over them (0: not
  * computed) -> whether the column encodes, code width in bytes, base and stride.  needs_gcd: the span alone does not decide, the gcd pass has to run. */
 int plx_encoding_choose_affine(int64_t min, int64_t max, uint64_t gcd, int32_t* ok, int32_t* width, int64_t* base, uint64_t* stride, int32_t* needs_gcd);
+/* The decimal shadow of an f64 column (kind 3, four-byte codes): value = (double)(int64)(base + code) / 10^e, e in 0..9.  plx_column_placeholder_encoding takes kind 3
+ * with width 4, the exponent in `stride` and the base as is.  The three functions below are the host twins of what the device runs (one shared header), pure
+ * functions over host memory:
+ *   choose_decimal  the chooser over the valid rows of `values` (validity: LSB-first bitmap or null): the smallest exponent at which every row is k / 10^e bit for
+ *                   bit, base 0 when every k lies in [0, 2^32), else the minimum; ok = 0 for NaN, +-inf, -0.0, |k| >= 2^53, a span of 2^32 or a non-decimal;
+ *   decimal_decode  out[i] = the value of codes[i];
+ *   decimal_encode  codes[i] / ok[i] = the code of values[i] under (base, e), or ok[i] = 0 when the row has none (the encoder's mismatch). */
+int plx_encoding_choose_decimal(const double* values, const uint8_t* validity, int64_t n, int32_t* ok, int32_t* e, int64_t* base);
+int plx_encoding_decimal_decode(int64_t base, int32_t e, const uint32_t* codes, int64_t n, double* out);
+int plx_encoding_decimal_encode(const double* values, int64_t n, int64_t base, int32_t e, uint32_t* codes, uint8_t* ok);
+/* f64 columns of at least min_rows rows may get a decimal shadow (it takes half the column's bytes; default 2^22, environment PLX_ENCODED_DECIMAL_MIN_ROWS). */
+int plx_encoded_set_decimal_min_rows(int64_t min_rows);
+int64_t plx_encoded_decimal_min_rows(void);
 /* Caller-provided value bounds of an integer column (dictionary size of a Categorical, Parquet column-chunk min / max
  * statistics): every valid value lies in [lo, hi].  The planner uses them the way the reference uses sortedness flags and
  * metadata statistics -- to choose dense / direct-address group tables without a pass over the data.  Kernels that rely on

@@ -127,6 +127,11 @@ SIGNATURES = {
     "plx_column_placeholder": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, _u64p]),
     "plx_column_placeholder_encoding": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.c_uint64]),
     "plx_encoding_choose_affine": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, _i32p, _i32p, C.POINTER(C.c_int64), _u64p, _i32p]),
+    "plx_encoding_choose_decimal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _i32p, _i32p, C.POINTER(C.c_int64)]),
+    "plx_encoding_decimal_decode": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "plx_encoding_decimal_encode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "plx_encoded_set_decimal_min_rows": (C.c_int, [C.c_int64]),
+    "plx_encoded_decimal_min_rows": (C.c_int64, []),
     "plx_column_set_bounds": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64]),
     "plx_column_drop_statistics": (C.c_int, [C.c_uint64]),
     "plx_strview_dict_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, _u64p, _u64p]),
@@ -288,13 +293,22 @@ def last_plan() -> str:
 
 
 def last_plan_encodings() -> str:
-    """The inputs the last collect()'s fused aggregate scans read through their encoded shadows ("encoded{l_shipdate:affine16,l_discount:dict8}; "), or ""."""
+    """The inputs the last collect()'s fused aggregate scans read through their encoded shadows ("encoded{l_shipdate:affine16,l_discount:dict8,l_extendedprice:decimal32}; "), or ""."""
     return lib().plx_last_plan_encodings().decode()
 
 
 def jit_set_min_rows(min_rows: int) -> None:
     """Inputs of at least ``min_rows`` rows get a run-time specialised kernel (hiprtc); negative disables the JIT."""
     check(lib().plx_jit_set_min_rows(int(min_rows)))
+
+
+def encoded_set_decimal_min_rows(min_rows: int) -> None:
+    """f64 columns of at least ``min_rows`` rows may get a four-byte decimal shadow (default 2**22, PLX_ENCODED_DECIMAL_MIN_ROWS)."""
+    check(lib().plx_encoded_set_decimal_min_rows(int(min_rows)))
+
+
+def encoded_decimal_min_rows() -> int:
+    return int(lib().plx_encoded_decimal_min_rows())
 
 
 def jit_stats():

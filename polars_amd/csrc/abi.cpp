@@ -109,7 +109,8 @@ int plx_column_placeholder_encoding(plx_column col, int32_t kind, int32_t width,
   PLX_TRY
   ColumnPtr c = get_column(col);
   PLX_REQUIRE(!c->values, PLX_ERR_INVALID, "placeholder_encoding: placeholder columns only");
-  PLX_REQUIRE((kind == EncodedShadow::kAffine || kind == EncodedShadow::kDict) && (width == 1 || width == 2) && stride >= 1, PLX_ERR_INVALID, "placeholder_encoding: kind 1 | 2, width 1 | 2, stride >= 1");
+  if (kind == EncodedShadow::kDecimal) PLX_REQUIRE(width == 4 && stride <= (uint64_t)decimal::kMaxExp && c->dtype == PLX_F64, PLX_ERR_INVALID, "placeholder_encoding: kind 3 takes an f64 column, width 4 and the exponent 0..9 as stride");
+  else PLX_REQUIRE((kind == EncodedShadow::kAffine || kind == EncodedShadow::kDict) && (width == 1 || width == 2) && stride >= 1, PLX_ERR_INVALID, "placeholder_encoding: kind 1 | 2, width 1 | 2, stride >= 1");
   auto s = std::make_shared<EncodedShadow>();
   s->kind = kind; s->width = width; s->base = base; s->stride = stride;
   std::atomic_store(&c->shadow, s);
@@ -125,6 +126,33 @@ int plx_encoding_choose_affine(int64_t mn, int64_t mx, uint64_t gcd, int32_t* ok
   if (needs_gcd) *needs_gcd = enc::affine_needs_gcd(mn, mx) ? 1 : 0;
   PLX_CATCH
 }
+
+int plx_encoding_choose_decimal(const double* values, const uint8_t* validity, int64_t n, int32_t* ok, int32_t* e, int64_t* base) {
+  PLX_TRY
+  PLX_REQUIRE(n >= 0 && (values || n == 0), PLX_ERR_INVALID, "choose_decimal: bad arguments");
+  decimal::Stats st;
+  decimal::stats_init(st);
+  for (int64_t i = 0; i < n; i++) if (!validity || ((validity[i >> 3] >> (i & 7)) & 1)) decimal::stats_row(st, values[i]);
+  const decimal::Choice ch = decimal::choose(st);
+  if (ok) *ok = ch.ok ? 1 : 0;
+  if (e) *e = ch.e;
+  if (base) *base = ch.base;
+  PLX_CATCH
+}
+int plx_encoding_decimal_decode(int64_t base, int32_t e, const uint32_t* codes, int64_t n, double* out) {
+  PLX_TRY
+  PLX_REQUIRE(n >= 0 && ((codes && out) || n == 0) && e >= 0 && e <= decimal::kMaxExp, PLX_ERR_INVALID, "decimal_decode: bad arguments");
+  for (int64_t i = 0; i < n; i++) out[i] = decimal::decode(base, codes[i], e);
+  PLX_CATCH
+}
+int plx_encoding_decimal_encode(const double* values, int64_t n, int64_t base, int32_t e, uint32_t* codes, uint8_t* ok) {
+  PLX_TRY
+  PLX_REQUIRE(n >= 0 && ((values && codes && ok) || n == 0) && e >= 0 && e <= decimal::kMaxExp, PLX_ERR_INVALID, "decimal_encode: bad arguments");
+  for (int64_t i = 0; i < n; i++) { uint32_t c = 0; ok[i] = decimal::encode_row(values[i], base, e, &c) ? 1 : 0; codes[i] = ok[i] ? c : 0; }
+  PLX_CATCH
+}
+int plx_encoded_set_decimal_min_rows(int64_t min_rows) { PLX_TRY engine::encoded_set_decimal_min_rows(min_rows); PLX_CATCH }
+int64_t plx_encoded_decimal_min_rows(void) { return engine::encoded_decimal_min_rows(); }
 
 int plx_column_set_bounds(plx_column col, int64_t lo, int64_t hi) {
   PLX_TRY

@@ -100,11 +100,11 @@ void pool_trim(bool force = false);   // force: the reserved block (pool_reserve
 // An exact narrow copy of a column for the fused aggregate scans (encoded_inputs.hpp; engine.cpp encoded_shadow_for_scan), and what the engine remembers on the way
 // to one.  Immutable once published: a change is a new object (std::atomic_store on Column::shadow, like key_sample).
 struct EncodedShadow {
-  enum Kind { kNone = 0, kAffine = 1, kDict = 2 };
+  enum Kind { kNone = 0, kAffine = 1, kDict = 2, kDecimal = 3 };
   int kind = kNone;         // kNone: no codes (yet); only `scans` / `never_encode` mean anything
-  int width = 0;            // bytes per code: 1 | 2
-  int64_t base = 0;         // affine: value = base + stride * code
-  uint64_t stride = 1;
+  int width = 0;            // bytes per code: 1 | 2; decimal: 4
+  int64_t base = 0;         // affine: value = base + stride * code; decimal: value = (double)(base + code) / 10^stride (decimal.hpp)
+  uint64_t stride = 1;      // decimal: the exponent e, 0..9
   Buf codes;                // one code per row (null rows: code 0); the validity bitmap stays the column's own
   Buf dict;                 // dict: fused::kDictSlots u64 bit patterns in HBM, sorted, n_dict in use
   int n_dict = 0;

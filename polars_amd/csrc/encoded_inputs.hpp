@@ -5,10 +5,12 @@
 // column in its place:
 //   affine  integer column, value = base + stride * code          -> OP_LOAD(u8 | u16), [OP_MUL_I CONST stride], [OP_ADD_I CONST base]
 //   dict    f64 column by BIT PATTERN, value = dict[code]         -> OP_LOAD(u8), OP_DICT
+//   decimal f64 column of decimals, value = (base + code) / 10^e  -> OP_LOAD(u32), [OP_ADD_I CONST base], OP_DEC10(e)   (decimal.hpp)
 // This header holds the host-side pieces with no device dependency: the affine chooser and the rewrite of a compiled program (both pure functions, exposed through the
 // C ABI for the tests), and the launchers of the encoder kernels (kernels_encode.hip).
 #pragma once
 #include "core.hpp"
+#include "decimal.hpp"
 #include "fused.hpp"
 
 namespace plx {
@@ -40,7 +42,7 @@ struct InputEncoding {
   int kind = 0;                                 // EncodedShadow::Kind
   int width = 0;
   int64_t base = 0;
-  uint64_t stride = 1;
+  uint64_t stride = 1;                          // decimal: the exponent
   const void* codes = nullptr;
   const unsigned long long* dict = nullptr;
 };
@@ -62,12 +64,16 @@ inline bool encode_program(const fused::Shape& sh, const fused::Args& a, const I
   uint32_t did = 0;
   for (int i = 0; i < sh.n_inputs; i++) {
     const InputEncoding& ei = e[i];
-    if (!ei.kind || load_of[i] < 0 || (ei.width != 1 && ei.width != 2)) continue;
+    if (!ei.kind || load_of[i] < 0 || (ei.kind == 3 ? ei.width != 4 || ei.stride > (uint64_t)decimal::kMaxExp : ei.width != 1 && ei.width != 2)) continue;
     const uint8_t slot = sh.ops[load_of[i]].dst;
-    const bool mul = ei.kind == 1 && ei.stride != 1, add = ei.kind == 1 && ei.base != 0;
-    const int extra = ei.kind == 2 ? 1 : 2 * ((mul ? 1 : 0) + (add ? 1 : 0));
+    const bool mul = ei.kind == 1 && ei.stride != 1, add = ei.kind != 2 && ei.base != 0;
+    const int extra = ei.kind == 2 ? 1 : 2 * ((mul ? 1 : 0) + (add ? 1 : 0)) + (ei.kind == 3 ? 1 : 0);
     if (n + extra + (sh.n_ops - nl) > kMaxOps) continue;
-    if (ei.kind == 2) {
+    if (ei.kind == 3) {      // in place on the load's slot, like the affine decode: decimal::decode op by op
+      if (add && temp >= (uint32_t)kSlots) continue;
+      if (add) { x.imm[n] = (uint64_t)ei.base; s.ops[n++] = Op{OP_CONST, (uint8_t)temp, 0, 0, 0, {0, 0, 0}}; s.ops[n++] = Op{OP_ADD_I, slot, slot, (uint8_t)temp, 0, {0, 0, 0}}; }
+      s.ops[n++] = Op{OP_DEC10, slot, slot, slot, (uint8_t)ei.stride, {0, 0, 0}};
+    } else if (ei.kind == 2) {
       if (dicts >= kMaxDicts || ei.width != 1) continue;
       x.dict[dicts] = ei.dict;
       s.ops[n++] = Op{OP_DICT, slot, slot, slot, (uint8_t)dicts, {0, 0, 0}};
@@ -77,7 +83,7 @@ inline bool encode_program(const fused::Shape& sh, const fused::Args& a, const I
       if (mul) { x.imm[n] = ei.stride; s.ops[n++] = Op{OP_CONST, (uint8_t)temp, 0, 0, 0, {0, 0, 0}}; s.ops[n++] = Op{OP_MUL_I, slot, slot, (uint8_t)temp, 0, {0, 0, 0}}; }
       if (add) { x.imm[n] = (uint64_t)ei.base; s.ops[n++] = Op{OP_CONST, (uint8_t)temp, 0, 0, 0, {0, 0, 0}}; s.ops[n++] = Op{OP_ADD_I, slot, slot, (uint8_t)temp, 0, {0, 0, 0}}; }
     }
-    s.in_dtype[i] = ei.width == 1 ? PLX_U8 : PLX_U16;
+    s.in_dtype[i] = ei.width == 1 ? PLX_U8 : ei.width == 2 ? PLX_U16 : PLX_U32;
     x.in[i].values = ei.codes;
     did |= 1u << i;
   }
@@ -100,6 +106,11 @@ bool affine_encode(int dtype, const void* values, const uint64_t* validity, int6
 bool dict_collect(const uint64_t* values, const uint64_t* validity, int64_t n, int64_t step, std::vector<uint64_t>* patterns);
 // codes[i] = index of v[i] in the sorted dictionary `dict` (device, kDictSlots words, n_dict in use); self-checking like affine_encode.  Synchronises.
 bool dict_encode(const uint64_t* values, const uint64_t* validity, int64_t n, const unsigned long long* dict, int n_dict, uint8_t* codes);
+// decimal::Stats of the valid rows `0, step, 2 * step, ..` of an f64 column at the exponents e_lo .. e_hi.  Synchronises.
+decimal::Stats decimal_stats(const double* values, const uint64_t* validity, int64_t n, int64_t step, int e_lo, int e_hi);
+// codes[i] = decimal::encode_row(v[i]) as u32 (null rows: 0), eight rows per lane and one 32-byte store; false when any valid row has no code that decodes to its bits
+// (the codes are then garbage).  `codes` holds n rounded up to a multiple of 8 codes.  Synchronises.
+bool decimal_encode(const double* values, const uint64_t* validity, int64_t n, int64_t base, int e, uint32_t* codes);
 
 }  // namespace enc
 }  // namespace plx

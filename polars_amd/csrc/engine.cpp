@@ -3,6 +3,7 @@
 #include "engine.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <functional>
 #include <memory>
@@ -1134,9 +1135,32 @@ static int64_t sample_keys_cached(const ColumnPtr& key_col, const Shape& sh, con
 // ---- encoded inputs: narrow shadows of low-cardinality columns (encoded_inputs.hpp, DESIGN.md "Encoded shadows") ----
 // The whole policy lives here.  A column QUALIFIES in a scan when the program reads it whole through a plain OP_LOAD, the scan ends in the register or the LDS
 // aggregate sink (the only callers), the library owns its buffer (a borrowed one can be rewritten by its owner behind our back), and its codes would take at most a
-// quarter of its bytes: 8-byte integers and f64, 4-byte integers when one byte a row is enough.  The SECOND qualifying scan since the statistics were last dropped
+// quarter of its bytes: 8-byte integers and f64, 4-byte integers when one byte a row is enough -- or half of them, for an f64 column of decimals of at least
+// kDecimalMinRows rows (build_decimal_shadow).  The SECOND qualifying scan since the statistics were last dropped
 // tries to build the shadow before it launches; one that fails -- too many values, no memory, a row that does not decode to itself -- is never tried again.
 static bool encoded_inputs_enabled() { static const bool v = [] { const char* e = getenv("PLX_ENCODED_INPUTS"); return !(e && e[0] == '0'); }(); return v; }
+// Decimal shadows take HALF the column's bytes, so they are built for columns of at least this many rows only (the figure at which the run-time compiler starts, jit.cpp):
+// below it the scans are launch-bound, and 4 bytes a row saved is not worth 4 bytes a row held.  PLX_ENCODED_DECIMAL_MIN_ROWS / plx_encoded_set_decimal_min_rows.
+constexpr int64_t kDecimalMinRows = (int64_t)1 << 22;
+static std::atomic<int64_t> g_decimal_min_rows{[] { const char* e = getenv("PLX_ENCODED_DECIMAL_MIN_ROWS"); return e && e[0] ? (int64_t)atoll(e) : kDecimalMinRows; }()};
+void encoded_set_decimal_min_rows(int64_t min_rows) { g_decimal_min_rows.store(min_rows < 0 ? 0 : min_rows, std::memory_order_relaxed); }
+int64_t encoded_decimal_min_rows() { return g_decimal_min_rows.load(std::memory_order_relaxed); }
+// f64 column whose dictionary gave up -> u32 codes of its decimals (decimal.hpp), or null.  `step`: the stride of the sample (at most 2^20 rows): a column of arbitrary
+// doubles is rejected by it in microseconds.  The sample chooses the exponent and whether base 0 will do; a base other than 0 is the EXACT minimum, from one full pass
+// at the chosen exponent.  The encode pass checks every valid row: one that is no decimal at the exponent, or lies outside the codes' range, discards the shadow.
+static std::shared_ptr<EncodedShadow> build_decimal_shadow(const ColumnPtr& col, int64_t step) {
+  const int64_t n = col->len;
+  if (n < g_decimal_min_rows.load(std::memory_order_relaxed)) return nullptr;
+  const double* v = col->values->as<double>();
+  decimal::Choice ch = decimal::choose(enc::decimal_stats(v, col->valid_words(), n, step < 1 ? 1 : step, 0, decimal::kMaxExp));
+  if (ch.ok && step > 1 && ch.base != 0) ch = decimal::choose(enc::decimal_stats(v, col->valid_words(), n, 1, ch.e, ch.e), ch.e, ch.e);
+  if (!ch.ok) return nullptr;
+  auto s = std::make_shared<EncodedShadow>();
+  s->kind = EncodedShadow::kDecimal; s->width = 4; s->base = ch.base; s->stride = (uint64_t)ch.e;
+  s->codes = dev_alloc((size_t)((n + 7) / 8) * 8 * sizeof(uint32_t));      // the encoder stores eight codes at a time
+  if (!enc::decimal_encode(v, col->valid_words(), n, ch.base, ch.e, s->codes->as<uint32_t>())) return nullptr;
+  return s;
+}
 static std::shared_ptr<EncodedShadow> build_shadow(const ColumnPtr& col) {
   auto s = std::make_shared<EncodedShadow>();
   const int64_t n = col->len;
@@ -1144,8 +1168,10 @@ static std::shared_ptr<EncodedShadow> build_shadow(const ColumnPtr& col) {
   if (col->dtype == PLX_F64) {
     std::vector<uint64_t> pats;
     const int64_t step = (n + ((int64_t)1 << 20) - 1) >> 20;      // a strided sample of at most 2^20 rows first: a high-cardinality column costs microseconds, not a pass
-    if (step > 1 && !enc::dict_collect(col->values->as<uint64_t>(), col->valid_words(), n, step, &pats)) return nullptr;
-    if (!enc::dict_collect(col->values->as<uint64_t>(), col->valid_words(), n, 1, &pats) || pats.empty()) return nullptr;
+    const bool dict_ok = (step <= 1 || enc::dict_collect(col->values->as<uint64_t>(), col->valid_words(), n, step, &pats)) &&
+                         enc::dict_collect(col->values->as<uint64_t>(), col->valid_words(), n, 1, &pats);
+    if (!dict_ok) return build_decimal_shadow(col, step);      // too many patterns for a dictionary: a column of decimals still has four-byte codes
+    if (pats.empty()) return nullptr;
     s->kind = EncodedShadow::kDict; s->width = 1; s->n_dict = (int)pats.size();
     pats.resize(kDictSlots, 0);
     s->dict = dev_alloc(sizeof(uint64_t) * kDictSlots);
@@ -1217,7 +1243,7 @@ static ScanProgram scan_program_with_encodings(const Compiler& c, bool may_build
       if (!((taken >> i) & 1u)) continue;
       std::string name = "?";
       for (size_t j = 0; j < c.df->cols.size(); j++) if (c.df->cols[j] == c.cols[c.input_cols[i]]) name = c.df->names[j];
-      sp.note += std::string(first ? "" : ",") + name + ":" + (e[i].kind == EncodedShadow::kDict ? "dict" : "affine") + std::to_string(8 * e[i].width);
+      sp.note += std::string(first ? "" : ",") + name + ":" + (e[i].kind == EncodedShadow::kDict ? "dict" : e[i].kind == EncodedShadow::kDecimal ? "decimal" : "affine") + std::to_string(8 * e[i].width);
       first = false;
     }
     sp.note += "}";

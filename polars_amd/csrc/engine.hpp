@@ -76,6 +76,9 @@ bool dump_program_json(Plan& plan, int root, std::string* json, std::string* why
 bool describe_join_fusion(Plan& plan, int root, std::vector<fused::Shape>* shapes, std::string* why_not);
 // root = a Filter node: the predicate program of the one-pass filter -> frame kernel (k::fused_filter); false + why_not when it does not compile
 bool describe_filter_fusion(Plan& plan, int root, fused::Shape* shape, std::string* why_not);
+// f64 columns of at least min_rows rows may get a decimal shadow (encoded_inputs.hpp; default 2^22, PLX_ENCODED_DECIMAL_MIN_ROWS); negative counts as 0
+void encoded_set_decimal_min_rows(int64_t min_rows);
+int64_t encoded_decimal_min_rows();
 
 }  // namespace engine
 }  // namespace plx

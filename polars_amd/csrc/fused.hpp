@@ -66,7 +66,10 @@ enum OpCode : uint8_t {
   OP_DICT,
   // dst <- a part (year, month, ..., temporal.hpp) of the Date / Datetime value a, with the validity of a.  c = temporal::pack(part, unit): both are part of the Shape,
   // so the compiled kernels carry one part's arithmetic with constant divisors.  One source slot (a == b), no immediate
-  OP_DATEPART
+  OP_DATEPART,
+  // dst <- (double)(int64)a / 10^c, with the validity of a: the value of a decimal-encoded input (Column::shadow, decimal.hpp div10: a conversion, a multiplication
+  // and two FMAs in place of the IEEE division).  c = the exponent 0..9, part of the Shape.  One source slot (a == b), no immediate
+  OP_DEC10
 };
 
 struct Op {

@@ -3,6 +3,7 @@
 // (AOT-foldable), aggregate combine / identity / per-row value rules and the atomic cell updates.
 // See kernels_fused.hip for the kernel structure and the reference mapping.
 #pragma once
+#include "decimal.hpp"
 #include "dev.hpp"
 #include "fused.hpp"
 #include "fused_shapes.hpp"
@@ -379,6 +380,11 @@ __device__ __forceinline__ void exec_op(const Op op, const Shape& sh, const Args
                           // interpreter its branches are wave-uniform (and it holds every division once: see there)
 #pragma unroll
         for (int r = 0; r < kRows; r++) d[r] = (uint64_t)temporal::part((int64_t)a[r], temporal::unit_of(op.c), temporal::part_of(op.c));
+        vd = va;
+        break;
+      case OP_DEC10:      // (the exponent is a constant of a compiled program: d and r fold; in the interpreter the switch is wave-uniform)
+#pragma unroll
+        for (int r = 0; r < kRows; r++) d[r] = as_u(decimal::div10((double)(long long)a[r], op.c));
         vd = va;
         break;
       default:  // OP_MOV / OP_NOP

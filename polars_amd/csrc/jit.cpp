@@ -198,7 +198,7 @@ std::string cache_dir() {
 std::string headers_fingerprint() {   // the device headers the generated source includes: a stale cache entry must never survive an upgrade
   static const std::string fp = [] {
     uint64_t h = 0xcbf29ce484222325ull;
-    for (const char* f : {"fused.hpp", "fused_device.hpp", "fused_sinks.hpp", "fused_shapes.hpp", "partition_device.hpp", "partition2_device.hpp", "partition3_device.hpp", "dev.hpp", "kconfig.hpp", "temporal.hpp"}) {
+    for (const char* f : {"fused.hpp", "fused_device.hpp", "fused_sinks.hpp", "fused_shapes.hpp", "partition_device.hpp", "partition2_device.hpp", "partition3_device.hpp", "dev.hpp", "kconfig.hpp", "temporal.hpp", "decimal.hpp"}) {
       if (FILE* fp2 = fopen((include_dir() + "/" + f).c_str(), "rb")) {
         char buf[65536]; size_t n;
         while ((n = fread(buf, 1, sizeof buf, fp2)) > 0) h = fnv1a(std::string(buf, n), h);

@@ -294,5 +294,95 @@ bool dict_encode(const uint64_t* values, const uint64_t* validity, int64_t n, co
   return bad == 0;
 }
 
+// ---- decimal: statistics -------------------------------------------------------------------------------------------------------------------------------------------
+// decimal::Stats of the items `0, step, ..`: every lane keeps its own, a wave shuffle tree and the workgroup's LDS merge them, one partial per workgroup goes to HBM and
+// the host merges those.  A lane whose exponents have all failed does no more arithmetic (stats_row skips them): a column of arbitrary doubles costs one load a row.
+__device__ __forceinline__ decimal::Stats stats_shfl_xor(const decimal::Stats& s, int m) {
+  decimal::Stats o;
+  o.fail = (uint32_t)__shfl_xor((int)s.fail, m, 64); o.any = (uint32_t)__shfl_xor((int)s.any, m, 64);
+#pragma unroll
+  for (int e = 0; e < decimal::kNumExp; e++) { o.mn[e] = (int64_t)shfl_xor_u64((uint64_t)s.mn[e], m); o.mx[e] = (int64_t)shfl_xor_u64((uint64_t)s.mx[e], m); }
+  return o;
+}
+__global__ __launch_bounds__(kBlock) void decimal_stats_kernel(const double* __restrict__ v, const unsigned long long* __restrict__ validity, int64_t n_items, int64_t step,
+                                                               int e_lo, int e_hi, decimal::Stats* __restrict__ partials) {
+  __shared__ decimal::Stats red[kBlock / 64];
+  decimal::Stats st;
+  decimal::stats_init(st);
+  for (int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; item < n_items; item += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = item * step;
+    if (validity && !((validity[row >> 6] >> (row & 63)) & 1ull)) continue;
+    decimal::stats_row(st, v[row], e_lo, e_hi);
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) decimal::stats_merge(st, stats_shfl_xor(st, m));
+  if (lane_id() == 0) red[threadIdx.x >> 6] = st;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kBlock / 64; w++) decimal::stats_merge(st, red[w]);
+    partials[blockIdx.x] = st;
+  }
+}
+
+decimal::Stats decimal_stats(const double* values, const uint64_t* validity, int64_t n, int64_t step, int e_lo, int e_hi) {
+  decimal::Stats st;
+  decimal::stats_init(st);
+  if (n <= 0) return st;
+  PLX_REQUIRE(step >= 1 && e_lo >= 0 && e_hi <= decimal::kMaxExp, PLX_ERR_INVALID, "decimal_stats: step >= 1, exponents 0..9");
+  const int64_t n_items = (n + step - 1) / step;      // rows 0, step, .. (n_items - 1) * step < n
+  const int grid = k::grid_for(n_items, kBlock * 16);
+  Buf partials = dev_alloc(sizeof(decimal::Stats) * (size_t)grid);
+  {
+    ProfileScope ps(step == 1 ? "encode_decimal_stats" : "encode_decimal_sample", (uint64_t)n_items * 8, (uint64_t)n_items);
+    hipLaunchKernelGGL(decimal_stats_kernel, dim3(grid), dim3(kBlock), 0, stream(), values, (const unsigned long long*)validity, n_items, step, e_lo, e_hi, partials->as<decimal::Stats>());
+    PLX_HIP(hipGetLastError());
+  }
+  std::vector<decimal::Stats> host((size_t)grid);
+  d2h_sync(host.data(), partials->ptr, sizeof(decimal::Stats) * (size_t)grid);
+  for (const decimal::Stats& p : host) decimal::stats_merge(st, p);
+  return st;
+}
+
+// ---- decimal: encode -----------------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void decimal_encode_kernel(const unsigned long long* __restrict__ v, const unsigned long long* __restrict__ validity, int64_t n, long long base,
+                                                                int e, uint32_t* __restrict__ codes, unsigned int* __restrict__ flag) {
+  const int64_t groups = (n + kRowsPerLane - 1) / kRowsPerLane;
+  bool bad = false;
+  for (int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; gi < groups; gi += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row0 = gi * kRowsPerLane;
+    unsigned long long x[kRowsPerLane];
+    unsigned vb;
+    load_rows8<unsigned long long>(v, validity, row0, n, x, vb);
+    Pack<uint32_t, kRowsPerLane> out;
+#pragma unroll
+    for (int r = 0; r < kRowsPerLane; r++) {
+      const bool valid = (vb >> r) & 1u;
+      uint32_t code = 0;
+      const bool ok = decimal::encode_row(__longlong_as_double((long long)x[r]), base, e, &code);      // (compares the decoded bits with the row's)
+      if (valid && !ok) bad = true;
+      out.v[r] = valid && ok ? code : 0u;
+    }
+    store_pack<uint32_t, kRowsPerLane>(codes + row0, out);      // (the buffer holds whole groups)
+  }
+  if (bad) flag[0] = 1u;
+}
+
+bool decimal_encode(const double* values, const uint64_t* validity, int64_t n, int64_t base, int e, uint32_t* codes) {
+  if (n <= 0) return true;
+  PLX_REQUIRE(e >= 0 && e <= decimal::kMaxExp, PLX_ERR_INVALID, "decimal_encode: exponent 0..9");
+  Buf flag = dev_alloc_zero(8);
+  const int64_t groups = (n + kRowsPerLane - 1) / kRowsPerLane;
+  const int grid = k::grid_for(groups, kBlock * 4);
+  unsigned int* f = flag->as<unsigned int>();
+  {
+    ProfileScope ps("encode_decimal", (uint64_t)n * 12, (uint64_t)n);
+    hipLaunchKernelGGL(decimal_encode_kernel, dim3(grid), dim3(kBlock), 0, stream(), (const unsigned long long*)values, (const unsigned long long*)validity, n, (long long)base, e, codes, f);
+    PLX_HIP(hipGetLastError());
+  }
+  unsigned int bad = 0;
+  d2h_sync(&bad, f, 4);
+  return bad == 0;
+}
+
 }  // namespace enc
 }  // namespace plx

@@ -123,6 +123,8 @@ static int scan_grid(int64_t n_rows, int blocks_per_cu, const char* knob = nullp
 static_assert(!trust_nullable<StatProg<SHAPE_Q1>, LdsAggSink>() && !trust_nullable<StatProg<SHAPE_CFG2>, RegAggSink>() && !trust_nullable<StatProg<SHAPE_CFG2_NULLX>, RegAggSink>(),
               "rows wider than 16 bytes keep their loads as they were");
 static_assert(trust_nullable<StatProg<SHAPE_Q1_ENCODED>, LdsAggSink>() && dict_count(static_shape(SHAPE_Q1_ENCODED)) == 2, "encoded Q1: 15-byte rows, two dictionaries in LDS");
+static_assert(trust_nullable<StatProg<SHAPE_Q1_ENCODED_PRICE>, LdsAggSink>() && shape_row_bytes(static_shape(SHAPE_Q1_ENCODED_PRICE)) == 11 && dict_count(static_shape(SHAPE_Q1_ENCODED_PRICE)) == 2,
+              "encoded Q1 with the decimal price: 11-byte rows, two dictionaries in LDS");
 int64_t scan_waves(int64_t n_rows) { return (int64_t)scan_grid(n_rows, 8) * (kBlock / 64); }
 static uint64_t algo_bytes(const Shape& sh, const Args& args) {
   uint64_t algo = 0;
@@ -220,6 +222,7 @@ void fused_lds_agg(const Shape& sh, const Args& args, int n_groups, int static_i
     switch (static_id) {
       case SHAPE_Q1: PLX_LAUNCH_SCAN(StatProg<SHAPE_Q1>, LdsAggSink, grid, lds, sh, args, sp); break;
       case SHAPE_Q1_ENCODED: PLX_LAUNCH_SCAN(StatProg<SHAPE_Q1_ENCODED>, LdsAggSink, grid, lds, sh, args, sp); break;
+      case SHAPE_Q1_ENCODED_PRICE: PLX_LAUNCH_SCAN(StatProg<SHAPE_Q1_ENCODED_PRICE>, LdsAggSink, grid, lds, sh, args, sp); break;
       default: if (!jit::launch(sh, args, jit::LDSAGG, &sp, grid, lds)) { const DynLaunch d = dyn_launch(sh, args, lds); PLX_LAUNCH_SCAN(DynProg, LdsAggSink, grid, d.lds, sh, d.args, sp); } break;
     }
     PLX_HIP(hipGetLastError());

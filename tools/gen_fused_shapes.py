@@ -31,17 +31,19 @@ def encoded(s, kind, width, base=0, stride=1):
     return s
 
 
-AFFINE, DICT = 1, 2
+AFFINE, DICT, DECIMAL = 1, 2, 3
 DAY_US = 86_400_000_000
 
 
-def lineitem_encoded():
+def lineitem_encoded(price=False):
     """The Q1 columns as the shadows of the generator's data (csrc/datagen_device.hpp) come out: l_shipdate = day 8036 + k days, k < 2647 (two-byte codes, stride and
-    base); l_quantity 1..50 (one-byte codes, base only); l_discount / l_tax 11 and 9 distinct f64 values (one-byte dictionary codes); the rest stay as they are."""
+    base); l_quantity 1..50 (one-byte codes, base only); l_discount / l_tax 11 and 9 distinct f64 values (one-byte dictionary codes); the rest stay as they are -- or, with `price`, l_extendedprice
+    as well: cents in [0, 2^32) (four-byte decimal codes, base 0, exponent 2: the stride argument carries the exponent)."""
     flag = pl.Categorical(["A", "N", "R"], pl.UInt8)
     status = pl.Categorical(["F", "O"], pl.UInt8)
     return pl.DataFrame([encoded(ph("l_shipdate", pl.Datetime), AFFINE, 2, 8036 * DAY_US, DAY_US), ph("l_returnflag", flag, rng=(0, 2)), ph("l_linestatus", status, rng=(0, 1)),
-                         encoded(ph("l_quantity", pl.Int64), AFFINE, 1, 1, 1), ph("l_extendedprice", pl.Float64), encoded(ph("l_discount", pl.Float64), DICT, 1),
+                         encoded(ph("l_quantity", pl.Int64), AFFINE, 1, 1, 1),
+                         encoded(ph("l_extendedprice", pl.Float64), DECIMAL, 4, 0, 2) if price else ph("l_extendedprice", pl.Float64), encoded(ph("l_discount", pl.Float64), DICT, 1),
                          encoded(ph("l_tax", pl.Float64), DICT, 1)])
 
 
@@ -82,6 +84,8 @@ def shapes():
                        pl.DataFrame([ph("ps_partkey", pl.Int64), ph("ps_suppkey", pl.Int64), ph("ps_group", pl.Int64)]).lazy()), 1),
         ("SHAPE_Q1_ENCODED", "TPC-H Q1 over the encoded shadows of l_shipdate (u16, stride, base), l_quantity (u8, base), l_discount and l_tax (u8 dictionary codes)",
          Q.q1(lineitem_encoded().lazy()), 0),
+        ("SHAPE_Q1_ENCODED_PRICE", "TPC-H Q1 over the same shadows and l_extendedprice as four-byte decimal codes (base 0, exponent 2): 11 bytes a row",
+         Q.q1(lineitem_encoded(price=True).lazy()), 0),
     ]
 
 
