@@ -186,6 +186,12 @@ static bool contains_column_outside_agg(const Plan& plan, int e) {
   if (x.kind == PLX_AE_COLUMN) return true;
   return contains_column_outside_agg(plan, x.lhs) || contains_column_outside_agg(plan, x.rhs) || contains_column_outside_agg(plan, x.cond);
 }
+static bool contains_column(const Plan& plan, int e) {
+  if (e < 0) return false;
+  const AE& x = plan.ae[e];
+  if (x.kind == PLX_AE_COLUMN) return true;
+  return contains_column(plan, x.lhs) || contains_column(plan, x.rhs) || contains_column(plan, x.cond);
+}
 static void collect_aggs(const Plan& plan, int e, std::vector<int>& out) {
   if (e < 0) return;
   const AE& x = plan.ae[e];
@@ -1626,6 +1632,17 @@ static int and_predicates(Compiler& c, const std::vector<int>& preds) {
 static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& preds, const FramePtr& src, FramePtr& out, Shape* shape_out, int* sid_out,
                          std::string* why, bool compile_only) {
   for (int e : node.exprs) if (!contains_agg(plan, e) || contains_column_outside_agg(plan, e)) { if (why) *why = "select mixes row expressions and aggregations"; return false; }
+  // select(lit(2.5).sum()) aggregates a one-row literal (sum 2.5, count 1, whatever the filter keeps), as the per-node evaluator does: a fused program would
+  // repeat the constant on every row it scans
+  {
+    std::vector<int> lit_check;
+    for (int e : node.exprs) collect_aggs(plan, e, lit_check);
+    for (int a : lit_check)
+      if (plan.ae[a].kind == PLX_AE_AGG && !contains_column(plan, plan.ae[a].lhs)) {
+        if (why) *why = "aggregate of a literal is a scalar, not a value per row; done by the per-node kernels";
+        return false;
+      }
+  }
   Compiler c(plan, *src);
   std::vector<int> agg_nodes;
   std::vector<FinalSpec> specs;
