@@ -504,6 +504,15 @@ const char* plx_last_plan_description(void);
  * "encoded{l_shipdate:affine16,l_discount:dict8}; " per scan; "" when every scan read its columns as stored.  Kept beside the plan description, not in
  * it: the description names the route, and the route of a query is the same whether its inputs are read plain or encoded. */
 const char* plx_last_plan_encodings(void);
+/* Rows per wave tile of the process's last fused aggregate scan (whole-frame aggregates or the LDS group table): 512 when it ran over wide tiles, 128 when it did
+ * not, 0 before the first.  For tests; the plan description does not say. */
+int32_t plx_last_scan_tile_rows(void);
+/* The launchers' choice between the two tile sizes, as a pure function (no GPU needed): 1 = 512-row wide tiles.  They are chosen exactly when the program is compiled
+ * (ahead of time or at run time), a row is at most 16 bytes of integer or f64 columns (no Boolean, no f32), one of them narrower than eight bytes, no input is nullable or carries a bitmap, n_rows holds one whole tile,
+ * every values pointer is aligned to eight rows of its column, and the knob (PLX_WIDE_TILES, default on) is on.  dtypes / nullable / values / validity: n_inputs
+ * entries each, pointers as integers.  -1: bad arguments. */
+int32_t plx_wide_tiles_choice(int32_t compiled, int32_t knob_on, int64_t n_rows, int32_t n_inputs, const int32_t* dtypes, const int32_t* nullable, const uint64_t* values,
+                              const uint64_t* validity);
 
 /* ---- synthetic benchmark data (no reference counterpart: dbgen lives outside the reference tree) -------
  * Fills n_rows of the TPC-H Q1 lineitem columns directly in HBM with a counter-based generator (row i is a pure

@@ -228,6 +228,8 @@ SIGNATURES = {
     "plx_jit_set_min_rows": (C.c_int, [C.c_int64]),
     "plx_last_plan_description": (C.c_char_p, []),
     "plx_last_plan_encodings": (C.c_char_p, []),
+    "plx_last_scan_tile_rows": (C.c_int32, []),
+    "plx_wide_tiles_choice": (C.c_int32, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "plx_profile_enable": (C.c_int, [C.c_int]),
     "plx_profile_fetch": (C.c_int, [C.POINTER(ProfileRecord), C.c_int32, _i32p]),
     "plx_profile_clear": (C.c_int, []),
@@ -295,6 +297,18 @@ def last_plan() -> str:
 def last_plan_encodings() -> str:
     """The inputs the last collect()'s fused aggregate scans read through their encoded shadows ("encoded{l_shipdate:affine16,l_discount:dict8,l_extendedprice:decimal32}; "), or ""."""
     return lib().plx_last_plan_encodings().decode()
+
+
+def last_scan_tile_rows() -> int:
+    """Rows per wave tile of the last fused aggregate scan: 512 (wide tiles), 128, or 0 before the first."""
+    return int(lib().plx_last_scan_tile_rows())
+
+
+def wide_tiles_choice(compiled, knob_on, n_rows, dtypes, nullable, values, validity) -> int:
+    """The launchers' choice of 512-row wide tiles for a scan over these inputs (plx_wide_tiles_choice): pointers as integers, no GPU needed."""
+    n = len(dtypes)
+    return int(lib().plx_wide_tiles_choice(int(bool(compiled)), int(bool(knob_on)), int(n_rows), n, (C.c_int32 * n)(*[int(d) for d in dtypes]),
+                                           (C.c_int32 * n)(*[int(bool(x)) for x in nullable]), (C.c_uint64 * n)(*[int(v) for v in values]), (C.c_uint64 * n)(*[int(v) for v in validity])))
 
 
 def jit_set_min_rows(min_rows: int) -> None:

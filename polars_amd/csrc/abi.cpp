@@ -15,6 +15,7 @@
 #include "jit.hpp"
 #include "join.hpp"
 #include "kernels.hpp"
+#include "kernels_fused.hpp"
 #include "ops.hpp"
 #include "scan.hpp"
 #include "sort.hpp"
@@ -936,6 +937,19 @@ int plx_execute_plan(const plx_ir* ir, int32_t n_ir, const plx_aexpr* exprs, int
 }
 const char* plx_last_plan_description(void) { return t_plan_desc.c_str(); }
 const char* plx_last_plan_encodings(void) { return t_plan_encoded.c_str(); }
+int32_t plx_last_scan_tile_rows(void) { return k::last_scan_tile_rows(); }
+int32_t plx_wide_tiles_choice(int32_t compiled, int32_t knob_on, int64_t n_rows, int32_t n_inputs, const int32_t* dtypes, const int32_t* nullable, const uint64_t* values,
+                              const uint64_t* validity) {
+  if (n_inputs < 0 || n_inputs > fused::kMaxInputs || (n_inputs && (!dtypes || !nullable || !values || !validity))) return -1;
+  fused::Shape sh{}; fused::Args args{};
+  sh.n_inputs = (uint8_t)n_inputs; sh.pred = fused::kNone; sh.key = fused::kNone;
+  args.n_rows = n_rows;
+  for (int i = 0; i < n_inputs; i++) {
+    sh.in_dtype[i] = (uint8_t)dtypes[i]; sh.in_nullable[i] = (uint8_t)(nullable[i] != 0);
+    args.in[i].values = (const void*)(uintptr_t)values[i]; args.in[i].validity = (const uint64_t*)(uintptr_t)validity[i];
+  }
+  return k::wide_tiles_choice(sh, args, compiled != 0, knob_on != 0) ? 1 : 0;
+}
 
 int plx_debug_program_json(const plx_ir* ir, int32_t n_ir, const plx_aexpr* exprs, int32_t n_exprs, int32_t root, char* buf, size_t cap) {
   PLX_TRY
@@ -1041,6 +1055,17 @@ int plx_jit_selftest(const plx_ir* ir, int32_t n_ir, const plx_aexpr* exprs, int
         jobs.push_back({sh, jit::part3_agg_sink(fused::kP2Hash, pack)});
       }
     }
+  }
+  // the wide-tile form of the two aggregate scans, where the shape has one
+  {
+    std::vector<std::pair<fused::Shape, jit::Sink>> forms;
+    fused::Args aligned{}; aligned.n_rows = fused::kWideTileRows;      // null pointers are aligned: what is left is the shape's own part of the decision
+    for (auto& j : jobs) {
+      const bool wide = k::wide_tiles_choice(j.first, aligned, true, true);
+      if (j.second == jit::REGAGG && wide) forms.push_back({j.first, jit::REGAGG_WIDE});
+      if (j.second == jit::LDSAGG && wide) forms.push_back({j.first, jit::LDSAGG_WIDE});
+    }
+    jobs.insert(jobs.end(), forms.begin(), forms.end());
   }
   for (auto& j : jobs) {
     const std::string log = jit::selftest(j.first, j.second);

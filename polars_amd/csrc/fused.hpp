@@ -35,6 +35,8 @@ constexpr int kMaxAggs = 16;
 constexpr int kMaxKeys = 4;          // columns of a wide (unpackable) group key
 constexpr int kRows = 2;            // rows per lane per tile (one 16-B load of an 8-B column)
 constexpr int kTileRows = 64 * kRows;
+constexpr int kWideRows = 8;        // rows per lane of a wide tile (fused_device.hpp wide_load): four passes of the two-row program
+constexpr int kWideTileRows = 64 * kWideRows;
 constexpr uint8_t kNone = 255;
 
 enum OpCode : uint8_t {

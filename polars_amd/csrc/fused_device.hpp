@@ -448,6 +448,80 @@ __host__ __device__ constexpr int shape_row_bytes(const Shape& s) {
   return b;
 }
 __host__ __device__ constexpr bool narrow_rows(const Shape& s) { return s.n_inputs > 0 && shape_row_bytes(s) <= 16; }
+// ---- wide tiles (compiled aggregate scans over narrow rows whose inputs are all non-nullable) ----------------------------------------------------------
+// A wave takes kWideTileRows = 512 consecutive rows per iteration and lane l owns rows base + 8l .. base + 8l + 7: every input column is ONE 8- or 16-byte load per
+// lane (two for a four-byte column, four for an eight-byte one), kept as raw bits.  The two-row program then runs four times, its OP_LOADs replaced by an unpack of
+// rows (2j, 2j + 1) from those registers (run_program_wide).  Only whole tiles come here: no row-count compare, no clamp, no bitmap.
+__host__ __device__ constexpr int wide_dtype_bytes(int dt) {
+  switch (dt) {
+    case PLX_I8: case PLX_U8: return 1;
+    case PLX_I16: case PLX_U16: return 2;
+    case PLX_I32: case PLX_U32: return 4;
+    case PLX_I64: case PLX_U64: case PLX_F64: return 8;
+    default: return 0;      // no wide tiles: BOOL is bit-packed, and load_input (the 128-row path that finishes the same kernel) has no F32 case
+  }
+}
+__host__ __device__ constexpr bool wide_tiles_shape(const Shape& s) {
+  if (!narrow_rows(s)) return false;
+  bool any_narrow = false;      // a row of eight-byte columns alone is one 16-byte load per column and two rows already: nothing to gain
+  for (int i = 0; i < s.n_inputs; i++) {
+    if (s.in_nullable[i] != 0 || wide_dtype_bytes(s.in_dtype[i]) == 0) return false;
+    any_narrow = any_narrow || wide_dtype_bytes(s.in_dtype[i]) < 8;
+  }
+  if (!any_narrow) return false;
+  for (int pc = 0; pc < s.n_ops; pc++) if (s.ops[pc].code == OP_LOAD && s.ops[pc].a >= s.n_inputs) return false;
+  return true;
+}
+struct WideRaw { uint32_t w[kMaxInputs][2 * kWideRows]; };      // input i uses its first 2 * width dwords; every index is a compile-time constant
+template <class P>
+__device__ __forceinline__ void wide_load(const Args& args, int64_t row0, WideRaw& raw) {
+  constexpr Shape sh = P::shape();
+#pragma unroll
+  for (int i = 0; i < kMaxInputs; i++) {
+    if (i < sh.n_inputs) {
+      const int wb = wide_dtype_bytes(sh.in_dtype[i]);
+      const unsigned char* p = reinterpret_cast<const unsigned char*>(args.in[i].values) + row0 * wb;
+      if (wb == 1) {
+        const uint2 x = *reinterpret_cast<const uint2*>(p);
+        raw.w[i][0] = x.x; raw.w[i][1] = x.y;
+      } else {
+#pragma unroll
+        for (int q = 0; q < wb / 2; q++) {      // 16 bytes a load: one for a two-byte column, two for four bytes, four for eight
+          const uint4 x = reinterpret_cast<const uint4*>(p)[q];
+          raw.w[i][4 * q] = x.x; raw.w[i][4 * q + 1] = x.y; raw.w[i][4 * q + 2] = x.z; raw.w[i][4 * q + 3] = x.w;
+        }
+      }
+    }
+  }
+}
+// row e (0 .. 7) of an input from its raw dwords, widened to 64 bits as load2 widens it
+__device__ __forceinline__ uint64_t wide_unpack(const uint32_t* w, int dt, int e) {
+  switch (dt) {
+    case PLX_I8: return (uint64_t)(long long)(int8_t)(w[e >> 2] >> ((e & 3) * 8));
+    case PLX_U8: return (uint64_t)(uint8_t)(w[e >> 2] >> ((e & 3) * 8));
+    case PLX_I16: return (uint64_t)(long long)(int16_t)(w[e >> 1] >> ((e & 1) * 16));
+    case PLX_U16: return (uint64_t)(uint16_t)(w[e >> 1] >> ((e & 1) * 16));
+    case PLX_I32: return (uint64_t)(long long)(int32_t)w[e];
+    case PLX_U32: return (uint64_t)w[e];
+    default: return (uint64_t)w[2 * e] | ((uint64_t)w[2 * e + 1] << 32);
+  }
+}
+template <class P, int ND, class RF>
+__device__ __forceinline__ void run_program_wide(const Args& args, const WideRaw& raw, int j, RF& rf) {
+  constexpr Shape sh = P::shape();
+#pragma unroll
+  for (int pc = 0; pc < sh.n_ops; pc++) {
+    const Op op = sh.ops[pc];
+    if (op.code == OP_LOAD) {
+#pragma unroll
+      for (int r = 0; r < kRows; r++) rf.set(r, op.dst, wide_unpack(raw.w[op.a], sh.in_dtype[op.a], kRows * j + r));
+      rf.setv(op.dst, (1u << kRows) - 1);
+    } else {
+      exec_op<true, ND, true>(op, sh, args, pc, 0, rf);
+    }
+  }
+}
+
 template <class P, class RF>
 __device__ __forceinline__ void run_loads_full(const Args& args, int64_t row0, RF& rf) {
   constexpr Shape sh = P::shape();

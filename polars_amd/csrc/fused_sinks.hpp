@@ -570,7 +570,13 @@ __host__ __device__ constexpr bool trust_nullable() {
   if constexpr (P::kStatic && (std::is_same<Sink, LdsAggSink>::value || std::is_same<Sink, RegAggSink>::value)) return narrow_rows(P::shape());
   else return false;
 }
+// ... and those whose inputs are ALL non-nullable fixed-width columns have a wide-tile form (fused_device.hpp wide_load); the launcher picks it when the pointers allow
 template <class P, class Sink>
+__host__ __device__ constexpr bool wide_tiles_form() {
+  if constexpr (trust_nullable<P, Sink>()) return wide_tiles_shape(P::shape());
+  else return false;
+}
+template <class P, class Sink, bool WIDE = false>
 __device__ __forceinline__ void fused_scan_body(const Shape dsh, const Args args, const typename Sink::Params sp) {   // by value: kernel arguments passed by
                                                                                                               // reference become addressable stack copies (spills)
   Sink sink;
@@ -591,9 +597,33 @@ __device__ __forceinline__ void fused_scan_body(const Shape dsh, const Args args
     if constexpr (ND > 0) { stage_dicts<ND>(args); __syncthreads(); }
     sink.init(sh, sp);
     // (two tiles of a wave evaluated together, so that the second tile's bitmap lookups fly while the first waits, were measured on TPC-H Q3's orders scan with the
-    // customer filter: no change -- that scan was bound by the LINES its lookups pull from the L2, which OP_MASKV halves.  Two and four tiles per iteration were also
-    // measured on the encoded Q1 scan, profiles/encoded_scan_tiles: no gain beyond the run-to-run spread once the dictionaries are in LDS)
-    for (int64_t t = wave; t < ntiles; t += nwaves) {
+    // customer filter: no change -- that scan was bound by the LINES its lookups pull from the L2, which OP_MASKV halves.)
+    // Several tiles per iteration were tried twice on the encoded Q1 scan.  profiles/encoded_scan_tiles ran the 128-row tile two and four times per iteration: the
+    // same narrow loads (28 per four tiles) and the same per-tile address arithmetic, only issued earlier, on 15-byte rows that already ran at the plain scan's
+    // bandwidth -- no gain, removed.  WIDE is a different geometry, not an unrolling: 512 rows per wave iteration, eight consecutive rows per lane, every column ONE
+    // 8- or 16-byte load per lane (8 loads for the 11-byte Q1 row), one address computation per column and 512 rows, and no row-count compare -- it cuts the
+    // instructions per row (profiles/wide_tiles).  Whole 512-row tiles only; what is left (< 512 rows) goes through the 128-row path below.
+    int64_t first_tile = 0;
+    if constexpr (WIDE) {
+      static_assert(wide_tiles_form<P, Sink>(), "wide tiles: a compiled aggregate scan over narrow rows without nullable inputs");
+      const int64_t nwide = args.n_rows / kWideTileRows;
+      const int lane = lane_id();
+      for (int64_t t = wave; t < nwide; t += nwaves) {
+        const int64_t row0 = t * kWideTileRows + (int64_t)lane * kWideRows;
+        WideRaw raw;
+        wide_load<P>(args, row0, raw);
+#pragma unroll
+        for (int j = 0; j < kWideRows / kRows; j++) {
+          run_program_wide<P, ND>(args, raw, j, rf);
+          bool pass[kRows];
+#pragma unroll
+          for (int r = 0; r < kRows; r++) pass[r] = sh.pred == kNone || ((rf.get(r, sh.pred) & 1) && ((rf.getv(sh.pred) >> r) & 1));
+          sink.consume(sh, rf, pass, row0 + kRows * j, sp);
+        }
+      }
+      first_tile = nwide * (kWideTileRows / kTileRows);
+    }
+    for (int64_t t = first_tile + wave; t < ntiles; t += nwaves) {
       bool pass[kRows]; int64_t row0;
       tile_rows<P, ND, kTrust>(dsh, args, t, rf, pass, row0);
       sink.consume(sh, rf, pass, row0, sp);
@@ -613,6 +643,11 @@ __device__ __forceinline__ void fused_scan_body(const Shape dsh, const Args args
 template <class P, class Sink>
 __global__ __launch_bounds__(kBlock) void fused_scan_kernel(Shape dsh, Args args, typename Sink::Params sp) {
   fused_scan_body<P, Sink>(dsh, args, sp);
+}
+// the wide-tile form of the same scan (wide_tiles_form): a kernel of its own, chosen by the launcher
+template <class P, class Sink>
+__global__ __launch_bounds__(kBlock) void fused_scan_wide_kernel(Shape dsh, Args args, typename Sink::Params sp) {
+  fused_scan_body<P, Sink, true>(dsh, args, sp);
 }
 
 // ---- sink: the selection of a filter -> frame, in ballot form (BallotOut, fused.hpp) ---------------------------------------------------

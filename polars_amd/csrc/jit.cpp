@@ -32,9 +32,12 @@ std::map<std::string, Entry> g_cache;
 int g_compiled = 0;
 double g_ms = 0;
 
+bool wide_tiles(Sink s) { return s == REGAGG_WIDE || s == LDSAGG_WIDE; }
 const char* sink_type(Sink s) {
   static const char* n[] = {"RegAggSink", "LdsAggSink", "DenseAggSink", "HashAggSink", "WideAggSink", "JoinBuildSink", "ProbeAggSink", "DirectBuildSink", "DirectProbeAggSink", "BitmapBuildSink",
                             "part_count", "part_scatter", "part_agg", "part2_scatter_hash", "part2_scatter_direct", "part2_agg_hash", "part2_agg_direct", "part2_scatter_hash_t2", "part2_scatter_direct_t2"};
+  if (s == REGAGG_WIDE) return "RegAggSink";
+  if (s == LDSAGG_WIDE) return "LdsAggSink";
   if (s == PART3_AGG_PAIRV) return "part3_agg";
   if (s >= PART3_SCATTER_PAIRV && s < PART3_AGG_PAIRV) return "part3_scatter";
   if (s == PART3_AGG_PAIR || s == PART3_AGG_PAIR_DIRECT) return "part3_agg";
@@ -93,7 +96,7 @@ std::string source_for(const Shape& sh, Sink sink) {
   std::ostringstream o;
   const std::string sym = kernel_symbol(sh, sink);
   o << "#define plx_jit_kernel " << sym << "\n";
-  o << ((sink == BALLOT || sink == DIRECT_HITS) ? "#include \"fused_sinks.hpp\"\n" : sink >= PART3_SCATTER ? "#include \"partition3_device.hpp\"\n" : sink >= PART2_SCATTER_HASH ? "#include \"partition2_device.hpp\"\n" : sink >= PART_COUNT ? "#include \"partition_device.hpp\"\n" : "#include \"fused_sinks.hpp\"\n") << "namespace plx { namespace k {\n"
+  o << ((sink == BALLOT || sink == DIRECT_HITS || wide_tiles(sink)) ? "#include \"fused_sinks.hpp\"\n" : sink >= PART3_SCATTER ? "#include \"partition3_device.hpp\"\n" : sink >= PART2_SCATTER_HASH ? "#include \"partition2_device.hpp\"\n" : sink >= PART_COUNT ? "#include \"partition_device.hpp\"\n" : "#include \"fused_sinks.hpp\"\n") << "namespace plx { namespace k {\n"
        "struct JitProg {\n  static constexpr bool kStatic = true; static constexpr int kId = -2;\n  static constexpr Shape shape() {\n    Shape s{};\n";
   o << "    s.n_inputs = " << (int)sh.n_inputs << "; s.n_ops = " << (int)sh.n_ops << "; s.n_aggs = " << (int)sh.n_aggs << "; s.pred = " << (int)sh.pred
     << "; s.key = " << (int)sh.key << "; s.n_keys = " << (int)sh.n_keys << ";\n";
@@ -127,6 +130,11 @@ std::string source_for(const Shape& sh, Sink sink) {
            "  part2_agg_body<Shape, " << (sink == PART2_AGG_DIRECT ? 1 : 0) << ", p2_agg_chunks_in_flight(cl.rec_words)>(csh, cl, pp, ap);\n}\n}}\n";
       break;
     default:
+      if (wide_tiles(sink)) {
+        o << "extern \"C\" __global__ __launch_bounds__(kBlock) void plx_jit_kernel(Shape dsh, Args args, " << sink_type(sink)
+          << "::Params sp) {\n  fused_scan_body<JitProg, " << sink_type(sink) << ", true>(dsh, args, sp);\n}\n}}\n";
+        break;
+      }
       if (sink == PART3_AGG_PAIRV) {
         o << "extern \"C\" __global__ __launch_bounds__(kP2AggBlock) void plx_jit_kernel(PartPlan2 pp, AggParams2 ap) {\n"
              "  constexpr Shape csh = JitProg::shape(); constexpr RecLayout2 cl = rec_layout2(JitProg::shape(), 0u, " << fused::kPackPairV << "u);\n"
@@ -301,7 +309,7 @@ std::string selftest(const Shape& sh, Sink sink) {
     size_t cs = 0; hiprtcGetCodeSize(prog, &cs);
     std::vector<char> code(cs);
     hiprtcGetCode(prog, code.data());
-    const std::string base = std::string(dir) + "/" + sink_type(sink) + "_" + std::to_string((int)sink);
+    const std::string base = std::string(dir) + "/" + sink_type(sink) + (wide_tiles(sink) ? "_wide" : "") + "_" + std::to_string((int)sink);
     if (FILE* f = fopen((base + ".hsaco").c_str(), "wb")) { fwrite(code.data(), 1, code.size(), f); fclose(f); }
     if (FILE* f = fopen((base + ".hip").c_str(), "wb")) { fwrite(src.data(), 1, src.size(), f); fclose(f); }
   }

@@ -34,6 +34,9 @@ enum Sink { REGAGG = 0, LDSAGG, DENSE, HASH, WIDE, JOIN_BUILD, PROBE_AGG, DIRECT
             PART3_SCATTER_PAIR, PART3_AGG_PAIR = PART3_SCATTER_PAIR + 16, PART3_AGG_PAIR_DIRECT,
             // ... and with the value as a 48-bit offset (fused::kPackPairV, hash mode): PART3_SCATTER_PAIRV + (tiles - 1) + 4 * hot
             PART3_SCATTER_PAIRV, PART3_AGG_PAIRV = PART3_SCATTER_PAIRV + 8,
+            // the two aggregate scans over 512-row wide tiles (fused_sinks.hpp fused_scan_body<P, Sink, true>; plain scan sinks, launched with launch()).  A kind of
+            // its own each: kernel symbol and disk-cache key differ from the 128-row form's
+            REGAGG_WIDE, LDSAGG_WIDE,
             kNumSinks };
 inline Sink part3_scatter_sink(uint32_t mode, uint32_t tiles, uint32_t pack, bool hot) {
   if (pack == fused::kPackPairV) return (Sink)(PART3_SCATTER_PAIRV + (tiles - 1) + (hot ? 4 : 0));

@@ -28,11 +28,16 @@
 //     The aggregate scans over rows of at most 16 bytes also leave the bitmap test out
 //     of the loads of their non-nullable inputs (trust_nullable): the loads of a tile
 //     are then one basic block.
+//   * wide tiles: when none of those inputs is nullable and every column pointer is
+//     aligned to eight rows, the same scans run over 512-row wave tiles (lane l holds
+//     rows 8l .. 8l+7: one 8- or 16-byte load per column and lane; fused_device.hpp
+//     wide_load, wide_tiles_choice below) and finish the last < 512 rows per 128-row tile.
 #include "fused_sinks.hpp"
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
 #include "scan.hpp"
 #include "jit.hpp"
+#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -44,7 +49,7 @@
 #define PLX_STATIC_PROBE_AGG_CASES \
   case SHAPE_Q3_PROBE: hipLaunchKernelGGL((fused_scan_kernel<StatProg<SHAPE_Q3_PROBE>, ProbeAggSink>), dim3(grid), dim3(kBlock), 0, stream(), sh, args, t); break;
 #define PLX_STATIC_REGAGG_EXTRA_CASES \
-  case SHAPE_Q3_COUNT: PLX_LAUNCH_SCAN(StatProg<SHAPE_Q3_COUNT>, RegAggSink, grid, 0, sh, args, sp); break;
+  case SHAPE_Q3_COUNT: launch_static<SHAPE_Q3_COUNT, RegAggSink>(wide, grid, 0, sh, args, sp); break;
 #define PLX_STATIC_DIRECT_BUILD_CASES \
   case SHAPE_Q3_BUILD: hipLaunchKernelGGL((fused_scan_kernel<StatProg<SHAPE_Q3_BUILD>, DirectBuildSink>), dim3(grid), dim3(kBlock), 0, stream(), sh, args, t); break; \
   case SHAPE_Q3D_BUILD: hipLaunchKernelGGL((fused_scan_kernel<StatProg<SHAPE_Q3D_BUILD>, DirectBuildSink>), dim3(grid), dim3(kBlock), 0, stream(), sh, args, t); break;
@@ -58,7 +63,7 @@
 #define PLX_STATIC_Q3F_DIRECT_BUILD_CASES \
   case SHAPE_Q3F_BUILD: hipLaunchKernelGGL((fused_scan_kernel<StatProg<SHAPE_Q3F_BUILD>, DirectBuildSink>), dim3(grid), dim3(kBlock), 0, stream(), sh, args, t); break;
 #define PLX_STATIC_Q3F_REGAGG_CASES \
-  case SHAPE_Q3F_COUNT: PLX_LAUNCH_SCAN(StatProg<SHAPE_Q3F_COUNT>, RegAggSink, grid, 0, sh, args, sp); break;
+  case SHAPE_Q3F_COUNT: launch_static<SHAPE_Q3F_COUNT, RegAggSink>(wide, grid, 0, sh, args, sp); break;
 #else
 #define PLX_STATIC_BITMAP_BUILD_CASES
 #define PLX_STATIC_Q3F_JOIN_BUILD_CASES
@@ -114,9 +119,9 @@ __global__ __launch_bounds__(kBlock) void partials_finish_kernel(Shape sh, const
 // workgroups per CU than with 4, 6 or 8 (Q1 4.15 vs 4.61 / 4.40 / 4.46 ms, config 2 3.82 vs 4.12 / 4.05 ms, Q3 build 0.85 vs
 // 0.91 / 0.90 / 0.98 ms; gpurun_out/r02m, same box, repeated), while the probe scan wants 8 or 16 (1.83 ms; 2.34 with 10, 2.13
 // with 12): the grid-stride distance between a wave's consecutive tiles decides which HBM channels its columns land on together.
-static int scan_grid(int64_t n_rows, int blocks_per_cu, const char* knob = nullptr) {
+static int scan_grid(int64_t n_rows, int blocks_per_cu, const char* knob = nullptr, int tile_rows = kTileRows) {
   if (knob) { const char* e = getenv(knob); const int v = e ? atoi(e) : 0; if (v >= 1 && v <= 32) blocks_per_cu = v; }
-  int64_t ntiles = (n_rows + kTileRows - 1) / kTileRows;
+  int64_t ntiles = (n_rows + tile_rows - 1) / tile_rows;
   return grid_for(ntiles, kBlock / 64, blocks_per_cu);
 }
 // which ahead-of-time aggregate scans compile the bitmap test out of their non-nullable loads (fused_sinks.hpp trust_nullable): the wide-row kernels are untouched
@@ -135,20 +140,55 @@ static uint64_t algo_bytes(const Shape& sh, const Args& args) {
 #define PLX_LAUNCH_SCAN(PROG, SINK, grid, lds, sh, args, sp) \
   hipLaunchKernelGGL((fused_scan_kernel<PROG, SINK>), dim3(grid), dim3(kBlock), (lds), stream(), sh, args, sp)
 
+// ---- wide tiles: the host's choice -------------------------------------------------------------------------------------------
+// The 512-row form of a compiled aggregate scan (fused_sinks.hpp wide_tiles_form) loads eight consecutive rows of every column with one instruction per lane, so every
+// column pointer must be aligned to its eight-row pack (8, 16, 32 or 64 bytes by width): engine.cpp offset_args can hand a scan pointers that are not (a sliced frame).
+// PLX_WIDE_TILES=0 (read once) keeps the 128-row kernels: measurement runs and the tests.
+static bool wide_tiles_knob() {
+  static const bool on = [] { const char* e = getenv("PLX_WIDE_TILES"); return !(e && e[0] == '0'); }();
+  return on;
+}
+bool wide_tiles_choice(const Shape& sh, const Args& args, bool compiled, bool knob_on) {
+  if (!compiled || !knob_on || args.n_rows < kWideTileRows || !wide_tiles_shape(sh)) return false;
+  for (int i = 0; i < sh.n_inputs; i++) {
+    if (args.in[i].validity) return false;
+    if ((uintptr_t)args.in[i].values % (uintptr_t)(kWideRows * wide_dtype_bytes(sh.in_dtype[i])) != 0) return false;
+  }
+  return true;
+}
+static std::atomic<int> g_last_tile_rows{0};
+int last_scan_tile_rows() { return g_last_tile_rows.load(std::memory_order_relaxed); }
+// an ahead-of-time shape: its wide kernel exists exactly when wide_tiles_choice can say yes for it
+template <int ID, class Sink>
+static void launch_static(bool wide, int grid, size_t lds, const Shape& sh, const Args& args, const typename Sink::Params& sp) {
+  if constexpr (wide_tiles_form<StatProg<ID>, Sink>()) {
+    if (wide) { hipLaunchKernelGGL((fused_scan_wide_kernel<StatProg<ID>, Sink>), dim3(grid), dim3(kBlock), lds, stream(), sh, args, sp); return; }
+  }
+  PLX_REQUIRE(!wide, PLX_ERR_INVALID, "fused scan: no wide-tile kernel for this shape");
+  PLX_LAUNCH_SCAN(StatProg<ID>, Sink, grid, lds, sh, args, sp);
+}
+
 void fused_regagg(const Shape& sh, const Args& args, int static_id, uint64_t* out_host) {
-  const int grid = scan_grid(args.n_rows, 5, "PLX_BPC_REGAGG");
+  const bool wide = wide_tiles_choice(sh, args, static_id >= 0 || jit::program_mode(static_id, args.n_rows)[0] == 'j', wide_tiles_knob());
+  g_last_tile_rows.store(wide ? kWideTileRows : kTileRows, std::memory_order_relaxed);
+  const int grid = scan_grid(args.n_rows, 5, "PLX_BPC_REGAGG", wide ? kWideTileRows : kTileRows);
   Buf partials = dev_alloc(sizeof(uint64_t) * (size_t)(grid + 1) * kMaxAggs);
   unsigned long long* pp = partials->as<unsigned long long>();
   RegAggSink::Params sp{pp};
   {
     ProfileScope ps(scope_name("fused_scan_regagg_static", "fused_scan_regagg_generic", static_id).c_str(), algo_bytes(sh, args), (uint64_t)args.n_rows);
     switch (static_id) {
-      case SHAPE_CFG2: PLX_LAUNCH_SCAN(StatProg<SHAPE_CFG2>, RegAggSink, grid, 0, sh, args, sp); break;
-      case SHAPE_CFG2_NULLX: PLX_LAUNCH_SCAN(StatProg<SHAPE_CFG2_NULLX>, RegAggSink, grid, 0, sh, args, sp); break;
-      case SHAPE_CFG1: PLX_LAUNCH_SCAN(StatProg<SHAPE_CFG1>, RegAggSink, grid, 0, sh, args, sp); break;
+      case SHAPE_CFG2: launch_static<SHAPE_CFG2, RegAggSink>(wide, grid, 0, sh, args, sp); break;
+      case SHAPE_CFG2_NULLX: launch_static<SHAPE_CFG2_NULLX, RegAggSink>(wide, grid, 0, sh, args, sp); break;
+      case SHAPE_CFG1: launch_static<SHAPE_CFG1, RegAggSink>(wide, grid, 0, sh, args, sp); break;
       PLX_STATIC_REGAGG_EXTRA_CASES
       PLX_STATIC_Q3F_REGAGG_CASES
-      default: if (!jit::launch(sh, args, jit::REGAGG, &sp, grid, 0)) { const DynLaunch d = dyn_launch(sh, args, 0); PLX_LAUNCH_SCAN(DynProg, RegAggSink, grid, d.lds, sh, d.args, sp); } break;
+      default:
+        if (!jit::launch(sh, args, wide ? jit::REGAGG_WIDE : jit::REGAGG, &sp, grid, 0)) {
+          g_last_tile_rows.store(kTileRows, std::memory_order_relaxed);      // (no compiled kernel after all: the interpreter, whatever tile size the grid was cut for)
+          const DynLaunch d = dyn_launch(sh, args, 0); PLX_LAUNCH_SCAN(DynProg, RegAggSink, grid, d.lds, sh, d.args, sp);
+        }
+        break;
     }
     PLX_HIP(hipGetLastError());
   }
@@ -210,7 +250,9 @@ void fused_lds_agg(const Shape& sh, const Args& args, int n_groups, int static_i
   PLX_REQUIRE(copies > 0, PLX_ERR_INVALID, "fused_lds_agg: group table does not fit LDS");
   const int cells = n_groups * sh.n_aggs;
   const size_t lds = (size_t)cells * copies * 8;
-  const int grid = scan_grid(args.n_rows, 5, "PLX_BPC_LDSAGG");
+  const bool wide = wide_tiles_choice(sh, args, static_id >= 0 || jit::program_mode(static_id, args.n_rows)[0] == 'j', wide_tiles_knob());
+  g_last_tile_rows.store(wide ? kWideTileRows : kTileRows, std::memory_order_relaxed);
+  const int grid = scan_grid(args.n_rows, 5, "PLX_BPC_LDSAGG", wide ? kWideTileRows : kTileRows);
   const bool use_partials = n_groups <= 64;
   Buf partials;
   LdsAggSink::Params sp{};
@@ -220,10 +262,15 @@ void fused_lds_agg(const Shape& sh, const Args& args, int n_groups, int static_i
   {
     ProfileScope ps(scope_name("fused_scan_ldsagg_static", "fused_scan_ldsagg_generic", static_id).c_str(), algo_bytes(sh, args), (uint64_t)args.n_rows);
     switch (static_id) {
-      case SHAPE_Q1: PLX_LAUNCH_SCAN(StatProg<SHAPE_Q1>, LdsAggSink, grid, lds, sh, args, sp); break;
-      case SHAPE_Q1_ENCODED: PLX_LAUNCH_SCAN(StatProg<SHAPE_Q1_ENCODED>, LdsAggSink, grid, lds, sh, args, sp); break;
-      case SHAPE_Q1_ENCODED_PRICE: PLX_LAUNCH_SCAN(StatProg<SHAPE_Q1_ENCODED_PRICE>, LdsAggSink, grid, lds, sh, args, sp); break;
-      default: if (!jit::launch(sh, args, jit::LDSAGG, &sp, grid, lds)) { const DynLaunch d = dyn_launch(sh, args, lds); PLX_LAUNCH_SCAN(DynProg, LdsAggSink, grid, d.lds, sh, d.args, sp); } break;
+      case SHAPE_Q1: launch_static<SHAPE_Q1, LdsAggSink>(wide, grid, lds, sh, args, sp); break;
+      case SHAPE_Q1_ENCODED: launch_static<SHAPE_Q1_ENCODED, LdsAggSink>(wide, grid, lds, sh, args, sp); break;
+      case SHAPE_Q1_ENCODED_PRICE: launch_static<SHAPE_Q1_ENCODED_PRICE, LdsAggSink>(wide, grid, lds, sh, args, sp); break;
+      default:
+        if (!jit::launch(sh, args, wide ? jit::LDSAGG_WIDE : jit::LDSAGG, &sp, grid, lds)) {
+          g_last_tile_rows.store(kTileRows, std::memory_order_relaxed);
+          const DynLaunch d = dyn_launch(sh, args, lds); PLX_LAUNCH_SCAN(DynProg, LdsAggSink, grid, d.lds, sh, d.args, sp);
+        }
+        break;
     }
     PLX_HIP(hipGetLastError());
   }

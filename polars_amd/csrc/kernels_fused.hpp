@@ -19,6 +19,12 @@ void fused_regagg(const fused::Shape& sh, const fused::Args& args, int static_id
 int lds_agg_copies(int n_groups, int n_aggs);
 void fused_lds_agg(const fused::Shape& sh, const fused::Args& args, int n_groups, int static_id, uint64_t* out_dev, unsigned int* oob = nullptr /* device flag: a group id outside the table */);
 
+// The two scans above run over 512-row wave tiles (kernels_fused.hip "wide tiles") when this says so: a compiled program (ahead of time or at run time) over narrow
+// rows, no nullable input, at least one whole tile, every column pointer aligned to eight rows, and the knob (PLX_WIDE_TILES, read once by the launchers) on.
+bool wide_tiles_choice(const fused::Shape& sh, const fused::Args& args, bool compiled, bool knob_on);
+// rows per wave tile of the last fused_regagg / fused_lds_agg launch: 512, 128, or 0 before the first
+int last_scan_tile_rows();
+
 // filter -> exprs -> atomics into an HBM table. Tables must be initialised with
 // fill_u64(keys, cap + 2, kEmptyKey) / init_agg_cells(acc, slots, sh).
 void fused_dense_agg(const fused::Shape& sh, const fused::Args& args, const fused::DenseTable& t, int static_id);
