@@ -125,7 +125,13 @@ typedef enum plx_agg_op {
   PLX_AGG_MAX = 3,
   PLX_AGG_COUNT = 4, /* non-null count, u32 (IdxSize) */
   PLX_AGG_LEN = 5,   /* row count incl. nulls, u32 */
-  PLX_AGG_FIRST = 6  /* first row of each group (group_by only; used for key columns) */
+  PLX_AGG_FIRST = 6, /* first row of each group (group_by only; used for key columns) */
+  /* Variance / standard deviation of the valid rows with `ddof` delta degrees of freedom: f64 (f32 stays f32), null when valid rows <= ddof; a NaN or an
+   * infinity among the values gives NaN.  A PLX_AE_AGG node of these kinds carries ddof (0..255) in lit.u; plx_groupby_agg uses ddof = 1, plx_groupby_agg_ddof
+   * takes one per aggregate; a whole column goes through plx_reduce_var (plx_reduce refuses the two kinds).  Numeric operands only: a Boolean operand is
+   * PLX_ERR_UNSUPPORTED.  Fused scans accumulate sums about a pivot: the accuracy contract is DESIGN.md 4.14. */
+  PLX_AGG_VAR = 7,
+  PLX_AGG_STD = 8
 } plx_agg_op;
 
 /* Null keys match nothing (nulls_equal is not on this path).  PLX_JOIN_FULL: every pair of the inner join, one row per unmatched left row (null right index) and one
@@ -299,6 +305,10 @@ int plx_gather(plx_column col, plx_column idx, plx_column* out);
  * *out_dtype (sum: SumCast rule; mean: f64, f32 stays f32; count/len: u32);
  * *out_valid = 0 when the result is null (mean/min/max of empty or all-null). */
 int plx_reduce(plx_agg_op op, plx_column col, plx_scalar* out_value, plx_dtype* out_dtype, int32_t* out_valid);
+/* Whole-column variance (want_std != 0: standard deviation) with ddof 0..255 delta degrees of freedom.  *out_dtype is f64 (f32 for an f32 column);
+ * *out_valid = 0 when the column has at most ddof valid rows.  One streaming pass of Chan merges, no atomics: the same column gives the same bits every time, and
+ * a common offset of any size costs no digits.  Numeric columns only (PLX_ERR_UNSUPPORTED names the dtype otherwise). */
+int plx_reduce_var(plx_column col, int32_t ddof, int32_t want_std, plx_scalar* out_value, plx_dtype* out_dtype, int32_t* out_valid);
 
 /* Hash group-by with in-place aggregation.  n_keys >= 1 key columns (integer,
  * bool or float; a null key forms its own group; floats canonicalised).
@@ -309,6 +319,10 @@ int plx_reduce(plx_agg_op op, plx_column col, plx_scalar* out_value, plx_dtype* 
 int plx_groupby_agg(const plx_column* keys, int32_t n_keys, const plx_column* values,
                     const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order,
                     plx_column* out_keys, plx_column* out_aggs);
+/* The same with ddof[i] (0..255) for aggregate i: read for PLX_AGG_VAR / PLX_AGG_STD, ignored for every other kind.  ddof == NULL: 1 everywhere. */
+int plx_groupby_agg_ddof(const plx_column* keys, int32_t n_keys, const plx_column* values,
+                         const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order, const int32_t* ddof,
+                         plx_column* out_keys, plx_column* out_aggs);
 
 /* Equi-join on one key column pair -> row-index pairs (PLX_U32). For LEFT joins the
  * right index column carries nulls for unmatched left rows. Null keys never match.
@@ -761,7 +775,7 @@ int plx_profile_clear(void);
  *   _polars_plugin_field_<name>(fields, n, out, kwargs, kwargs_len)   output field (minor 1 signature, plugin.rs:186-207)
  * Functions: plx_cmp / plx_arith (kwargs {"op": "gt" | ... | "add" | ...}) and one symbol per operator for callers
  * without kwargs: plx_eq ne lt le gt ge, plx_add sub mul truediv floordiv mod, plx_filter(values, mask),
- * plx_when_then_otherwise(mask, then, otherwise), plx_dt_part(values; kwargs part, unit), plx_sum mean min max (length-1 result).  Python side: polars.plugins.register_plugin_function(
+ * plx_when_then_otherwise(mask, then, otherwise), plx_dt_part(values; kwargs part, unit), plx_sum mean min max (length-1 result), plx_var / plx_std (length-1 result; kwargs ddof).  Python side: polars.plugins.register_plugin_function(
  *     plugin_path=".../libpolars_amd.so", function_name="plx_gt", args=[pl.col("a"), pl.lit(3)]).           */
 typedef struct plx_caller_context { uint64_t bitflags; } plx_caller_context;
 uint32_t _polars_plugin_get_version(void);
@@ -777,6 +791,11 @@ PLX_DECLARE_PLUGIN(plx_add) PLX_DECLARE_PLUGIN(plx_sub) PLX_DECLARE_PLUGIN(plx_m
 PLX_DECLARE_PLUGIN(plx_sum) PLX_DECLARE_PLUGIN(plx_mean) PLX_DECLARE_PLUGIN(plx_min) PLX_DECLARE_PLUGIN(plx_max)
 PLX_DECLARE_PLUGIN(plx_when_then_otherwise)   /* (mask, then, otherwise): plx_if_then_else; the field is the `then` input's */
 PLX_DECLARE_PLUGIN(plx_dt_part)               /* (values): plx_temporal_part; kwargs {"part": "year" | ..., "unit": "date" | "ms" | "us" | "ns"}; the field is the part's dtype */
+/* plx_var / plx_std (values): plx_reduce_var; kwargs {"ddof": 0..255} (absent: 1); a length-1 result; the field is Float64, Float32 for a Float32 input */
+void _polars_plugin_plx_var(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
+void _polars_plugin_field_plx_var(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
+void _polars_plugin_plx_std(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
+void _polars_plugin_field_plx_std(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
 
 #ifdef __cplusplus
 }

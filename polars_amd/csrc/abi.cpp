@@ -345,7 +345,16 @@ int plx_filter(plx_column col, plx_column mask, plx_column* out) { PLX_TRY *out 
 int plx_gather(plx_column col, plx_column idx, plx_column* out) { PLX_TRY *out = register_column(ops::gather(get_column(col), get_column(idx))); PLX_CATCH }
 int plx_reduce(plx_agg_op op, plx_column col, plx_scalar* out_value, plx_dtype* out_dtype, int32_t* out_valid) {
   PLX_TRY
+  PLX_REQUIRE(op != PLX_AGG_VAR && op != PLX_AGG_STD, PLX_ERR_INVALID, "plx_reduce: var / std take ddof: call plx_reduce_var");
   ops::ScalarValue r = ops::reduce(op, get_column(col));
+  if (out_value) *out_value = r.v;
+  if (out_dtype) *out_dtype = (plx_dtype)r.dtype;
+  if (out_valid) *out_valid = r.valid ? 1 : 0;
+  PLX_CATCH
+}
+int plx_reduce_var(plx_column col, int32_t ddof, int32_t want_std, plx_scalar* out_value, plx_dtype* out_dtype, int32_t* out_valid) {
+  PLX_TRY
+  ops::ScalarValue r = ops::reduce_var(get_column(col), ddof, want_std != 0);
   if (out_value) *out_value = r.v;
   if (out_dtype) *out_dtype = (plx_dtype)r.dtype;
   if (out_valid) *out_valid = r.valid ? 1 : 0;
@@ -354,14 +363,18 @@ int plx_reduce(plx_agg_op op, plx_column col, plx_scalar* out_value, plx_dtype* 
 
 int plx_groupby_agg(const plx_column* keys, int32_t n_keys, const plx_column* values, const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order,
                     plx_column* out_keys, plx_column* out_aggs) {
+  return plx_groupby_agg_ddof(keys, n_keys, values, aggs, n_aggs, maintain_order, nullptr, out_keys, out_aggs);
+}
+int plx_groupby_agg_ddof(const plx_column* keys, int32_t n_keys, const plx_column* values, const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order,
+                         const int32_t* ddof, plx_column* out_keys, plx_column* out_aggs) {
   PLX_TRY
   PLX_REQUIRE(keys && n_keys >= 1 && (n_aggs == 0 || (values && aggs && out_aggs)) && out_keys, PLX_ERR_INVALID, "bad arguments");
   std::vector<ColumnPtr> k, v, ok, oa;
-  std::vector<int> a;
+  std::vector<int> a, dd;
   for (int i = 0; i < n_keys; i++) k.push_back(get_column(keys[i]));
-  for (int i = 0; i < n_aggs; i++) { a.push_back(aggs[i]); v.push_back((aggs[i] == PLX_AGG_LEN || values[i] == 0) ? nullptr : get_column(values[i])); }
+  for (int i = 0; i < n_aggs; i++) { a.push_back(aggs[i]); dd.push_back(ddof ? ddof[i] : 1); v.push_back((aggs[i] == PLX_AGG_LEN || values[i] == 0) ? nullptr : get_column(values[i])); }
   std::string d;
-  engine::groupby_columns(k, v, a, maintain_order != 0, ok, oa, &d);
+  engine::groupby_columns(k, v, a, maintain_order != 0, ok, oa, &d, &dd);
   t_plan_desc = d;
   for (int i = 0; i < n_keys; i++) out_keys[i] = register_column(ok[i]);
   for (int i = 0; i < n_aggs; i++) out_aggs[i] = register_column(oa[i]);
@@ -558,6 +571,26 @@ std::string pickle_str_value(const uint8_t* kw, size_t n, const char* key) {
   for (size_t i = 0; i + 1 < toks.size(); i++) if (toks[i] == key) return toks[i + 1];
   return "";
 }
+// value of an integer-valued key in a pickled dict: the key's str token, an optional memo op (MEMOIZE / BINPUT / LONG_BINPUT), then BININT1 / BININT2 / BININT; a str
+// value holding decimal digits counts too.  `absent` when the key is not there; -1 when its value is neither.  A byte scan, not a pickle parser: it is meant for the
+// flat {"ddof": int} kwargs the two symbols document -- a dict that holds the key's text as a VALUE, or other string items next to a non-integer ddof, is misread
+long long pickle_int_value(const uint8_t* kw, size_t n, const char* key, long long absent) {
+  const size_t klen = strlen(key);
+  for (size_t i = 0; i + 2 + klen <= n; i++) {
+    if (!((kw[i] == 0x8c || kw[i] == 'U') && kw[i + 1] == klen && !memcmp(kw + i + 2, key, klen))) continue;
+    size_t j = i + 2 + klen;
+    if (j < n && kw[j] == 0x94) j += 1; else if (j < n && kw[j] == 'q') j += 2; else if (j < n && kw[j] == 'r') j += 5;
+    if (j + 1 < n && kw[j] == 'K') return kw[j + 1];
+    if (j + 2 < n && kw[j] == 'M') return (long long)kw[j + 1] | ((long long)kw[j + 2] << 8);
+    if (j + 4 < n && kw[j] == 'J') { int32_t v; memcpy(&v, kw + j + 1, 4); return v; }
+    const std::string sv = pickle_str_value(kw, n, key);
+    if (sv.empty() || sv.size() > 9) return -1;
+    long long v = 0;
+    for (char ch : sv) { if (ch < '0' || ch > '9') return -1; v = v * 10 + (ch - '0'); }
+    return v;
+  }
+  return absent;
+}
 // a length-1 input is a literal (Polars broadcasts it): read it on the host instead of uploading it
 bool series_scalar(const plx_series_export& s, int dt, plx_scalar* out, bool* valid) {
   int64_t total = 0; const ArrowArray* one = nullptr;
@@ -720,6 +753,17 @@ PLX_PLUGIN_CMP(eq, PLX_EQ) PLX_PLUGIN_CMP(ne, PLX_NE) PLX_PLUGIN_CMP(lt, PLX_LT)
 PLX_PLUGIN_ARITH(add, PLX_ADD) PLX_PLUGIN_ARITH(sub, PLX_SUB) PLX_PLUGIN_ARITH(mul, PLX_MUL) PLX_PLUGIN_ARITH(truediv, PLX_TRUE_DIV)
 PLX_PLUGIN_ARITH(floordiv, PLX_FLOOR_DIV) PLX_PLUGIN_ARITH(mod, PLX_MOD)
 PLX_PLUGIN_REDUCE(sum, PLX_AGG_SUM, FIELD_SUM) PLX_PLUGIN_REDUCE(mean, PLX_AGG_MEAN, FIELD_MEAN) PLX_PLUGIN_REDUCE(min, PLX_AGG_MIN, FIELD_SAME) PLX_PLUGIN_REDUCE(max, PLX_AGG_MAX, FIELD_SAME)
+// var / std of a series: kwargs {"ddof": 0..255} (absent: 1); a length-1 result under the input's name, Float64 (Float32 for a Float32 input)
+#define PLX_PLUGIN_VAR(NAME, WANT_STD)                                                                                                            \
+  void _polars_plugin_plx_##NAME(PLX_PLUGIN_SIG) {                                                                                                \
+    const long long ddof = pickle_int_value(kwargs, kwargs_len, "ddof", 1);                                                                      \
+    plugin_call(inputs, n_inputs, out, ctx, 1, [&](std::vector<PluginInput>& in) {                                                                \
+      PLX_REQUIRE(ddof >= 0 && ddof <= 255, PLX_ERR_INVALID, "plx_" #NAME ": kwargs ddof must be an integer 0..255");                            \
+      return ops::scalar_column(ops::reduce_var(in[0].col, (int)ddof, WANT_STD));                                                                 \
+    });                                                                                                                                           \
+  }                                                                                                                                               \
+  void _polars_plugin_field_plx_##NAME(PLX_FIELD_SIG) { (void)kwargs; (void)kwargs_len; plugin_field(fields, n_fields, out, FIELD_MEAN, 0); }
+PLX_PLUGIN_VAR(var, false) PLX_PLUGIN_VAR(std, true)
 void _polars_plugin_plx_filter(PLX_PLUGIN_SIG) {
   (void)kwargs; (void)kwargs_len;
   plugin_call(inputs, n_inputs, out, ctx, 2, [&](std::vector<PluginInput>& in) {

@@ -21,6 +21,7 @@
 #include "ops.hpp"
 #include "sort.hpp"
 #include "temporal.hpp"
+#include "variance.hpp"
 
 namespace plx {
 namespace engine {
@@ -57,6 +58,8 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       PLX_REQUIRE(e.lit.u < (uint64_t)temporal::kNumUnits && temporal::part_ok(e.op, (int)e.lit.u), PLX_ERR_INVALID,
                   "date part: part " + std::to_string(e.op) + " of unit " + std::to_string((long long)e.lit.i) + " (plx_temporal_part_kind 0..9, plx_time_unit 0..3; the time of day and date() exist for a Datetime only)");
     }
+    if (e.kind == PLX_AE_AGG && (e.op == PLX_AGG_VAR || e.op == PLX_AGG_STD))
+      PLX_REQUIRE(e.lhs >= 0 && e.lit.u <= 255, PLX_ERR_INVALID, "var / std: the node carries ddof 0..255 in lit.u, got " + std::to_string((long long)e.lit.i));
     PLX_REQUIRE(e.lhs < i && e.rhs < i && e.cond < i, PLX_ERR_INVALID, "AExpr arena must be topologically ordered (children before parents)");
     p.ae.push_back(std::move(e));
   }
@@ -147,6 +150,9 @@ int infer_dtype(const Plan& plan, int e, const Frame& schema) {
       switch (x.op) {
         case PLX_AGG_SUM: return sum_out_dtype(in);
         case PLX_AGG_MEAN: return in == PLX_F32 ? PLX_F32 : PLX_F64;
+        case PLX_AGG_VAR: case PLX_AGG_STD:
+          PLX_REQUIRE(dtype_is_int(in) || dtype_is_float(in), PLX_ERR_UNSUPPORTED, std::string(x.op == PLX_AGG_STD ? "std" : "var") + " of a " + dtype_name(in) + " expression: numeric operands only");
+          return in == PLX_F32 ? PLX_F32 : PLX_F64;
         case PLX_AGG_COUNT: case PLX_AGG_LEN: return PLX_U32;
         default: return in;
       }
@@ -260,6 +266,7 @@ static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<i
     case PLX_AE_LEN: { ops::ScalarValue s; s.dtype = PLX_U32; s.valid = true; s.v.u = (uint32_t)df.height; return {ops::scalar_column(s), true}; }
     case PLX_AE_AGG: {
       Evaluated c = eval(plan, x.lhs, df, overrides);
+      if (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD) return {ops::scalar_column(ops::reduce_var(c.col, (int)x.lit.u, x.op == PLX_AGG_STD)), true};
       return {ops::scalar_column(ops::reduce(x.op, c.col)), true};
     }
     case PLX_AE_BINARY: {
@@ -543,6 +550,45 @@ class Compiler {
   }
   int count_agg(int src) { return nodes[src].nullable ? add_agg(AGG_COUNT, src) : add_agg(AGG_LEN, -1); }
 
+  // ---- var / std: sums about a pivot ----
+  // The cells of the sinks are commutative atomics: they can hold sum(x - p) and sum((x - p)^2), not a Welford state.  p = the mean of the source expression over the
+  // first kVarPivotRows rows of the frame (the query's predicate left out), from a throw-away fused select and one small download; 0 when none of those rows is valid,
+  // when that mean is not finite, and when nothing may be launched (compile only).  Any convex combination of source values lies inside [min, max] of the source, which
+  // is all the accuracy contract asks of it.  One pivot per (program, source node).
+  static constexpr int64_t kVarPivotRows = 4096;
+  bool device_pivot = false;                       // set by the drivers that are about to run the program on the device
+  std::vector<std::pair<int, double>> var_pivots;  // (f64 source node, p)
+  std::vector<std::pair<int, double>> pivot_by_expr;   // (source expression of the plan, p): every var / std node lowered here
+  std::vector<std::pair<int, double>> seed_pivots;     // pivots another compiler of the same plan took over the same rows (the left join's second program): no second pre-pass
+  std::string var_note;                            // "var pivot x=...; " per source, for the plan description
+  double var_pivot(int src_expr, int sf) {
+    for (auto& pv : var_pivots) if (pv.first == sf) { pivot_by_expr.push_back({src_expr, pv.second}); return pv.second; }
+    double p = 0.0;
+    bool seeded = false;
+    for (auto& pv : seed_pivots) if (pv.first == src_expr) { p = pv.second; seeded = true; }
+    const int64_t rows = std::min<int64_t>(n_rows, kVarPivotRows);
+    if (!seeded && device_pivot && rows > 0) {
+      Compiler t(plan, *df);
+      t.n_rows = rows;
+      const int s = t.lower(src_expr);
+      const int tf = t.nodes[s].ty == 'f' ? s : t.mk(t.nodes[s].ty == 'u' ? OP_U2F : OP_I2F, s, s, 'f');
+      const int sum_idx = t.add_agg(AGG_SUM_F, tf), cnt_idx = t.count_agg(s);
+      t.finish();
+      uint64_t host[kMaxAggs] = {0};
+      k::fused_regagg(t.shape, t.args, find_static_shape(t.shape), host);
+      const uint64_t cnt = t.shape.aggs[cnt_idx].kind == AGG_LEN ? (uint64_t)rows : host[cnt_idx];
+      double sum; memcpy(&sum, &host[sum_idx], 8);
+      if (cnt) p = sum / (double)cnt;
+      if (!std::isfinite(p)) p = 0.0;
+    }
+    var_pivots.push_back({sf, p});
+    pivot_by_expr.push_back({src_expr, p});
+    std::ostringstream o; o.precision(17);
+    o << "var pivot " << output_name(plan, src_expr) << "=" << p << "; ";
+    var_note += o.str();
+    return p;
+  }
+
   // lowers one AGG / LEN node; returns how to finalise it
   FinalSpec lower_agg(int e) {
     const AE& x = plan.ae.at(e);
@@ -552,6 +598,7 @@ class Compiler {
     if (x.op == PLX_AGG_LEN) { fs.kind = FIN_TRUNC32; fs.a = (uint8_t)add_agg(AGG_LEN, -1); fs.out_dtype = PLX_U32; return fs; }
     // Boolean inputs: sum = number of true values (UInt32, sum_output_dtype) and mean = their fraction; a boolean slot holds 0 / 1,
     // so both reuse the integer cells.  min / max of booleans would need a bit-packed finalisation: per-node path.
+    if (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD) infer_dtype(plan, e, *df);      // (fails, naming the dtype, when the operand is not numeric)
     if (in_dt == PLX_BOOL && x.op != PLX_AGG_COUNT && x.op != PLX_AGG_SUM && x.op != PLX_AGG_MEAN) throw Unsupported("min / max of a boolean expression");
     int src = lower(x.lhs);
     switch (x.op) {
@@ -574,6 +621,20 @@ class Compiler {
         return fs;
       }
       case PLX_AGG_COUNT: fs.kind = FIN_TRUNC32; fs.a = (uint8_t)count_agg(src); fs.out_dtype = PLX_U32; return fs;
+      case PLX_AGG_VAR: case PLX_AGG_STD: {
+        // d = s - p, q = d * d; cells sum(d), sum(q), count(src): std / var / any ddof over one source share all three (add_agg dedups).  p is an immediate of
+        // OP_CONST, so the Shape does not depend on it
+        // (the source is an integer or an f64 node here: load() refuses Float32 columns, so fs.out_dtype is always f64 from this compiler -- Float32 results come from
+        //  groupby_columns' f64 view and from the per-node kernel)
+        int sf = src;
+        if (nodes[src].ty != 'f') sf = mk(nodes[src].ty == 'u' ? OP_U2F : OP_I2F, src, src, 'f');
+        const int d = mk(OP_SUB_F, sf, konst_f(var_pivot(x.lhs, sf)), 'f');
+        const int q = mk(OP_MUL_F, d, d, 'f');
+        fs.kind = x.op == PLX_AGG_STD ? FIN_STD : FIN_VAR;
+        fs.a = (uint8_t)add_agg(AGG_SUM_F, d); fs.c = (uint8_t)add_agg(AGG_SUM_F, q); fs.b = (uint8_t)count_agg(src);
+        fs.ddof = (uint8_t)x.lit.u; fs.out_dtype = PLX_F64;
+        return fs;
+      }
       default: throw Unsupported("aggregation kind");
     }
   }
@@ -1494,7 +1555,7 @@ static ColumnPtr finalize_column(const FusedAggResult& r, const FinalSpec& fs, F
   auto out = std::make_shared<Column>();
   out->dtype = fs.out_dtype; out->len = G;
   out->values = dev_alloc(values_bytes(fs.out_dtype, G));
-  const bool nullable = fs.kind == FIN_MEAN || fs.kind == FIN_MINMAX_I || fs.kind == FIN_MINMAX_F;
+  const bool nullable = fs.kind == FIN_MEAN || fs.kind == FIN_MINMAX_I || fs.kind == FIN_MINMAX_F || fs.kind == FIN_VAR || fs.kind == FIN_STD;
   if (nullable) out->validity = dev_alloc_zero(bitmap_bytes(G)); else out->null_count = 0;
   FinalSpec f = fs;
   if (fs.kind == FIN_COPY64 && dtype_width(fs.out_dtype) < 4) f.kind = FIN_NARROW;
@@ -1587,7 +1648,7 @@ static std::string finals_outputs_fields(const Plan& plan, const std::vector<int
   std::ostringstream o;
   o << "\"finals\":[";
   for (size_t i = 0; i < specs.size(); i++)
-    o << (i ? "," : "") << "{\"kind\":" << (int)specs[i].kind << ",\"a\":" << (int)specs[i].a << ",\"b\":" << (int)specs[i].b << ",\"c\":" << (int)specs[i].c << ",\"out_dtype\":" << (int)specs[i].out_dtype << "}";
+    o << (i ? "," : "") << "{\"kind\":" << (int)specs[i].kind << ",\"a\":" << (int)specs[i].a << ",\"b\":" << (int)specs[i].b << ",\"c\":" << (int)specs[i].c << ",\"out_dtype\":" << (int)specs[i].out_dtype << ",\"ddof\":" << (int)specs[i].ddof << "}";
   o << "],\"outputs\":[";
   for (size_t i = 0; i < out_exprs.size(); i++) {
     int e = out_exprs[i];
@@ -1644,6 +1705,7 @@ static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& pr
       }
   }
   Compiler c(plan, *src);
+  c.device_pivot = !compile_only;
   std::vector<int> agg_nodes;
   std::vector<FinalSpec> specs;
   try {
@@ -1664,7 +1726,7 @@ static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& pr
   r.acc = dev_alloc(sizeof(uint64_t) * kMaxAggs);
   h2d_async(r.acc->ptr, host.data(), sizeof(uint64_t) * (size_t)c.shape.n_aggs);
   PLX_HIP(hipStreamSynchronize(stream()));
-  plan.desc += std::string("FusedFilterAgg{fused_scan[") + jit::program_mode(static_id, c.args.n_rows) + "]+register_sink, inputs=" + std::to_string(c.shape.n_inputs) + ", ops=" + std::to_string(c.shape.n_ops) + ", aggs=" + std::to_string(c.shape.n_aggs) + "}; ";
+  plan.desc += c.var_note + std::string("FusedFilterAgg{fused_scan[") + jit::program_mode(static_id, c.args.n_rows) + "]+register_sink, inputs=" + std::to_string(c.shape.n_inputs) + ", ops=" + std::to_string(c.shape.n_ops) + ", aggs=" + std::to_string(c.shape.n_aggs) + "}; ";
   if (!sp.note.empty()) plan.encoded += sp.note + "; ";
   out = std::make_shared<Frame>();
   out->height = 1;
@@ -1684,6 +1746,7 @@ static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& p
                           std::string* why, bool compile_only) {
   for (int e : node.exprs) if (!contains_agg(plan, e) || contains_column_outside_agg(plan, e)) { if (why) *why = "group_by aggregation list contains a non-aggregated column"; return false; }
   Compiler c(plan, *src);
+  c.device_pivot = !compile_only;
   std::vector<int> agg_nodes;
   std::vector<FinalSpec> specs;
   KeyPlan kp;
@@ -1718,7 +1781,7 @@ static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& p
     plan.desc += "AssumedBoundsViolated{exact statistics, second run}; ";
     return fused_groupby(plan, node, preds, src, out, shape_out, sid_out, why, compile_only);
   }
-  plan.desc += kp.note + "FusedFilterGroupBy{" + d + ", inputs=" + std::to_string(c.shape.n_inputs) + ", ops=" + std::to_string(c.shape.n_ops) + ", aggs=" + std::to_string(c.shape.n_aggs) + ", groups=" + std::to_string(r.n_groups) + "}; ";
+  plan.desc += kp.note + c.var_note + "FusedFilterGroupBy{" + d + ", inputs=" + std::to_string(c.shape.n_inputs) + ", ops=" + std::to_string(c.shape.n_ops) + ", aggs=" + std::to_string(c.shape.n_aggs) + ", groups=" + std::to_string(r.n_groups) + "}; ";
   out = std::make_shared<Frame>();
   out->height = r.n_groups;
   FinBatch batch{};
@@ -2090,6 +2153,7 @@ struct JoinGroupBy {
   std::vector<FinalSpec> specs, aspecs;
   KeyPlan akp;
   int len_idx = -1, a_len_idx = -1;
+  bool device_pivot = false;                            // the programs are about to run: a var / std source gets its pivot from the device (Compiler::var_pivot)
   MemberBitmap unmatched_keys;                          // left join: the build keys that pass the build side's predicate
 };
 
@@ -2124,6 +2188,7 @@ static void compile_join_programs(const Plan& plan, const IRN& gb, JoinGroupBy& 
   cp.pred = and_preds(cp, s.ppreds, j.psemis, nbs);
   cp.key = cp.load(s.pki);
   cp.df = &j.pview;
+  cp.device_pivot = ca.device_pivot = j.device_pivot;
   j.len_idx = cp.add_agg(AGG_LEN, -1);
   for (int e : gb.exprs) collect_aggs(plan, e, j.agg_nodes);
   for (int a : j.agg_nodes) j.specs.push_back(cp.lower_agg(a));
@@ -2145,6 +2210,7 @@ static void compile_join_programs(const Plan& plan, const IRN& gb, JoinGroupBy& 
     for (auto& gk : j.gkeys) if (gk.is_join_key) jk_expr = gk.expr;
     j.akp = lower_keys(ca, std::vector<int>{jk_expr});
     j.a_len_idx = ca.add_agg(AGG_LEN, -1);
+    ca.seed_pivots = cp.pivot_by_expr;      // the same sources over the same probe rows
     for (int a : j.agg_nodes) j.aspecs.push_back(ca.lower_agg(a));
     ca.finish();
   }
@@ -2494,6 +2560,7 @@ static bool unmatched_left_groups(Plan& plan, const IRN& gb, JoinGroupBy& j, Fra
 
 static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::string* why, std::vector<Shape>* shapes_out = nullptr, bool compile_only = false) {
   JoinGroupBy j;
+  j.device_pivot = !compile_only;
   if (!plan_join_groupby(plan, gb, j, why)) return false;
   // count, build, probe, the semi filters' scans, and LAST the probe side's predicate + key program of the partitioned probe's scatter
   if (shapes_out) { shapes_out->push_back(j.cnt->shape); shapes_out->push_back(j.cb->shape); shapes_out->push_back(j.cp->shape); for (auto& u : j.semis) shapes_out->push_back(u.scan->shape); shapes_out->push_back(j.cs->shape); }
@@ -2513,6 +2580,7 @@ static bool fused_join_groupby(Plan& plan, const IRN& gb, FramePtr& out, std::st
   if (!direct_table_route(plan, j, known_dups, g) && !hash_table_route(plan, j, known_dups, multi_ok, rep_cols, g, why)) return false;
   out = matched_groups_frame(plan, gb, j, g);
   if (j.left_join && !unmatched_left_groups(plan, gb, j, *out)) return fused_join_groupby(plan, gb, out, why, shapes_out, compile_only);
+  plan.desc += j.cp->var_note;      // (once per source, from the run that produced the result)
   return true;
 }
 
@@ -2695,17 +2763,18 @@ static FramePtr exec_select(Plan& plan, const IRN& n, bool hstack, FramePtr in_g
 static FramePtr exec_groupby_materialised(Plan& plan, const IRN& n, const FramePtr& in) {
   // evaluate key and aggregation-input expressions as columns, then the generic grouped aggregation
   std::vector<ColumnPtr> keys, values;
-  std::vector<int> aggs, agg_nodes;
+  std::vector<int> aggs, agg_nodes, ddof;
   for (int e : n.keys) keys.push_back(broadcast(eval(plan, e, *in, nullptr), in->height));
   for (int e : n.exprs) collect_aggs(plan, e, agg_nodes);
   for (int a : agg_nodes) {
     const AE& x = plan.ae[a];
+    ddof.push_back(x.kind == PLX_AE_AGG && (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD) ? (int)x.lit.u : 1);
     if (x.kind == PLX_AE_LEN) { aggs.push_back(PLX_AGG_LEN); values.push_back(nullptr); }
     else { aggs.push_back(x.op); values.push_back(broadcast(eval(plan, x.lhs, *in, nullptr), in->height)); }
   }
   std::vector<ColumnPtr> okeys, oaggs;
   std::string d;
-  groupby_columns(keys, values, aggs, n.maintain_order != 0, okeys, oaggs, &d);
+  groupby_columns(keys, values, aggs, n.maintain_order != 0, okeys, oaggs, &d, &ddof);
   plan.desc += "GroupBy{materialised inputs; " + d + "}; ";
   auto out = std::make_shared<Frame>();
   out->height = okeys.empty() ? 0 : okeys[0]->len;
@@ -3265,9 +3334,16 @@ bool dump_program_json(Plan& plan, int root, std::string* json, std::string* why
 // generic grouped aggregation over already materialised columns: builds a LOAD-only
 // program and reuses the fused table kernels.
 void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, bool maintain_order,
-                     std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc) {
+                     std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc, const std::vector<int>* ddof) {
   PLX_REQUIRE(!keys.empty(), PLX_ERR_INVALID, "group_by needs at least one key");
   PLX_REQUIRE(values.size() == aggs.size(), PLX_ERR_INVALID, "group_by: values/aggs length mismatch");
+  PLX_REQUIRE(!ddof || ddof->size() == aggs.size(), PLX_ERR_INVALID, "group_by: ddof/aggs length mismatch");
+  for (size_t i = 0; i < aggs.size(); i++) {
+    if (aggs[i] != PLX_AGG_VAR && aggs[i] != PLX_AGG_STD) continue;
+    PLX_REQUIRE(!ddof || ((*ddof)[i] >= 0 && (*ddof)[i] <= 255), PLX_ERR_INVALID, "group_by: ddof must be 0..255");
+    PLX_REQUIRE(values[i], PLX_ERR_INVALID, "group_by: var / std need a value column");
+    if (!(dtype_is_int(values[i]->dtype) || dtype_is_float(values[i]->dtype))) fail(PLX_ERR_UNSUPPORTED, std::string("group_by: var / std of a ") + dtype_name(values[i]->dtype) + " column: numeric columns only");
+  }
   // synthesise a plan: frame of k0..kn, v0..vm; GroupBy over a scan
   auto f = std::make_shared<Frame>();
   f->height = keys[0]->len;
@@ -3288,6 +3364,7 @@ void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<Colum
       f->names.push_back("__v" + std::to_string(i)); f->cols.push_back(values[i]);
       AE c; c.kind = PLX_AE_COLUMN; c.name = f->names.back(); p.ae.push_back(c);
       a.kind = PLX_AE_AGG; a.op = aggs[i]; a.lhs = (int)p.ae.size() - 1;
+      if (aggs[i] == PLX_AGG_VAR || aggs[i] == PLX_AGG_STD) a.lit.u = ddof ? (uint64_t)(*ddof)[i] : 1;
     }
     p.ae.push_back(a);
     AE al; al.kind = PLX_AE_ALIAS; al.lhs = (int)p.ae.size() - 1; al.name = "__a" + std::to_string(i); p.ae.push_back(al);
@@ -3304,7 +3381,7 @@ void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<Colum
     for (auto& kc : k2) if (kc->dtype == PLX_F32) { kc = ops::cast(kc, PLX_F64); changed = true; }
     if (!changed) fail(PLX_ERR_UNSUPPORTED, "group_by: " + why);
     std::vector<ColumnPtr> ok, oa;
-    groupby_columns(k2, v2, aggs, maintain_order, ok, oa, desc);
+    groupby_columns(k2, v2, aggs, maintain_order, ok, oa, desc, ddof);
     for (size_t i = 0; i < keys.size(); i++) out_keys.push_back(keys[i]->dtype == PLX_F32 ? ops::cast(ok[i], PLX_F32) : ok[i]);
     for (size_t i = 0; i < values.size(); i++) {
       bool was_f32 = values[i] && values[i]->dtype == PLX_F32;

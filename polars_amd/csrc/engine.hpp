@@ -59,9 +59,10 @@ FramePtr execute(Plan& plan, int root);
 int infer_dtype(const Plan& plan, int e, const Frame& schema);
 std::string output_name(const Plan& plan, int e);
 
-// generic group-by used by plx_groupby_agg and the GroupBy executor (keys / values already columns)
+// generic group-by used by plx_groupby_agg and the GroupBy executor (keys / values already columns).  ddof: one entry per aggregate, read for PLX_AGG_VAR /
+// PLX_AGG_STD (null: 1 everywhere)
 void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, bool maintain_order,
-                     std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc);
+                     std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc, const std::vector<int>* ddof = nullptr);
 
 // compile-only entry used by tests: lowers `Filter*(pred) -> Select/GroupBy` rooted at
 // `root` and reports the fused shape (and whether an AOT specialisation matches)

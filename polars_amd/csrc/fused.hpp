@@ -211,10 +211,15 @@ enum FinalKind : uint8_t {
   FIN_MEAN,        // out f64 (or f32) = f64(cell a) / count(cell b); null when count == 0
   FIN_MINMAX_I,    // out (width by dtype) = cell a; null when count(cell b) == 0
   FIN_MINMAX_F,    // out f64 = cell a; null when count(b) == 0; NaN when ordered count(c) == 0
-  FIN_NARROW       // out (1/2 B) = low bits of cell a
+  FIN_NARROW,      // out (1/2 B) = low bits of cell a
+  // var / std from sums about a pivot p (variance.hpp): cell a = sum (x - p), cell c = sum (x - p)^2, cell b = the rows counted; out f64 (or f32) =
+  // max(c - a^2 / n, 0) / (n - ddof), its square root for FIN_STD; null when n <= ddof.  (The f32 output is there for a caller that sets it: the expression compiler never
+  // does today -- it refuses Float32 inputs -- so Float32 results are cast from the f64 column by groupby_columns or come from the per-node kernel.)
+  FIN_VAR, FIN_STD
 };
 struct FinalSpec {
   uint8_t kind, a, b, c, out_dtype;
+  uint8_t ddof;    // FIN_VAR / FIN_STD only
 };
 // ---- key decoding (packed group key -> key column) ---------------------------------
 struct KeyDecode {

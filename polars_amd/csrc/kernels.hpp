@@ -6,6 +6,7 @@
 #include "kconfig.hpp"
 
 namespace plx {
+namespace variance { struct Moments; }      // variance.hpp
 namespace k {
 
 // launch geometry helpers -------------------------------------------------------
@@ -108,6 +109,8 @@ struct ReduceResult {
 };
 // one pass computing every whole-column aggregate; synchronises to return the result
 ReduceResult reduce_all(int dtype, const void* values, const uint64_t* validity, int64_t n);
+// n, mean and centred sum of squares of the valid rows (var_kernel: Chan merges, no atomics; blocks until the result is on the host).  The ten numeric dtypes of reduce_all
+variance::Moments reduce_var(int dtype, const void* values, const uint64_t* validity, int64_t n);
 
 // ---- filter / gather (kernels_filter.hip) --------------------------------------
 struct FilterPlan {

@@ -35,6 +35,7 @@
 #include "fused_sinks.hpp"
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
+#include "variance.hpp"
 #include "scan.hpp"
 #include "jit.hpp"
 #include <atomic>
@@ -827,6 +828,12 @@ __device__ __forceinline__ bool finalize_one(const unsigned long long* cell, con
         case 4: reinterpret_cast<uint32_t*>(out)[g] = (uint32_t)v; break;
         default: reinterpret_cast<uint64_t*>(out)[g] = v; break;
       }
+    } break;
+    case FIN_VAR: case FIN_STD: {
+      // cells: a = sum of d, c = sum of d * d (d = x - pivot), b = the rows counted (variance.hpp)
+      const double n = (double)cell[sp.b];
+      const double v = variance::finalize(n, variance::from_shifted(n, as_f(cell[sp.a]), as_f(cell[sp.c])), (int)sp.ddof, sp.kind == FIN_STD, &valid);
+      if (sp.out_dtype == PLX_F32) reinterpret_cast<float*>(out)[g] = (float)v; else reinterpret_cast<double*>(out)[g] = v;
     } break;
     default: {  // FIN_MINMAX_F
       valid = cell[sp.b] != 0;

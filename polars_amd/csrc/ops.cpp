@@ -1,6 +1,7 @@
 // ops.cpp -- column-level operators: dtype checks, validity combination and output
 // allocation around the raw gfx950 kernels.
 #include "ops.hpp"
+#include "variance.hpp"
 
 #include <cmath>
 
@@ -316,6 +317,18 @@ ScalarValue reduce(int op, const ColumnPtr& c) {
     }
     default: fail(PLX_ERR_INVALID, "reduce: bad aggregation");
   }
+}
+
+ScalarValue reduce_var(const ColumnPtr& c, int ddof, bool want_std) {
+  PLX_REQUIRE(ddof >= 0 && ddof <= 255, PLX_ERR_INVALID, "var / std: ddof must be 0..255");
+  if (!(dtype_is_int(c->dtype) || dtype_is_float(c->dtype))) fail(PLX_ERR_UNSUPPORTED, std::string("var / std of a ") + dtype_name(c->dtype) + " column: numeric columns only");
+  ScalarValue r; r.v.u = 0; r.dtype = c->dtype == PLX_F32 ? PLX_F32 : PLX_F64;
+  const variance::Moments m = k::reduce_var(c->dtype, c->data(), c->valid_words(), c->len);
+  bool valid = false;
+  const double v = variance::finalize(m.n, m.m2, ddof, want_std, &valid);
+  r.valid = valid;
+  if (valid) { if (r.dtype == PLX_F32) r.v.f32 = (float)v; else r.v.f64 = v; }
+  return r;
 }
 
 ColumnPtr full_column(int dtype, plx_scalar v, bool valid, int64_t len) {

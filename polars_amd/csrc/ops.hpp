@@ -29,6 +29,8 @@ std::vector<ColumnPtr> gather_columns(const std::vector<ColumnPtr>& cols, const 
 // whole-column aggregate -> scalar (aggregate/mod.rs)
 struct ScalarValue { plx_scalar v; int dtype; bool valid; };
 ScalarValue reduce(int agg_op, const ColumnPtr& c);
+// var (want_std: its square root) of the valid rows with `ddof` delta degrees of freedom: Float64 (Float32 for a Float32 column), null when valid rows <= ddof
+ScalarValue reduce_var(const ColumnPtr& c, int ddof, bool want_std);
 ColumnPtr scalar_column(const ScalarValue& s);                 // length-1 column
 ColumnPtr full_column(int dtype, plx_scalar v, bool valid, int64_t len);  // broadcast literal
 ColumnPtr fill_null(const ColumnPtr& c, plx_scalar v);                     // valid ? value : literal (same dtype)

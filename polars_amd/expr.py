@@ -96,6 +96,15 @@ class Expr:
     def count(self): return Expr("agg", F.AGG_COUNT, self)
     def len(self): return Expr("agg", F.AGG_LEN, self)
 
+    def var(self, ddof: int = 1) -> "Expr":
+        """Variance of the non-null values with `ddof` delta degrees of freedom (py-polars expr.var): Float64 (Float32 stays Float32), null when at most `ddof`
+        values are left.  The node keeps ddof in `value`."""
+        return Expr("agg", F.AGG_VAR, self, value=check_ddof(ddof, "var"))
+
+    def std(self, ddof: int = 1) -> "Expr":
+        """Standard deviation: the square root of var(ddof)."""
+        return Expr("agg", F.AGG_STD, self, value=check_ddof(ddof, "std"))
+
     # -- misc -----------------------------------------------------------------------------
     @property
     def str(self) -> "ExprStringNameSpace":
@@ -114,6 +123,7 @@ class Expr:
         if self.kind == "col": return f"col({self.name!r})"
         if self.kind == "lit": return f"lit({self.value!r})"
         if self.kind == "binary": return f"({self.lhs!r} <{self.op}> {self.rhs!r})"
+        if self.kind == "agg" and self.op in (F.AGG_VAR, F.AGG_STD): return f"{self.lhs!r}.{'var' if self.op == F.AGG_VAR else 'std'}(ddof={self.value})"
         if self.kind == "agg": return f"{self.lhs!r}.agg{self.op}()"
         if self.kind == "alias": return f"{self.lhs!r}.alias({self.name!r})"
         if self.kind == "cast": return f"{self.lhs!r}.cast({self.dtype})"
@@ -128,6 +138,13 @@ class Expr:
 
     def __bool__(self):
         raise TypeError("the truth value of an Expr is ambiguous; use & / | / ~")
+
+
+def check_ddof(ddof: Any, what: str) -> int:
+    """ddof of var / std: an integer 0..255 (it travels in one byte of the finalisation spec); anything else is a TypeError."""
+    if isinstance(ddof, (bool, np.bool_)) or not isinstance(ddof, (int, np.integer)) or not 0 <= int(ddof) <= 255:
+        raise TypeError(f"{what}(ddof=...) takes an integer 0..255, got {ddof!r}")
+    return int(ddof)
 
 
 STR_MATCH_NAMES = {F.STR_STARTS_WITH: "starts_with", F.STR_ENDS_WITH: "ends_with", F.STR_CONTAINS: "contains"}
@@ -298,6 +315,14 @@ def max(name: str) -> Expr:  # noqa: A001
 
 def count(name: str) -> Expr:
     return col(name).count()
+
+
+def var(name: str, ddof: int = 1) -> Expr:
+    return col(name).var(ddof)
+
+
+def std(name: str, ddof: int = 1) -> Expr:
+    return col(name).std(ddof)
 
 
 _EPOCH = _dt.date(1970, 1, 1)

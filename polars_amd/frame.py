@@ -396,6 +396,25 @@ class Series:
     def count(self): return self._reduce(F.AGG_COUNT)
     def len(self): return len(self)
 
+    def _reduce_var(self, ddof: int, want_std: bool, what: str):
+        from .expr import check_ddof
+        ddof = check_ddof(ddof, what)
+        if not self.dtype.is_numeric():
+            raise TypeError(f"{what}() needs a numeric column, got {self.dtype}")
+        v, dt, ok = F.Scalar(), C.c_int32(), C.c_int32()
+        F.check(F.lib().plx_reduce_var(self._h, ddof, int(want_std), C.byref(v), C.byref(dt), C.byref(ok)))
+        if not ok.value:
+            return None
+        return float(np.float32(v.f32)) if dt.value == F.F32 else v.f64
+
+    def var(self, ddof: int = 1):
+        """Variance of the non-null values (Series.var): None when at most `ddof` values are left."""
+        return self._reduce_var(ddof, False, "var")
+
+    def std(self, ddof: int = 1):
+        """Standard deviation of the non-null values (Series.std)."""
+        return self._reduce_var(ddof, True, "std")
+
     @property
     def str(self) -> "SeriesStringNameSpace":
         """String predicates (starts_with / ends_with / contains of a literal) on a dictionary column or on a column of raw views."""

@@ -191,6 +191,12 @@ class Lowering:
                 out = T.Float32 if dt == T.Float32 else T.Float64
             elif e.op in (F.AGG_COUNT, F.AGG_LEN):
                 out = T.UInt32
+            elif e.op in (F.AGG_VAR, F.AGG_STD):
+                what = "var" if e.op == F.AGG_VAR else "std"
+                if not (isinstance(dt, T.DataType) and dt.is_numeric()):      # Boolean, Date / Datetime, Categorical
+                    raise TypeError(f"{what}() needs a numeric expression, got {dt}")
+                # ddof rides in the literal slot of the AGG node (plx_aexpr.lit.u), as a date part's unit does
+                return self._push(kind=F.AE_AGG, op=e.op, lhs=idx, lit=int(e.value)), (T.Float32 if dt == T.Float32 else T.Float64)
             else:
                 out = dt
             return self._push(kind=F.AE_AGG, op=e.op, lhs=idx), out
@@ -488,8 +494,8 @@ class Lowering:
                     a.lit.u = int(d["lit"]) & 0xFFFFFFFFFFFFFFFF
                 else:
                     a.lit.i = int(d["lit"])
-            if d["kind"] == F.AE_TEMPORAL:
-                a.lit.u = int(d["lit"])            # the operand's time unit rides in the literal slot, like a lookup bitmap's handle
+            if d["kind"] == F.AE_TEMPORAL or (d["kind"] == F.AE_AGG and d["op"] in (F.AGG_VAR, F.AGG_STD)):
+                a.lit.u = int(d["lit"])            # the operand's time unit / the ddof of var and std rides in the literal slot, like a lookup bitmap's handle
             if d["kind"] == F.AE_BITMAP_LOOKUP:
                 a.lit.u = d["lut"]._h              # the lookup bitmap's column handle rides in the literal slot (plx_aexpr.lit)
                 keep.append(d["lut"])

@@ -152,6 +152,12 @@ class Translator:
             return self.expr(x.expr).cast(dt)
         if kind == "Agg":
             name = str(x.name)
+            if name in ("std", "var") and len(x.arguments) == 1:      # visitor/expr_nodes.rs: the Agg node's `options` is ddof
+                try:
+                    ddof = E.check_ddof(x.options, name)
+                except TypeError as e:
+                    raise NotSupported(str(e))
+                return E.Expr("agg", F.AGG_STD if name == "std" else F.AGG_VAR, self.expr(x.arguments[0]), value=ddof)
             if name not in _AGGS or len(x.arguments) != 1:
                 raise NotSupported(f"aggregation {name}")
             if name in ("min", "max") and x.options:

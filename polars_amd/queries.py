@@ -36,6 +36,11 @@ def cfg5(lf):
     return lf.group_by("k").agg(E.col("v").sum().alias("v_sum"), E.col("v").mean().alias("v_mean"))
 
 
+def h2o_sd(lf):
+    """group_by(id4, id5).agg(v3.std(), v3.mean()) -- the H2O group-by benchmark's `sd(v3) by id4, id5` (beside the mean: both share the count cell)"""
+    return lf.group_by("id4", "id5").agg(E.col("v3").std().alias("v3_sd"), E.col("v3").mean().alias("v3_mean"))
+
+
 def q1(lineitem, cutoff=Q1_CUTOFF):
     """TPC-H Q1; the final sort by (flag, status) happens on the host."""
     c = E.col
