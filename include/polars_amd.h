@@ -222,7 +222,13 @@ int plx_memory_reserve(uint64_t bytes);
 int plx_column_from_host(plx_dtype dtype, const void* values, const uint8_t* validity,
                          int64_t bit_offset, int64_t len, plx_column* out);
 /* Wrap device buffers owned by the caller (e.g. a torch tensor): no copy; the
- * caller keeps them alive until plx_column_free. validity may be NULL. */
+ * caller keeps them alive until plx_column_free. validity may be NULL.
+ * Alignment: dev_values is a multiple of the element width (8 for PLX_BOOL, whose
+ * values are a bitmap); it need NOT be a multiple of 16 -- a window that starts
+ * anywhere inside a larger buffer is fine.  dev_validity is a multiple of 8 and
+ * covers whole 64-bit words, (len + 63) / 64 of them, with bit 0 of word 0 the
+ * first row: every kernel loads validity (and Boolean values) as uint64_t.
+ * A pointer below that returns PLX_ERR_INVALID before anything is launched. */
 int plx_column_from_device(plx_dtype dtype, void* dev_values, void* dev_validity, int64_t len,
                            plx_column* out);
 /* Planning-only column: dtype / length / nullability (/ integer range statistics) but NO

@@ -89,6 +89,12 @@ int plx_column_from_device(plx_dtype dtype, void* dev_values, void* dev_validity
   PLX_TRY
   device();
   PLX_REQUIRE(out && (dev_values || len == 0), PLX_ERR_INVALID, "null pointer");
+  PLX_REQUIRE(dtype >= PLX_BOOL && dtype <= PLX_F64 && len >= 0, PLX_ERR_INVALID, "column_from_device: bad dtype or length");
+  // every kernel loads values as their element type and bitmaps as uint64_t words
+  const uintptr_t value_align = dtype == PLX_BOOL ? 8 : (uintptr_t)dtype_width(dtype);
+  PLX_REQUIRE(((uintptr_t)dev_values % value_align) == 0, PLX_ERR_INVALID,
+              std::string("column_from_device: the values pointer of a ") + dtype_name(dtype) + " column must be a multiple of " + std::to_string(value_align));
+  PLX_REQUIRE(((uintptr_t)dev_validity % 8) == 0, PLX_ERR_INVALID, "column_from_device: the validity pointer must be a multiple of 8 (validity is read as 64-bit words)");
   auto c = std::make_shared<Column>();
   c->dtype = dtype; c->len = len;
   c->values = dev_borrow(dev_values, values_bytes(dtype, len));
