@@ -322,6 +322,17 @@ def build(name):
     if name == "v1_packed_ids":
         return {"n": n, "keys": ["k"], "aggs": [("v_sum", "sum", "v"), ("v_mean", "mean", "v")], "dictionary": ["k"],
                 "cols": {"k": (rng.integers(0, 400_000, n).astype(np.uint32), None), "v": (rng.uniform(-100, 100, n), None)}}
+    if name == "v1_edges":
+        # a sparse single key as v1_single_key's; the value columns carry the planted edge groups of tests/agg_edges.py (Int64 kinds in v, Float64 kinds in x)
+        try:
+            from tests import agg_edges
+        except ImportError:
+            import agg_edges
+        g = rng.integers(0, 300_000, n)
+        p = agg_edges.planted(g, None, 300_000)
+        kvalid = (rng.random(n) > 0.001) | np.isin(g, np.array(sorted(p["chosen"])))
+        return {"n": n, "keys": ["k"], "aggs": [(op, op, "v") for op in ("sum", "mean", "min", "max", "count")] + [("len", "len", None)],
+                "cols": {"k": (sparse(g), kvalid), "v": p["v"], "x": p["x"]}, "ids": g, "chosen": p["chosen"]}
     if name == "v1_wide_keys":
         g = rng.integers(0, 100_000, n)
         v, _ = _values(rng, n)
