@@ -131,8 +131,24 @@ typedef enum plx_agg_op {
    * takes one per aggregate; a whole column goes through plx_reduce_var (plx_reduce refuses the two kinds).  Numeric operands only: a Boolean operand is
    * PLX_ERR_UNSUPPORTED.  Fused scans accumulate sums about a pivot: the accuracy contract is DESIGN.md 4.14. */
   PLX_AGG_VAR = 7,
-  PLX_AGG_STD = 8
+  PLX_AGG_STD = 8,
+  /* An order statistic of the valid rows (median = quantile 0.5, linear): f64 (f32 stays f32), null when no row is valid.  Values rank in the sort's total order
+   * (NaN greatest, -0 == +0).  A PLX_AE_AGG node of this kind carries q (a real number in [0, 1]) in lit.f64 and the plx_quantile_interpolation in its dtype slot;
+   * plx_groupby_agg_params takes one pair per aggregate (plx_groupby_agg / plx_groupby_agg_ddof refuse the kind); a whole column goes through plx_reduce_quantile
+   * (plx_reduce refuses the kind).  Integer and float operands only: a Boolean operand is PLX_ERR_UNSUPPORTED.  It is no sum of cells: fused scans decline it, a
+   * whole column runs a radix select and a group-by sorted segments. */
+  PLX_AGG_QUANTILE = 9
 } plx_agg_op;
+
+/* With pos = (n - 1) * q over the n valid values in order and a, b the values at ranks floor(pos), ceil(pos): NEAREST = the value at rank floor(pos + 0.5),
+ * LOWER = a, HIGHER = b, MIDPOINT = a == b ? a : (a + b) / 2, LINEAR = a == b ? a : (pos - floor(pos)) * (b - a) + a. */
+typedef enum plx_quantile_interpolation {
+  PLX_QUANTILE_NEAREST = 0,
+  PLX_QUANTILE_LOWER = 1,
+  PLX_QUANTILE_HIGHER = 2,
+  PLX_QUANTILE_MIDPOINT = 3,
+  PLX_QUANTILE_LINEAR = 4
+} plx_quantile_interpolation;
 
 /* Null keys match nothing (nulls_equal is not on this path).  PLX_JOIN_FULL: every pair of the inner join, one row per unmatched left row (null right index) and one
  * row per unmatched right row (null left index); null-key rows of either side count as unmatched.  PLX_JOIN_RIGHT: the left join with the sides exchanged -- every
@@ -315,6 +331,11 @@ int plx_reduce(plx_agg_op op, plx_column col, plx_scalar* out_value, plx_dtype* 
  * *out_valid = 0 when the column has at most ddof valid rows.  One streaming pass of Chan merges, no atomics: the same column gives the same bits every time, and
  * a common offset of any size costs no digits.  Numeric columns only (PLX_ERR_UNSUPPORTED names the dtype otherwise). */
 int plx_reduce_var(plx_column col, int32_t ddof, int32_t want_std, plx_scalar* out_value, plx_dtype* out_dtype, int32_t* out_valid);
+/* Whole-column quantile q in [0, 1] (NaN or outside: PLX_ERR_INVALID) with a plx_quantile_interpolation; the median is (0.5, PLX_QUANTILE_LINEAR).  *out_dtype is
+ * f64 (f32 for an f32 column); *out_valid = 0 when the column has no valid row.  A radix select over the sort's value codes: the column is never sorted, and the
+ * same column gives the same bits every time.  plx_last_plan_description() names the digit rounds.  Integer and float columns only (PLX_ERR_UNSUPPORTED names the
+ * dtype otherwise); at most 2^32 - 2 rows. */
+int plx_reduce_quantile(plx_column col, double q, int32_t interpolation, plx_scalar* out_value, plx_dtype* out_dtype, int32_t* out_valid);
 
 /* Hash group-by with in-place aggregation.  n_keys >= 1 key columns (integer,
  * bool or float; a null key forms its own group; floats canonicalised).
@@ -329,6 +350,12 @@ int plx_groupby_agg(const plx_column* keys, int32_t n_keys, const plx_column* va
 int plx_groupby_agg_ddof(const plx_column* keys, int32_t n_keys, const plx_column* values,
                          const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order, const int32_t* ddof,
                          plx_column* out_keys, plx_column* out_aggs);
+/* The same with q[i] / interpolation[i] (plx_quantile_interpolation) for aggregate i as well: read for PLX_AGG_QUANTILE, ignored for every other kind.  A NULL array
+ * means the defaults: ddof 1, q 0.5, PLX_QUANTILE_LINEAR (the median).  Quantiles run over sorted segments, every other kind as in plx_groupby_agg; the group order
+ * is that of the same call without the quantiles. */
+int plx_groupby_agg_params(const plx_column* keys, int32_t n_keys, const plx_column* values,
+                           const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order, const int32_t* ddof,
+                           const double* q, const int32_t* interpolation, plx_column* out_keys, plx_column* out_aggs);
 
 /* Equi-join on one key column pair -> row-index pairs (PLX_U32). For LEFT joins the
  * right index column carries nulls for unmatched left rows. Null keys never match.
@@ -410,6 +437,7 @@ typedef struct plx_aexpr {
   int32_t dtype; /* literal dtype / cast target (plx_dtype) */
   int32_t is_null; /* literal is NULL */
   plx_scalar lit;   /* PLX_AE_LITERAL: the value; PLX_AE_BITMAP_LOOKUP: lit.u = the lookup bitmap's plx_column handle; PLX_AE_TEMPORAL: lit.u = the plx_time_unit;
+                     * PLX_AE_AGG of PLX_AGG_VAR / PLX_AGG_STD: lit.u = ddof; of PLX_AGG_QUANTILE: lit.f64 = q (and dtype = the plx_quantile_interpolation);
                      * read for those kinds only */
   const char* name; /* column name / alias */
   int32_t cond;     /* PLX_AE_TERNARY: arena index of the predicate; read for that kind only (appended last: arenas of earlier callers never carry the kind) */
@@ -781,7 +809,7 @@ int plx_profile_clear(void);
  *   _polars_plugin_field_<name>(fields, n, out, kwargs, kwargs_len)   output field (minor 1 signature, plugin.rs:186-207)
  * Functions: plx_cmp / plx_arith (kwargs {"op": "gt" | ... | "add" | ...}) and one symbol per operator for callers
  * without kwargs: plx_eq ne lt le gt ge, plx_add sub mul truediv floordiv mod, plx_filter(values, mask),
- * plx_when_then_otherwise(mask, then, otherwise), plx_dt_part(values; kwargs part, unit), plx_sum mean min max (length-1 result), plx_var / plx_std (length-1 result; kwargs ddof).  Python side: polars.plugins.register_plugin_function(
+ * plx_when_then_otherwise(mask, then, otherwise), plx_dt_part(values; kwargs part, unit), plx_sum mean min max (length-1 result), plx_var / plx_std (length-1 result; kwargs ddof), plx_median (length-1 result).  Python side: polars.plugins.register_plugin_function(
  *     plugin_path=".../libpolars_amd.so", function_name="plx_gt", args=[pl.col("a"), pl.lit(3)]).           */
 typedef struct plx_caller_context { uint64_t bitflags; } plx_caller_context;
 uint32_t _polars_plugin_get_version(void);
@@ -802,6 +830,9 @@ void _polars_plugin_plx_var(const plx_series_export* inputs, size_t n_inputs, co
 void _polars_plugin_field_plx_var(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
 void _polars_plugin_plx_std(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
 void _polars_plugin_field_plx_std(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
+/* plx_median (values): plx_reduce_quantile(0.5, PLX_QUANTILE_LINEAR); no kwargs; a length-1 result; the field is Float64, Float32 for a Float32 input */
+void _polars_plugin_plx_median(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
+void _polars_plugin_field_plx_median(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,9 @@ EQ, NE, LT, LE, GT, GE = range(6)
 ADD, SUB, MUL, TRUE_DIV, FLOOR_DIV, MOD = range(6)
 AND, OR, XOR = range(3)
 AGG_SUM, AGG_MEAN, AGG_MIN, AGG_MAX, AGG_COUNT, AGG_LEN, AGG_FIRST, AGG_VAR, AGG_STD = range(9)      # VAR / STD: ddof rides in plx_aexpr.lit.u
+AGG_QUANTILE = 9                                                          # q rides in plx_aexpr.lit.f64, the interpolation in plx_aexpr.dtype
+QUANTILE_NEAREST, QUANTILE_LOWER, QUANTILE_HIGHER, QUANTILE_MIDPOINT, QUANTILE_LINEAR = range(5)      # plx_quantile_interpolation
+QUANTILE_INTERPOLATIONS = {"nearest": QUANTILE_NEAREST, "lower": QUANTILE_LOWER, "higher": QUANTILE_HIGHER, "midpoint": QUANTILE_MIDPOINT, "linear": QUANTILE_LINEAR}
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI, JOIN_FULL, JOIN_RIGHT = range(6)
 JOIN_COALESCE_DEFAULT, JOIN_COALESCE, JOIN_KEEP_BOTH = range(3)          # plx_ir.coalesce
 JOIN_ORDER_NONE, JOIN_ORDER_LEFT, JOIN_ORDER_RIGHT, JOIN_ORDER_LEFT_RIGHT, JOIN_ORDER_RIGHT_LEFT = range(5)   # plx_join_order
@@ -201,6 +204,8 @@ SIGNATURES = {
     "plx_reduce_var": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.POINTER(Scalar), _i32p, _i32p]),
     "plx_groupby_agg": (C.c_int, [_u64p, C.c_int32, _u64p, _i32p, C.c_int32, C.c_int32, _u64p, _u64p]),
     "plx_groupby_agg_ddof": (C.c_int, [_u64p, C.c_int32, _u64p, _i32p, C.c_int32, C.c_int32, _i32p, _u64p, _u64p]),
+    "plx_reduce_quantile": (C.c_int, [C.c_uint64, C.c_double, C.c_int32, C.POINTER(Scalar), _i32p, _i32p]),
+    "plx_groupby_agg_params": (C.c_int, [_u64p, C.c_int32, _u64p, _i32p, C.c_int32, C.c_int32, _i32p, C.POINTER(C.c_double), _i32p, _u64p, _u64p]),
     "plx_join_indices": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _u64p, _u64p]),
     "plx_datagen_lineitem_q1": (C.c_int, [C.c_int64, C.c_uint64, _u64p]),
     "plx_datagen_lineitem_q1_host": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

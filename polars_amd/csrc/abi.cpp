@@ -352,6 +352,7 @@ int plx_gather(plx_column col, plx_column idx, plx_column* out) { PLX_TRY *out =
 int plx_reduce(plx_agg_op op, plx_column col, plx_scalar* out_value, plx_dtype* out_dtype, int32_t* out_valid) {
   PLX_TRY
   PLX_REQUIRE(op != PLX_AGG_VAR && op != PLX_AGG_STD, PLX_ERR_INVALID, "plx_reduce: var / std take ddof: call plx_reduce_var");
+  PLX_REQUIRE(op != PLX_AGG_QUANTILE, PLX_ERR_INVALID, "plx_reduce: a quantile takes q and an interpolation: call plx_reduce_quantile");
   ops::ScalarValue r = ops::reduce(op, get_column(col));
   if (out_value) *out_value = r.v;
   if (out_dtype) *out_dtype = (plx_dtype)r.dtype;
@@ -366,6 +367,16 @@ int plx_reduce_var(plx_column col, int32_t ddof, int32_t want_std, plx_scalar* o
   if (out_valid) *out_valid = r.valid ? 1 : 0;
   PLX_CATCH
 }
+int plx_reduce_quantile(plx_column col, double q, int32_t interpolation, plx_scalar* out_value, plx_dtype* out_dtype, int32_t* out_valid) {
+  PLX_TRY
+  std::string d;
+  ops::ScalarValue r = ops::reduce_quantile(get_column(col), q, interpolation, &d);
+  t_plan_desc = d;
+  if (out_value) *out_value = r.v;
+  if (out_dtype) *out_dtype = (plx_dtype)r.dtype;
+  if (out_valid) *out_valid = r.valid ? 1 : 0;
+  PLX_CATCH
+}
 
 int plx_groupby_agg(const plx_column* keys, int32_t n_keys, const plx_column* values, const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order,
                     plx_column* out_keys, plx_column* out_aggs) {
@@ -373,14 +384,27 @@ int plx_groupby_agg(const plx_column* keys, int32_t n_keys, const plx_column* va
 }
 int plx_groupby_agg_ddof(const plx_column* keys, int32_t n_keys, const plx_column* values, const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order,
                          const int32_t* ddof, plx_column* out_keys, plx_column* out_aggs) {
+  for (int i = 0; aggs && i < n_aggs; i++)
+    if (aggs[i] == PLX_AGG_QUANTILE) { plx::set_last_error("plx_groupby_agg / plx_groupby_agg_ddof: a quantile takes q and an interpolation: call plx_groupby_agg_params"); return PLX_ERR_INVALID; }
+  return plx_groupby_agg_params(keys, n_keys, values, aggs, n_aggs, maintain_order, ddof, nullptr, nullptr, out_keys, out_aggs);
+}
+int plx_groupby_agg_params(const plx_column* keys, int32_t n_keys, const plx_column* values, const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order,
+                           const int32_t* ddof, const double* q, const int32_t* interpolation, plx_column* out_keys, plx_column* out_aggs) {
   PLX_TRY
   PLX_REQUIRE(keys && n_keys >= 1 && (n_aggs == 0 || (values && aggs && out_aggs)) && out_keys, PLX_ERR_INVALID, "bad arguments");
   std::vector<ColumnPtr> k, v, ok, oa;
-  std::vector<int> a, dd;
+  std::vector<int> a;
+  std::vector<engine::AggParams> ap;
   for (int i = 0; i < n_keys; i++) k.push_back(get_column(keys[i]));
-  for (int i = 0; i < n_aggs; i++) { a.push_back(aggs[i]); dd.push_back(ddof ? ddof[i] : 1); v.push_back((aggs[i] == PLX_AGG_LEN || values[i] == 0) ? nullptr : get_column(values[i])); }
+  for (int i = 0; i < n_aggs; i++) {
+    engine::AggParams p;
+    if (ddof) p.ddof = ddof[i];
+    if (q) p.q = q[i];
+    if (interpolation) p.interpolation = interpolation[i];
+    a.push_back(aggs[i]); ap.push_back(p); v.push_back((aggs[i] == PLX_AGG_LEN || values[i] == 0) ? nullptr : get_column(values[i]));
+  }
   std::string d;
-  engine::groupby_columns(k, v, a, maintain_order != 0, ok, oa, &d, &dd);
+  engine::groupby_columns(k, v, a, maintain_order != 0, ok, oa, &d, &ap);
   t_plan_desc = d;
   for (int i = 0; i < n_keys; i++) out_keys[i] = register_column(ok[i]);
   for (int i = 0; i < n_aggs; i++) out_aggs[i] = register_column(oa[i]);
@@ -770,6 +794,12 @@ PLX_PLUGIN_REDUCE(sum, PLX_AGG_SUM, FIELD_SUM) PLX_PLUGIN_REDUCE(mean, PLX_AGG_M
   }                                                                                                                                               \
   void _polars_plugin_field_plx_##NAME(PLX_FIELD_SIG) { (void)kwargs; (void)kwargs_len; plugin_field(fields, n_fields, out, FIELD_MEAN, 0); }
 PLX_PLUGIN_VAR(var, false) PLX_PLUGIN_VAR(std, true)
+// the median of a series: no kwargs; a length-1 result under the input's name, Float64 (Float32 for a Float32 input)
+void _polars_plugin_plx_median(PLX_PLUGIN_SIG) {
+  (void)kwargs; (void)kwargs_len;
+  plugin_call(inputs, n_inputs, out, ctx, 1, [&](std::vector<PluginInput>& in) { return ops::scalar_column(ops::reduce_quantile(in[0].col, 0.5, PLX_QUANTILE_LINEAR, nullptr)); });
+}
+void _polars_plugin_field_plx_median(PLX_FIELD_SIG) { (void)kwargs; (void)kwargs_len; plugin_field(fields, n_fields, out, FIELD_MEAN, 0); }
 void _polars_plugin_plx_filter(PLX_PLUGIN_SIG) {
   (void)kwargs; (void)kwargs_len;
   plugin_call(inputs, n_inputs, out, ctx, 2, [&](std::vector<PluginInput>& in) {

@@ -19,6 +19,7 @@
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
 #include "ops.hpp"
+#include "quantile.hpp"
 #include "sort.hpp"
 #include "temporal.hpp"
 #include "variance.hpp"
@@ -60,6 +61,9 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
     }
     if (e.kind == PLX_AE_AGG && (e.op == PLX_AGG_VAR || e.op == PLX_AGG_STD))
       PLX_REQUIRE(e.lhs >= 0 && e.lit.u <= 255, PLX_ERR_INVALID, "var / std: the node carries ddof 0..255 in lit.u, got " + std::to_string((long long)e.lit.i));
+    if (e.kind == PLX_AE_AGG && e.op == PLX_AGG_QUANTILE)
+      PLX_REQUIRE(e.lhs >= 0 && quantile::q_ok(e.lit.f64) && quantile::interpolation_ok(e.dtype), PLX_ERR_INVALID,
+                  "quantile: the node carries q in [0, 1] in lit.f64 and a plx_quantile_interpolation 0..4 in its dtype slot, got q=" + std::to_string(e.lit.f64) + ", interpolation=" + std::to_string(e.dtype));
     PLX_REQUIRE(e.lhs < i && e.rhs < i && e.cond < i, PLX_ERR_INVALID, "AExpr arena must be topologically ordered (children before parents)");
     p.ae.push_back(std::move(e));
   }
@@ -153,6 +157,9 @@ int infer_dtype(const Plan& plan, int e, const Frame& schema) {
         case PLX_AGG_VAR: case PLX_AGG_STD:
           PLX_REQUIRE(dtype_is_int(in) || dtype_is_float(in), PLX_ERR_UNSUPPORTED, std::string(x.op == PLX_AGG_STD ? "std" : "var") + " of a " + dtype_name(in) + " expression: numeric operands only");
           return in == PLX_F32 ? PLX_F32 : PLX_F64;
+        case PLX_AGG_QUANTILE:
+          PLX_REQUIRE(dtype_is_int(in) || dtype_is_float(in), PLX_ERR_UNSUPPORTED, std::string("median / quantile of a ") + dtype_name(in) + " expression: integer and float operands only");
+          return in == PLX_F32 ? PLX_F32 : PLX_F64;
         case PLX_AGG_COUNT: case PLX_AGG_LEN: return PLX_U32;
         default: return in;
       }
@@ -214,6 +221,11 @@ struct Evaluated { ColumnPtr col; bool scalar; };  // scalar: length-1, broadcas
 
 using ops::scalar_of;
 
+// what the per-node reductions that have a route of their own ran (the radix select of a median): eval() appends, the executor that called it moves the text into
+// the plan description
+static thread_local std::string t_node_notes;
+static void flush_node_notes(Plan& plan) { plan.desc += t_node_notes; t_node_notes.clear(); }
+
 static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<int, ColumnPtr>* overrides) {
   check_cancel();
   if (overrides) { auto it = overrides->find(e); if (it != overrides->end()) return {it->second, false}; }
@@ -267,6 +279,12 @@ static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<i
     case PLX_AE_AGG: {
       Evaluated c = eval(plan, x.lhs, df, overrides);
       if (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD) return {ops::scalar_column(ops::reduce_var(c.col, (int)x.lit.u, x.op == PLX_AGG_STD)), true};
+      if (x.op == PLX_AGG_QUANTILE) {
+        std::string d;
+        const ops::ScalarValue v = ops::reduce_quantile(c.col, x.lit.f64, x.dtype, &d);
+        t_node_notes += d + "; ";
+        return {ops::scalar_column(v), true};
+      }
       return {ops::scalar_column(ops::reduce(x.op, c.col)), true};
     }
     case PLX_AE_BINARY: {
@@ -589,6 +607,12 @@ class Compiler {
     return p;
   }
 
+  // an order statistic is no sum of cells: a list that holds one is declined as a whole, before a var / std beside it spends its pivot pre-pass
+  static constexpr const char* kOrderStatistic = "median / quantile: an order statistic (sorted-segment route)";
+  void decline_order_statistics(const std::vector<int>& agg_nodes) const {
+    for (int a : agg_nodes) if (plan.ae.at(a).kind == PLX_AE_AGG && plan.ae[a].op == PLX_AGG_QUANTILE) throw Unsupported(kOrderStatistic);
+  }
+
   // lowers one AGG / LEN node; returns how to finalise it
   FinalSpec lower_agg(int e) {
     const AE& x = plan.ae.at(e);
@@ -596,6 +620,7 @@ class Compiler {
     if (x.kind == PLX_AE_LEN) { fs.kind = FIN_TRUNC32; fs.a = (uint8_t)add_agg(AGG_LEN, -1); fs.out_dtype = PLX_U32; return fs; }
     const int in_dt = infer_dtype(plan, x.lhs, *df);
     if (x.op == PLX_AGG_LEN) { fs.kind = FIN_TRUNC32; fs.a = (uint8_t)add_agg(AGG_LEN, -1); fs.out_dtype = PLX_U32; return fs; }
+    if (x.op == PLX_AGG_QUANTILE) throw Unsupported(kOrderStatistic);
     // Boolean inputs: sum = number of true values (UInt32, sum_output_dtype) and mean = their fraction; a boolean slot holds 0 / 1,
     // so both reuse the integer cells.  min / max of booleans would need a bit-packed finalisation: per-node path.
     if (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD) infer_dtype(plan, e, *df);      // (fails, naming the dtype, when the operand is not numeric)
@@ -1709,8 +1734,9 @@ static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& pr
   std::vector<int> agg_nodes;
   std::vector<FinalSpec> specs;
   try {
-    c.pred = and_predicates(c, preds);
     for (int e : node.exprs) collect_aggs(plan, e, agg_nodes);
+    c.decline_order_statistics(agg_nodes);
+    c.pred = and_predicates(c, preds);
     for (int a : agg_nodes) specs.push_back(c.lower_agg(a));
     c.finish();
   } catch (const Unsupported& u) { if (why) *why = u.why; return false; }
@@ -1752,10 +1778,11 @@ static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& p
   KeyPlan kp;
   int len_idx = -1, first_idx = -1;
   try {
+    for (int e : node.exprs) collect_aggs(plan, e, agg_nodes);
+    c.decline_order_statistics(agg_nodes);
     c.pred = and_predicates(c, preds);
     kp = lower_keys(c, node.keys);
     len_idx = c.add_agg(AGG_LEN, -1);
-    for (int e : node.exprs) collect_aggs(plan, e, agg_nodes);
     for (int a : agg_nodes) specs.push_back(c.lower_agg(a));
     if (node.maintain_order) first_idx = c.add_agg(AGG_FIRST_ROW, -1);
     c.finish();
@@ -2191,6 +2218,7 @@ static void compile_join_programs(const Plan& plan, const IRN& gb, JoinGroupBy& 
   cp.device_pivot = ca.device_pivot = j.device_pivot;
   j.len_idx = cp.add_agg(AGG_LEN, -1);
   for (int e : gb.exprs) collect_aggs(plan, e, j.agg_nodes);
+  cp.decline_order_statistics(j.agg_nodes);
   for (int a : j.agg_nodes) j.specs.push_back(cp.lower_agg(a));
   cp.finish();
   // the probe side's predicate + key alone, row id as payload: the program of the partitioned probe's scatter (k::partitioned_probe_hits)
@@ -2748,6 +2776,7 @@ static FramePtr exec_select(Plan& plan, const IRN& n, bool hstack, FramePtr in_g
       int at = out->find(name);
       if (at >= 0) out->cols[at] = c; else { out->names.push_back(name); out->cols.push_back(c); }
     }
+    flush_node_notes(plan);
     plan.desc += "HStack{per-node kernels}; ";
     return out;
   }
@@ -2756,6 +2785,7 @@ static FramePtr exec_select(Plan& plan, const IRN& n, bool hstack, FramePtr in_g
     out->names.push_back(output_name(plan, n.exprs[i]));
     out->cols.push_back(all_scalar ? evs[i].col : broadcast(evs[i], in->height));
   }
+  flush_node_notes(plan);
   plan.desc += "Select{per-node kernels}; ";
   return out;
 }
@@ -2763,18 +2793,28 @@ static FramePtr exec_select(Plan& plan, const IRN& n, bool hstack, FramePtr in_g
 static FramePtr exec_groupby_materialised(Plan& plan, const IRN& n, const FramePtr& in) {
   // evaluate key and aggregation-input expressions as columns, then the generic grouped aggregation
   std::vector<ColumnPtr> keys, values;
-  std::vector<int> aggs, agg_nodes, ddof;
+  std::vector<int> aggs, agg_nodes;
+  std::vector<AggParams> params;
+  std::map<int, ColumnPtr> by_expr;      // one column per source expression: the quantiles over one source share its sort
   for (int e : n.keys) keys.push_back(broadcast(eval(plan, e, *in, nullptr), in->height));
   for (int e : n.exprs) collect_aggs(plan, e, agg_nodes);
   for (int a : agg_nodes) {
     const AE& x = plan.ae[a];
-    ddof.push_back(x.kind == PLX_AE_AGG && (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD) ? (int)x.lit.u : 1);
+    AggParams ap;
+    if (x.kind == PLX_AE_AGG && (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD)) ap.ddof = (int)x.lit.u;
+    if (x.kind == PLX_AE_AGG && x.op == PLX_AGG_QUANTILE) { ap.q = x.lit.f64; ap.interpolation = x.dtype; }
+    params.push_back(ap);
     if (x.kind == PLX_AE_LEN) { aggs.push_back(PLX_AGG_LEN); values.push_back(nullptr); }
-    else { aggs.push_back(x.op); values.push_back(broadcast(eval(plan, x.lhs, *in, nullptr), in->height)); }
+    else {
+      auto it = by_expr.find(x.lhs);
+      if (it == by_expr.end()) it = by_expr.emplace(x.lhs, broadcast(eval(plan, x.lhs, *in, nullptr), in->height)).first;
+      aggs.push_back(x.op); values.push_back(it->second);
+    }
   }
+  flush_node_notes(plan);
   std::vector<ColumnPtr> okeys, oaggs;
   std::string d;
-  groupby_columns(keys, values, aggs, n.maintain_order != 0, okeys, oaggs, &d, &ddof);
+  groupby_columns(keys, values, aggs, n.maintain_order != 0, okeys, oaggs, &d, &params);
   plan.desc += "GroupBy{materialised inputs; " + d + "}; ";
   auto out = std::make_shared<Frame>();
   out->height = okeys.empty() ? 0 : okeys[0]->len;
@@ -3278,6 +3318,7 @@ static FramePtr exec_node(Plan& plan, int node_id) {
 
 FramePtr execute(Plan& plan, int root) {
   plan.desc.clear();
+  t_node_notes.clear();
   return exec_node(plan, root);
 }
 
@@ -3333,8 +3374,8 @@ bool dump_program_json(Plan& plan, int root, std::string* json, std::string* why
 
 // generic grouped aggregation over already materialised columns: builds a LOAD-only
 // program and reuses the fused table kernels.
-void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, bool maintain_order,
-                     std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc, const std::vector<int>* ddof) {
+static void groupby_cells(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, bool maintain_order,
+                          std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc, const std::vector<int>* ddof) {
   PLX_REQUIRE(!keys.empty(), PLX_ERR_INVALID, "group_by needs at least one key");
   PLX_REQUIRE(values.size() == aggs.size(), PLX_ERR_INVALID, "group_by: values/aggs length mismatch");
   PLX_REQUIRE(!ddof || ddof->size() == aggs.size(), PLX_ERR_INVALID, "group_by: ddof/aggs length mismatch");
@@ -3381,7 +3422,7 @@ void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<Colum
     for (auto& kc : k2) if (kc->dtype == PLX_F32) { kc = ops::cast(kc, PLX_F64); changed = true; }
     if (!changed) fail(PLX_ERR_UNSUPPORTED, "group_by: " + why);
     std::vector<ColumnPtr> ok, oa;
-    groupby_columns(k2, v2, aggs, maintain_order, ok, oa, desc, ddof);
+    groupby_cells(k2, v2, aggs, maintain_order, ok, oa, desc, ddof);
     for (size_t i = 0; i < keys.size(); i++) out_keys.push_back(keys[i]->dtype == PLX_F32 ? ops::cast(ok[i], PLX_F32) : ok[i]);
     for (size_t i = 0; i < values.size(); i++) {
       bool was_f32 = values[i] && values[i]->dtype == PLX_F32;
@@ -3393,6 +3434,68 @@ void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<Colum
   if (desc) *desc = p.desc;
   for (size_t i = 0; i < keys.size(); i++) out_keys.push_back(out->cols[i]);
   for (size_t i = 0; i < values.size(); i++) out_aggs.push_back(out->cols[keys.size() + i]);
+}
+
+// The aggregates that are sums of cells run through the synthesised fused plan (groupby_cells), which also owns the keys, the group order and maintain_order.  The
+// order statistics run over sorted segments, one sort per distinct source column, and are placed into the group frame by the rank of every group's key
+// (DESIGN.md 4.15).
+void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, bool maintain_order,
+                     std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc, const std::vector<AggParams>* params) {
+  PLX_REQUIRE(values.size() == aggs.size(), PLX_ERR_INVALID, "group_by: values/aggs length mismatch");
+  PLX_REQUIRE(!params || params->size() == aggs.size(), PLX_ERR_INVALID, "group_by: params/aggs length mismatch");
+  std::vector<ColumnPtr> cell_values;
+  std::vector<int> cell_aggs, cell_ddof, cell_of(aggs.size(), -1);
+  std::vector<size_t> quantiles;
+  for (size_t i = 0; i < aggs.size(); i++) {
+    const AggParams ap = params ? (*params)[i] : AggParams{};
+    if (aggs[i] == PLX_AGG_QUANTILE) {
+      PLX_REQUIRE(quantile::q_ok(ap.q), PLX_ERR_INVALID, "group_by: quantile q must be a real number in [0, 1], got " + std::to_string(ap.q));
+      PLX_REQUIRE(quantile::interpolation_ok(ap.interpolation), PLX_ERR_INVALID, "group_by: interpolation " + std::to_string(ap.interpolation) + " is no plx_quantile_interpolation (0..4)");
+      PLX_REQUIRE(values[i], PLX_ERR_INVALID, "group_by: median / quantile need a value column");
+      if (!(dtype_is_int(values[i]->dtype) || dtype_is_float(values[i]->dtype))) fail(PLX_ERR_UNSUPPORTED, std::string("group_by: median / quantile of a ") + dtype_name(values[i]->dtype) + " column: integer and float columns only");
+      quantiles.push_back(i);
+      continue;
+    }
+    cell_of[i] = (int)cell_aggs.size();
+    cell_values.push_back(values[i]); cell_aggs.push_back(aggs[i]); cell_ddof.push_back(ap.ddof);
+  }
+  if (quantiles.empty()) { groupby_cells(keys, values, aggs, maintain_order, out_keys, out_aggs, desc, &cell_ddof); return; }
+  if (cell_aggs.empty()) { cell_values.push_back(nullptr); cell_aggs.push_back(PLX_AGG_LEN); cell_ddof.push_back(1); }      // the group frame has to exist
+  std::vector<ColumnPtr> cells;
+  std::string d;
+  groupby_cells(keys, cell_values, cell_aggs, maintain_order, out_keys, cells, &d, &cell_ddof);
+  const int64_t G = out_keys[0]->len;
+  for (auto& kc : keys) PLX_REQUIRE(kc->len == keys[0]->len, PLX_ERR_SHAPE, "group_by: key length mismatch");
+  // rank of every group's key among the groups, in the order the segments come out in
+  ColumnPtr place;
+  if (G > 1) {
+    std::vector<sort::SortKey> gk;
+    for (const ColumnPtr& kc : out_keys) { sort::SortKey s; s.col = kc; s.nulls_last = true; gk.push_back(s); }
+    place = sort::invert_permutation(sort::sort_indices(gk, -1, nullptr));
+  }
+  std::vector<ColumnPtr> placed(aggs.size());
+  std::string sorts;
+  int n_sources = 0;
+  std::vector<bool> done(aggs.size(), false);
+  for (size_t a = 0; a < quantiles.size(); a++) {
+    const size_t i = quantiles[a];
+    if (done[i]) continue;
+    std::vector<size_t> mine;
+    std::vector<sort::QuantileSpec> specs;
+    for (size_t b = a; b < quantiles.size(); b++) {
+      const size_t j = quantiles[b];
+      if (values[j] != values[i]) continue;
+      const AggParams ap = params ? (*params)[j] : AggParams{};
+      mine.push_back(j); specs.push_back({ap.q, ap.interpolation}); done[j] = true;
+    }
+    PLX_REQUIRE(values[i]->len == keys[0]->len, PLX_ERR_SHAPE, "group_by: value length mismatch");
+    std::string sd;
+    std::vector<ColumnPtr> cols = sort::segment_quantiles(keys, values[i], specs, G, &sd);
+    for (size_t m = 0; m < mine.size(); m++) placed[mine[m]] = place ? ops::gather(cols[m], place) : cols[m];
+    sorts += (n_sources++ ? " + " : "") + sd;
+  }
+  for (size_t i = 0; i < aggs.size(); i++) out_aggs.push_back(cell_of[i] >= 0 ? cells[(size_t)cell_of[i]] : placed[i]);
+  if (desc) *desc = d + "quantile[sorted segments: " + sorts + ", groups=" + std::to_string(G) + ", sources=" + std::to_string(n_sources) + ", outputs=" + std::to_string(quantiles.size()) + "]";
 }
 
 }  // namespace engine

@@ -59,10 +59,12 @@ FramePtr execute(Plan& plan, int root);
 int infer_dtype(const Plan& plan, int e, const Frame& schema);
 std::string output_name(const Plan& plan, int e);
 
-// generic group-by used by plx_groupby_agg and the GroupBy executor (keys / values already columns).  ddof: one entry per aggregate, read for PLX_AGG_VAR /
-// PLX_AGG_STD (null: 1 everywhere)
+// generic group-by used by plx_groupby_agg* and the GroupBy executor (keys / values already columns).  params: one entry per aggregate -- ddof is read for
+// PLX_AGG_VAR / PLX_AGG_STD, q / interpolation for PLX_AGG_QUANTILE (null: the defaults everywhere).  Quantile entries over the SAME value column (pointer) share
+// one sort
+struct AggParams { int ddof = 1; double q = 0.5; int interpolation = PLX_QUANTILE_LINEAR; };
 void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, bool maintain_order,
-                     std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc, const std::vector<int>* ddof = nullptr);
+                     std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc, const std::vector<AggParams>* params = nullptr);
 
 // compile-only entry used by tests: lowers `Filter*(pred) -> Select/GroupBy` rooted at
 // `root` and reports the fused shape (and whether an AOT specialisation matches)

@@ -18,12 +18,15 @@
 //   top-k  : `limit` << n: MSD radix select on the first key finds the smallest prefix bucket that contains the
 //            limit-th row; rows at or below it (ties included) are compacted in row order and only those are
 //            sorted -- same result as the full stable sort followed by head(limit).
+//   quantile: a whole column never sorts: the same MSD select finds the codes at two neighbouring ranks (select_ranks); a group-by sorts (keys, value) once per
+//            source, finds the segment heads through the permutation and picks two values per group (segment_quantiles).  The arithmetic is quantile.hpp's.
 // Everything is HBM-streaming integer work: 12 B read + 12 B written per row and pass.
 #include <algorithm>
 
 #include "dev.hpp"
 #include "kernels.hpp"
 #include "ops.hpp"
+#include "quantile.hpp"
 #include "scan.hpp"
 #include "sort.hpp"
 
@@ -45,26 +48,8 @@ struct KeyCol {
 
 enum EncodeMode { ENC_VALUE = 0, ENC_NULL_RANK = 1, ENC_SELECT = 2 };
 
-__device__ __forceinline__ uint64_t flip_f64(double d) {
-  const uint64_t b = (d != d) ? 0x7ff8000000000000ull : (uint64_t)__double_as_longlong(d + 0.0);   // one NaN, -0 -> +0
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ uint64_t encode_value(const KeyCol& kc, int64_t r) {
-  constexpr uint64_t kSign = 0x8000000000000000ull;
-  switch (kc.dtype) {
-    case PLX_I8: return (uint64_t)(long long)reinterpret_cast<const int8_t*>(kc.values)[r] ^ kSign;
-    case PLX_I16: return (uint64_t)(long long)reinterpret_cast<const int16_t*>(kc.values)[r] ^ kSign;
-    case PLX_I32: return (uint64_t)(long long)reinterpret_cast<const int32_t*>(kc.values)[r] ^ kSign;
-    case PLX_I64: return reinterpret_cast<const uint64_t*>(kc.values)[r] ^ kSign;
-    case PLX_U8: return reinterpret_cast<const uint8_t*>(kc.values)[r];
-    case PLX_U16: return reinterpret_cast<const uint16_t*>(kc.values)[r];
-    case PLX_U32: return reinterpret_cast<const uint32_t*>(kc.values)[r];
-    case PLX_F32: return flip_f64((double)reinterpret_cast<const float*>(kc.values)[r]);
-    case PLX_F64: return flip_f64(reinterpret_cast<const double*>(kc.values)[r]);
-    case PLX_BOOL: return (reinterpret_cast<const uint64_t*>(kc.values)[r >> 6] >> (r & 63)) & 1;
-    default: return reinterpret_cast<const uint64_t*>(kc.values)[r];
-  }
-}
+// the value code itself lives in quantile.hpp: the host decodes selected codes with its inverse
+__device__ __forceinline__ uint64_t encode_value(const KeyCol& kc, int64_t r) { return quantile::encode_value(kc.dtype, kc.values, r); }
 
 __global__ __launch_bounds__(kBlock) void encode_kernel(KeyCol kc, const uint32_t* __restrict__ perm, int64_t n, int descending, int nulls_last, int mode,
                                                         uint64_t* __restrict__ enc) {
@@ -477,6 +462,228 @@ ColumnPtr sort_indices(const std::vector<SortKey>& keys, int64_t limit, std::str
   else k::fill_iota_u32(out->values->as<uint32_t>(), n_out);   // every digit of every key was uniform
   d += "radix_sort[rows=" + std::to_string(m) + ", keys=" + std::to_string(keys.size()) + ", passes=" + std::to_string(w.passes) + ", uniform digits skipped=" + std::to_string(w.skipped) + "]";
   if (desc) *desc = d;
+  return out;
+}
+
+// ------------------------------------------------------------------------------ median / quantile ---
+// Whole column: MSD radix select.  The codes are ENC_SELECT's (nulls = ~0, after every valid row; a valid ~0 ties with them, which moves no valid rank).  The first
+// round histograms the top digit and reduces AND / OR over the valid codes: a digit on which AND == OR is the same in every valid row and costs no round, as in the
+// sort.  Every other digit is one select_hist_kernel pass under the prefix chosen so far.  8 B read per row and round.
+__global__ __launch_bounds__(kBlock) void select_first_kernel(const uint64_t* __restrict__ enc, const uint64_t* __restrict__ validity, int64_t n, unsigned int* __restrict__ hist,
+                                                              unsigned long long* __restrict__ and_or) {
+  __shared__ unsigned int h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  uint64_t a = ~0ull, o = 0ull;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t e = enc[i];
+    atomicAdd(&h[(int)(e >> 56)], 1u);
+    if (!validity || ((validity[i >> 6] >> (i & 63)) & 1)) { a &= e; o |= e; }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) { a &= shfl_xor_u64(a, m); o |= shfl_xor_u64(o, m); }
+  if ((threadIdx.x & 63) == 0) { atomicAnd(&and_or[0], (unsigned long long)a); atomicOr(&and_or[1], (unsigned long long)o); }
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
+}
+// *out = the smallest code greater than `code` (~0 when there is none; *out starts as ~0)
+__global__ __launch_bounds__(kBlock) void select_next_kernel(const uint64_t* __restrict__ enc, int64_t n, uint64_t code, unsigned long long* __restrict__ out) {
+  uint64_t m = ~0ull;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t e = enc[i];
+    if (e > code && e < m) m = e;
+  }
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) { const uint64_t t = shfl_xor_u64(m, s); m = t < m ? t : m; }
+  if ((threadIdx.x & 63) == 0 && m != ~0ull) atomicMin(out, (unsigned long long)m);
+}
+
+SelectedRanks select_ranks(const ColumnPtr& col, int64_t n_valid, uint64_t lo, uint64_t hi, std::string* desc) {
+  const int64_t n = col->len;
+  PLX_REQUIRE(n < 0xffffffffll, PLX_ERR_UNSUPPORTED, "quantile: more rows than u32 IdxSize");
+  PLX_REQUIRE(n_valid >= 1 && n_valid <= n && lo <= hi && hi <= lo + 1 && hi < (uint64_t)n_valid, PLX_ERR_INVALID, "quantile select: ranks outside the valid rows");
+  Buf enc = dev_alloc((size_t)n * 8);
+  SortKey key; key.col = col; key.descending = false; key.nulls_last = true;
+  encode(key, nullptr, n, ENC_SELECT, enc->as<uint64_t>());
+  constexpr size_t kHistBytes = 256 * sizeof(unsigned int);
+  Buf hist = dev_alloc(kHistBytes + 16);            // 256 counts, then AND and OR of the valid codes
+  unsigned long long* and_or = reinterpret_cast<unsigned long long*>(hist->as<unsigned char>() + kHistBytes);
+  struct { unsigned int h[256]; unsigned long long and_or[2]; } host;
+  static_assert(sizeof(host) == kHistBytes + 16, "histogram and the AND / OR pair are one copy");
+  const int grid = k::grid_for(n, kBlock * 8, 4);
+  uint64_t prefix = 0, need = lo + 1, below = 0, mult = 0;
+  auto pick = [&]() {      // the bucket that holds the need-th smallest row under the prefix
+    uint64_t c = 0; int b = 0;
+    for (; b < 255; b++) { if (c + host.h[b] >= need) break; c += host.h[b]; }
+    below += c; need -= c; mult = host.h[b];
+    prefix = (prefix << 8) | (uint64_t)b;
+  };
+  PLX_HIP(hipMemsetAsync(hist->ptr, 0, kHistBytes + 16, stream()));
+  PLX_HIP(hipMemsetAsync(and_or, 0xff, 8, stream()));
+  {
+    ProfileScope ps("quantile_select_first", (uint64_t)n * 8 + (uint64_t)n / 8, (uint64_t)n);
+    hipLaunchKernelGGL(select_first_kernel, dim3(grid), dim3(kBlock), 0, stream(), enc->as<uint64_t>(), col->valid_words(), n, hist->as<unsigned int>(), and_or);
+    PLX_HIP(hipGetLastError());
+  }
+  d2h_sync(&host, hist->ptr, sizeof(host));
+  pick();
+  int rounds = 1;
+  const uint64_t differs = host.and_or[0] ^ host.and_or[1];
+  const uint64_t common = host.and_or[0];
+  for (int shift = 48; shift >= 0; shift -= 8) {
+    if (((differs >> shift) & 255) == 0) { prefix = (prefix << 8) | ((common >> shift) & 255); continue; }      // every valid row agrees on this digit
+    PLX_HIP(hipMemsetAsync(hist->ptr, 0, kHistBytes, stream()));
+    {
+      ProfileScope ps("quantile_select_hist", (uint64_t)n * 8, (uint64_t)n);
+      hipLaunchKernelGGL(select_hist_kernel, dim3(grid), dim3(kBlock), 0, stream(), enc->as<uint64_t>(), n, shift, prefix, 1, hist->as<unsigned int>());
+      PLX_HIP(hipGetLastError());
+    }
+    d2h_sync(host.h, hist->ptr, kHistBytes);
+    pick();
+    rounds++;
+  }
+  mult = std::min<uint64_t>(mult, (uint64_t)n_valid - below);      // nulls share the last bucket of an all-ones prefix
+  SelectedRanks r;
+  r.code_lo = r.code_hi = prefix;
+  const char* next = "none";
+  if (hi != lo) {
+    if (below + mult > hi) next = "same";
+    else {
+      next = "min_pass";
+      PLX_HIP(hipMemsetAsync(and_or, 0xff, 8, stream()));
+      {
+        ProfileScope ps("quantile_select_next", (uint64_t)n * 8, (uint64_t)n);
+        hipLaunchKernelGGL(select_next_kernel, dim3(grid), dim3(kBlock), 0, stream(), enc->as<uint64_t>(), n, r.code_lo, and_or);
+        PLX_HIP(hipGetLastError());
+      }
+      unsigned long long nx = 0;
+      d2h_sync(&nx, and_or, 8);
+      r.code_hi = nx;
+    }
+  }
+  if (desc) *desc = "quantile_select[rows=" + std::to_string(n) + ", valid=" + std::to_string(n_valid) + ", rounds=" + std::to_string(rounds) + ", next=" + next + "]";
+  return r;
+}
+
+// Grouped: the rows sorted by (keys..., value asc nulls last) fall into one segment per group, the valid values of a segment in order in front of its nulls.
+struct SegKeys { KeyCol k[kSegmentMaxKeys]; int n; };
+
+__device__ __forceinline__ bool row_valid(const KeyCol& kc, int64_t r) { return !kc.validity || ((kc.validity[r >> 6] >> (r & 63)) & 1); }
+
+// mask bit i = row i of the sorted order starts a segment: i == 0, or a key differs from row i - 1 (the sort's equality: null == null, NaN == NaN, -0 == +0)
+__global__ __launch_bounds__(kBlock) void segment_heads_kernel(SegKeys keys, const uint32_t* __restrict__ perm, int64_t n, uint64_t* __restrict__ mask) {
+  const int64_t n_round = (n + 63) & ~63ll;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * blockDim.x) {
+    bool head = false;
+    if (i < n) {
+      head = i == 0;
+      if (!head) {
+        const int64_t r = (int64_t)perm[i], p = (int64_t)perm[i - 1];
+#pragma unroll
+        for (int j = 0; j < kSegmentMaxKeys; j++) {
+          if (j < keys.n && !head) {
+            const bool vr = row_valid(keys.k[j], r), vp = row_valid(keys.k[j], p);
+            head = vr != vp || (vr && encode_value(keys.k[j], r) != encode_value(keys.k[j], p));
+          }
+        }
+      }
+    }
+    const uint64_t m = ballot(head);
+    if ((threadIdx.x & 63) == 0) mask[i >> 6] = m;
+  }
+}
+
+// one group per lane: the segment [starts[g], starts[g + 1]) (the last one ends at n), its valid rows by a binary search for the first null, two gathered values
+__global__ __launch_bounds__(kBlock) void segment_quantile_kernel(KeyCol v, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ starts, int64_t n_groups, int64_t n,
+                                                                  double q, int interpolation, int out_f32, void* __restrict__ out, uint64_t* __restrict__ out_valid) {
+  const int64_t g_round = (n_groups + 63) & ~63ll;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < g_round; g += (int64_t)gridDim.x * blockDim.x) {
+    bool ok = false;
+    double res = 0.0;
+    if (g < n_groups) {
+      const int64_t s = (int64_t)starts[g], e = g + 1 < n_groups ? (int64_t)starts[g + 1] : n;
+      int64_t nv = e - s;
+      if (v.validity) {
+        int64_t lo = s, hi = e;
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (row_valid(v, (int64_t)perm[mid])) lo = mid + 1; else hi = mid; }
+        nv = lo - s;
+      }
+      if (nv > 0) {
+        const quantile::Rank rk = quantile::rank_of((uint64_t)nv, q, interpolation);
+        const double a = quantile::decode(v.dtype, encode_value(v, (int64_t)perm[s + (int64_t)rk.lo]));
+        const double b = rk.hi == rk.lo ? a : quantile::decode(v.dtype, encode_value(v, (int64_t)perm[s + (int64_t)rk.hi]));
+        res = quantile::combine(a, b, rk.frac, interpolation);
+        ok = true;
+      }
+      if (out_f32) reinterpret_cast<float*>(out)[g] = (float)res; else reinterpret_cast<double*>(out)[g] = res;
+    }
+    const uint64_t m = ballot(ok);
+    if ((threadIdx.x & 63) == 0) out_valid[g >> 6] = m;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void invert_permutation_kernel(const uint32_t* __restrict__ perm, int64_t n, uint32_t* __restrict__ inv) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t p = perm[i];
+    if ((int64_t)p < n) inv[p] = (uint32_t)i;
+  }
+}
+
+ColumnPtr invert_permutation(const ColumnPtr& perm) {
+  PLX_REQUIRE(perm->dtype == PLX_U32 && !perm->validity, PLX_ERR_INVALID, "invert_permutation: a u32 permutation without nulls");
+  ColumnPtr out = make_idx(perm->len);
+  if (!perm->len) return out;
+  ProfileScope ps("invert_permutation", (uint64_t)perm->len * 8, (uint64_t)perm->len);
+  hipLaunchKernelGGL(invert_permutation_kernel, dim3(k::grid_for(perm->len, kBlock * 4)), dim3(kBlock), 0, stream(), perm->values->as<uint32_t>(), perm->len, out->values->as<uint32_t>());
+  PLX_HIP(hipGetLastError());
+  return out;
+}
+
+std::vector<ColumnPtr> segment_quantiles(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, const std::vector<QuantileSpec>& specs, int64_t expect_groups, std::string* sort_desc) {
+  PLX_REQUIRE(!keys.empty() && (int)keys.size() <= kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, "grouped quantile: 1.." + std::to_string(kSegmentMaxKeys) + " key columns, got " + std::to_string(keys.size()));
+  const int64_t n = value->len;
+  const bool f32 = value->dtype == PLX_F32;
+  std::vector<SortKey> sk;
+  for (const ColumnPtr& kc : keys) { SortKey s; s.col = kc; s.nulls_last = true; sk.push_back(s); }
+  { SortKey s; s.col = value; s.nulls_last = true; sk.push_back(s); }
+  ColumnPtr perm = sort_indices(sk, -1, sort_desc);
+  int64_t n_groups = 0;
+  Buf starts = dev_alloc(4);
+  if (n) {
+    SegKeys segk{};
+    segk.n = (int)keys.size();
+    for (size_t j = 0; j < keys.size(); j++) segk.k[j] = key_col(keys[j]);
+    Buf mask = dev_alloc(bitmap_bytes(n));
+    {
+      ProfileScope ps("segment_heads", (uint64_t)n * 4 + (uint64_t)n / 8, (uint64_t)n);
+      hipLaunchKernelGGL(segment_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), segk, perm->values->as<uint32_t>(), n, mask->as<uint64_t>());
+      PLX_HIP(hipGetLastError());
+    }
+    k::FilterPlan fp = k::filter_prepare(mask->as<uint64_t>(), n);
+    n_groups = fp.n_out;
+    PLX_REQUIRE(n_groups == expect_groups, PLX_ERR_INVALID, "grouped quantile: segment count mismatch (" + std::to_string(n_groups) + " segments, " + std::to_string(expect_groups) + " groups)");
+    Buf iota = dev_alloc((size_t)n * 4);
+    k::fill_iota_u32(iota->as<uint32_t>(), n);
+    starts = dev_alloc((size_t)std::max<int64_t>(n_groups, 1) * 4);
+    k::filter_apply(fp, 4, iota->ptr, nullptr, starts->ptr, nullptr);
+  } else {
+    PLX_REQUIRE(expect_groups == 0, PLX_ERR_INVALID, "grouped quantile: segment count mismatch (0 segments, " + std::to_string(expect_groups) + " groups)");
+  }
+  std::vector<ColumnPtr> out;
+  for (const QuantileSpec& sp : specs) {
+    auto c = std::make_shared<Column>();
+    c->dtype = f32 ? PLX_F32 : PLX_F64; c->len = n_groups;
+    c->values = dev_alloc(values_bytes(c->dtype, std::max<int64_t>(n_groups, 1)));
+    c->validity = dev_alloc_zero(bitmap_bytes(n_groups));
+    c->null_count = -1;
+    if (n_groups) {
+      ProfileScope ps("segment_quantile", (uint64_t)n_groups * 32, (uint64_t)n_groups);
+      hipLaunchKernelGGL(segment_quantile_kernel, dim3(k::grid_for(n_groups, kBlock)), dim3(kBlock), 0, stream(), key_col(value), perm->values->as<uint32_t>(), starts->as<uint32_t>(), n_groups, n,
+                         sp.q, sp.interpolation, f32 ? 1 : 0, c->values->ptr, c->validity->as<uint64_t>());
+      PLX_HIP(hipGetLastError());
+    }
+    out.push_back(c);
+  }
   return out;
 }
 

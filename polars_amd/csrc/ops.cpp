@@ -6,6 +6,8 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "quantile.hpp"
+#include "sort.hpp"
 #include "temporal.hpp"
 
 namespace plx {
@@ -328,6 +330,24 @@ ScalarValue reduce_var(const ColumnPtr& c, int ddof, bool want_std) {
   const double v = variance::finalize(m.n, m.m2, ddof, want_std, &valid);
   r.valid = valid;
   if (valid) { if (r.dtype == PLX_F32) r.v.f32 = (float)v; else r.v.f64 = v; }
+  return r;
+}
+
+// median / quantile of a whole column (reference: ChunkQuantile, polars-core/src/chunked_array/ops/aggregate/quantile.rs): the ranks from quantile.hpp, the two value
+// codes from the radix select, decoded and combined here
+ScalarValue reduce_quantile(const ColumnPtr& c, double q, int interpolation, std::string* desc) {
+  PLX_REQUIRE(quantile::q_ok(q), PLX_ERR_INVALID, "quantile: q must be a real number in [0, 1], got " + std::to_string(q));
+  PLX_REQUIRE(quantile::interpolation_ok(interpolation), PLX_ERR_INVALID, "quantile: interpolation " + std::to_string(interpolation) + " is no plx_quantile_interpolation (0..4)");
+  if (!(dtype_is_int(c->dtype) || dtype_is_float(c->dtype))) fail(PLX_ERR_UNSUPPORTED, std::string("median / quantile of a ") + dtype_name(c->dtype) + " column: integer and float columns only");
+  PLX_REQUIRE(c->values || c->len == 0, PLX_ERR_INVALID, "placeholder column has no data");
+  ScalarValue r; r.v.u = 0; r.valid = false; r.dtype = c->dtype == PLX_F32 ? PLX_F32 : PLX_F64;
+  const int64_t n_valid = c->len - column_null_count(c);
+  if (n_valid <= 0) { if (desc) *desc = "quantile_select[rows=" + std::to_string(c->len) + ", valid=0]"; return r; }
+  const quantile::Rank rk = quantile::rank_of((uint64_t)n_valid, q, interpolation);
+  const sort::SelectedRanks sel = sort::select_ranks(c, n_valid, rk.lo, rk.hi, desc);
+  const double v = quantile::combine(quantile::decode(c->dtype, sel.code_lo), quantile::decode(c->dtype, sel.code_hi), rk.frac, interpolation);
+  r.valid = true;
+  if (r.dtype == PLX_F32) r.v.f32 = (float)v; else r.v.f64 = v;
   return r;
 }
 

@@ -2,6 +2,8 @@
 // validity/dtype logic around the raw kernels.  Used by the C ABI kernel-level entry
 // points and by the materialising expression evaluator.
 #pragma once
+#include <string>
+
 #include "core.hpp"
 
 namespace plx {
@@ -31,6 +33,9 @@ struct ScalarValue { plx_scalar v; int dtype; bool valid; };
 ScalarValue reduce(int agg_op, const ColumnPtr& c);
 // var (want_std: its square root) of the valid rows with `ddof` delta degrees of freedom: Float64 (Float32 for a Float32 column), null when valid rows <= ddof
 ScalarValue reduce_var(const ColumnPtr& c, int ddof, bool want_std);
+// quantile q in [0, 1] of the valid rows with a plx_quantile_interpolation (the median: 0.5, linear): Float64 (Float32 for a Float32 column), null without a valid
+// row; *desc (may be null) names the radix select's rounds
+ScalarValue reduce_quantile(const ColumnPtr& c, double q, int interpolation, std::string* desc);
 ColumnPtr scalar_column(const ScalarValue& s);                 // length-1 column
 ColumnPtr full_column(int dtype, plx_scalar v, bool valid, int64_t len);  // broadcast literal
 ColumnPtr fill_null(const ColumnPtr& c, plx_scalar v);                     // valid ? value : literal (same dtype)

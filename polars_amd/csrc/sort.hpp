@@ -28,5 +28,22 @@ ColumnPtr sort_indices(const std::vector<SortKey>& keys, int64_t limit, std::str
 // sorted codes (`keys` itself or a scratch buffer of the same size; the other one is released); *passes / *skipped (may be null) = digit passes run / skipped.
 Buf sort_keys_u64(Buf keys, int64_t m, int first_digit, int* passes, int* skipped);
 
+// ---- median / quantile (quantile.hpp holds the arithmetic and the inverse of the value codes) ----
+// The value codes at ranks lo and hi (hi == lo or lo + 1, both below n_valid >= 1) among the valid rows of `col` in the sort's order: an MSD radix select, the
+// column is never sorted.  *desc = "quantile_select[rows=, valid=, rounds=R, next=none|same|min_pass]": R digit rounds ran (digits on which every valid row agrees
+// cost none); the code at hi is the one at lo when its multiplicity covers hi, the smallest greater code (one min pass) otherwise.
+struct SelectedRanks { uint64_t code_lo = 0, code_hi = 0; };
+SelectedRanks select_ranks(const ColumnPtr& col, int64_t n_valid, uint64_t lo, uint64_t hi, std::string* desc);
+
+// Quantiles per group over sorted segments: one sort_indices(keys..., value; ascending, nulls last) whatever the number of (q, interpolation) pairs, the segment
+// heads found through the permutation (segment_heads_kernel) and compacted into starts[G], one lane per group picking two values (segment_quantile_kernel).  One
+// column per spec (Float64; Float32 for a Float32 value column; null for a group without a valid value), G rows in KEY-SORTED order -- the order of
+// sort_indices(group keys; ascending, nulls last).  G must equal expect_groups (PLX_ERR_INVALID naming both otherwise).
+constexpr int kSegmentMaxKeys = 8;
+struct QuantileSpec { double q; int interpolation; };
+std::vector<ColumnPtr> segment_quantiles(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, const std::vector<QuantileSpec>& specs, int64_t expect_groups, std::string* sort_desc);
+// inv[perm[i]] = i
+ColumnPtr invert_permutation(const ColumnPtr& perm);
+
 }  // namespace sort
 }  // namespace plx

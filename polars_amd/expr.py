@@ -105,6 +105,16 @@ class Expr:
         """Standard deviation: the square root of var(ddof)."""
         return Expr("agg", F.AGG_STD, self, value=check_ddof(ddof, "std"))
 
+    def quantile(self, quantile: float, interpolation: str = "nearest") -> "Expr":
+        """The quantile of the non-null values (py-polars expr.quantile): `quantile` a real number in [0, 1], interpolation one of "nearest", "lower", "higher",
+        "midpoint", "linear".  Float64 (Float32 stays Float32), null without a valid value; values rank in the sort's order (NaN greatest).  The node keeps
+        (q, interpolation) in `value`."""
+        return Expr("agg", F.AGG_QUANTILE, self, value=(check_quantile(quantile), check_interpolation(interpolation)))
+
+    def median(self) -> "Expr":
+        """quantile(0.5, "linear")."""
+        return Expr("agg", F.AGG_QUANTILE, self, value=(0.5, "linear"))
+
     # -- misc -----------------------------------------------------------------------------
     @property
     def str(self) -> "ExprStringNameSpace":
@@ -124,6 +134,8 @@ class Expr:
         if self.kind == "lit": return f"lit({self.value!r})"
         if self.kind == "binary": return f"({self.lhs!r} <{self.op}> {self.rhs!r})"
         if self.kind == "agg" and self.op in (F.AGG_VAR, F.AGG_STD): return f"{self.lhs!r}.{'var' if self.op == F.AGG_VAR else 'std'}(ddof={self.value})"
+        if self.kind == "agg" and self.op == F.AGG_QUANTILE:
+            return f"{self.lhs!r}.median()" if self.value == (0.5, "linear") else f"{self.lhs!r}.quantile({self.value[0]!r}, {self.value[1]!r})"
         if self.kind == "agg": return f"{self.lhs!r}.agg{self.op}()"
         if self.kind == "alias": return f"{self.lhs!r}.alias({self.name!r})"
         if self.kind == "cast": return f"{self.lhs!r}.cast({self.dtype})"
@@ -145,6 +157,20 @@ def check_ddof(ddof: Any, what: str) -> int:
     if isinstance(ddof, (bool, np.bool_)) or not isinstance(ddof, (int, np.integer)) or not 0 <= int(ddof) <= 255:
         raise TypeError(f"{what}(ddof=...) takes an integer 0..255, got {ddof!r}")
     return int(ddof)
+
+
+def check_quantile(q: Any) -> float:
+    """q of a quantile: a real number in [0, 1]; anything else (NaN, a number outside, no number at all) is a ValueError."""
+    if isinstance(q, (bool, np.bool_)) or not isinstance(q, (int, float, np.integer, np.floating)) or not 0.0 <= float(q) <= 1.0:
+        raise ValueError(f"quantile takes a real number in [0, 1], got {q!r}")
+    return float(q)
+
+
+def check_interpolation(interpolation: Any) -> str:
+    """One of the five interpolations on this path ("equiprobable" is not built)."""
+    if not isinstance(interpolation, str) or interpolation not in F.QUANTILE_INTERPOLATIONS:
+        raise ValueError(f"interpolation must be one of {sorted(F.QUANTILE_INTERPOLATIONS)}, got {interpolation!r}")
+    return interpolation
 
 
 STR_MATCH_NAMES = {F.STR_STARTS_WITH: "starts_with", F.STR_ENDS_WITH: "ends_with", F.STR_CONTAINS: "contains"}
@@ -323,6 +349,14 @@ def var(name: str, ddof: int = 1) -> Expr:
 
 def std(name: str, ddof: int = 1) -> Expr:
     return col(name).std(ddof)
+
+
+def median(name: str) -> Expr:
+    return col(name).median()
+
+
+def quantile(name: str, quantile: float, interpolation: str = "nearest") -> Expr:  # noqa: A002
+    return col(name).quantile(quantile, interpolation)
 
 
 _EPOCH = _dt.date(1970, 1, 1)

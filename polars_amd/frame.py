@@ -415,6 +415,22 @@ class Series:
         """Standard deviation of the non-null values (Series.std)."""
         return self._reduce_var(ddof, True, "std")
 
+    def quantile(self, quantile: float, interpolation: str = "nearest"):
+        """The quantile of the non-null values (Series.quantile): a radix select on the device, the column is never sorted.  None without a valid value."""
+        from .expr import check_interpolation, check_quantile
+        q, interpolation = check_quantile(quantile), check_interpolation(interpolation)
+        if not self.dtype.is_numeric():
+            raise TypeError(f"{'median' if (q, interpolation) == (0.5, 'linear') else 'quantile'}() needs a numeric column, got {self.dtype}")
+        v, dt, ok = F.Scalar(), C.c_int32(), C.c_int32()
+        F.check(F.lib().plx_reduce_quantile(self._h, q, F.QUANTILE_INTERPOLATIONS[interpolation], C.byref(v), C.byref(dt), C.byref(ok)))
+        if not ok.value:
+            return None
+        return float(np.float32(v.f32)) if dt.value == F.F32 else v.f64
+
+    def median(self):
+        """quantile(0.5, "linear")."""
+        return self.quantile(0.5, "linear")
+
     @property
     def str(self) -> "SeriesStringNameSpace":
         """String predicates (starts_with / ends_with / contains of a literal) on a dictionary column or on a column of raw views."""
@@ -1139,3 +1155,4 @@ class GroupBy:
     def min(self): return self._all("min")
     def max(self): return self._all("max")
     def count(self): return self._all("count")
+    def median(self): return self._all("median")

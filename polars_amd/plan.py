@@ -197,6 +197,13 @@ class Lowering:
                     raise TypeError(f"{what}() needs a numeric expression, got {dt}")
                 # ddof rides in the literal slot of the AGG node (plx_aexpr.lit.u), as a date part's unit does
                 return self._push(kind=F.AE_AGG, op=e.op, lhs=idx, lit=int(e.value)), (T.Float32 if dt == T.Float32 else T.Float64)
+            elif e.op == F.AGG_QUANTILE:
+                q, interpolation = e.value
+                if not (isinstance(dt, T.DataType) and dt.is_numeric()):      # Boolean, Date / Datetime, Categorical
+                    raise TypeError(f"{'median' if e.value == (0.5, 'linear') else 'quantile'}() needs a numeric expression, got {dt}")
+                # q rides in the literal slot of the AGG node (plx_aexpr.lit.f64), the interpolation in its otherwise unread dtype slot
+                return (self._push(kind=F.AE_AGG, op=e.op, lhs=idx, lit=float(q), dtype=F.QUANTILE_INTERPOLATIONS[interpolation]),
+                        T.Float32 if dt == T.Float32 else T.Float64)
             else:
                 out = dt
             return self._push(kind=F.AE_AGG, op=e.op, lhs=idx), out
@@ -496,6 +503,8 @@ class Lowering:
                     a.lit.i = int(d["lit"])
             if d["kind"] == F.AE_TEMPORAL or (d["kind"] == F.AE_AGG and d["op"] in (F.AGG_VAR, F.AGG_STD)):
                 a.lit.u = int(d["lit"])            # the operand's time unit / the ddof of var and std rides in the literal slot, like a lookup bitmap's handle
+            if d["kind"] == F.AE_AGG and d["op"] == F.AGG_QUANTILE:
+                a.lit.f64 = float(d["lit"])        # q (the interpolation went into the dtype slot with every other field)
             if d["kind"] == F.AE_BITMAP_LOOKUP:
                 a.lit.u = d["lut"]._h              # the lookup bitmap's column handle rides in the literal slot (plx_aexpr.lit)
                 keep.append(d["lut"])

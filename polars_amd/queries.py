@@ -41,6 +41,12 @@ def h2o_sd(lf):
     return lf.group_by("id4", "id5").agg(E.col("v3").std().alias("v3_sd"), E.col("v3").mean().alias("v3_mean"))
 
 
+def h2o_median_sd(lf):
+    """group_by(id4, id5).agg(v3.median(), v3.std()) -- the H2O group-by benchmark's `median(v3), sd(v3) by id4, id5` as it is asked: the std runs through the fused
+    scan's cells, the median over sorted segments"""
+    return lf.group_by("id4", "id5").agg(E.col("v3").median().alias("v3_median"), E.col("v3").std().alias("v3_sd"))
+
+
 def q1(lineitem, cutoff=Q1_CUTOFF):
     """TPC-H Q1; the final sort by (flag, status) happens on the host."""
     c = E.col
