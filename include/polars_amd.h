@@ -137,8 +137,23 @@ typedef enum plx_agg_op {
    * plx_groupby_agg_params takes one pair per aggregate (plx_groupby_agg / plx_groupby_agg_ddof refuse the kind); a whole column goes through plx_reduce_quantile
    * (plx_reduce refuses the kind).  Integer and float operands only: a Boolean operand is PLX_ERR_UNSUPPORTED.  It is no sum of cells: fused scans decline it, a
    * whole column runs a radix select and a group-by sorted segments. */
-  PLX_AGG_QUANTILE = 9
+  PLX_AGG_QUANTILE = 9,
+  /* The number of distinct values of the rows, a null counting as one value of its own: PLX_U32, never null; 0 for an empty column, at least 1 for a group.  Values
+   * are equal by the sort's equality (every NaN equals every NaN, -0 == +0, integers exactly).  No parameters: plx_groupby_agg, plx_groupby_agg_ddof and
+   * plx_groupby_agg_params all take it; a whole column goes through plx_reduce_n_unique (plx_reduce refuses the kind).  Any integer, float or Boolean operand (Date,
+   * Datetime and Categorical columns are integers here).  It is no sum of cells: fused scans decline it, a whole column runs one of three routes and a group-by the
+   * sorted segments of the quantiles. */
+  PLX_AGG_N_UNIQUE = 10
 } plx_agg_op;
+
+/* Which row of every class of equal rows PLX_IR_DISTINCT / plx_distinct_mask keep: FIRST the first in row order, LAST the last, NONE only the rows of classes of one
+ * row; ANY leaves the choice to the engine, which serves it as FIRST (the plan description says so). */
+typedef enum plx_unique_keep {
+  PLX_UNIQUE_ANY = 0,
+  PLX_UNIQUE_FIRST = 1,
+  PLX_UNIQUE_LAST = 2,
+  PLX_UNIQUE_NONE = 3
+} plx_unique_keep;
 
 /* With pos = (n - 1) * q over the n valid values in order and a, b the values at ranks floor(pos), ceil(pos): NEAREST = the value at rank floor(pos + 0.5),
  * LOWER = a, HIGHER = b, MIDPOINT = a == b ? a : (a + b) / 2, LINEAR = a == b ? a : (pos - floor(pos)) * (b - a) + a. */
@@ -336,6 +351,12 @@ int plx_reduce_var(plx_column col, int32_t ddof, int32_t want_std, plx_scalar* o
  * same column gives the same bits every time.  plx_last_plan_description() names the digit rounds.  Integer and float columns only (PLX_ERR_UNSUPPORTED names the
  * dtype otherwise); at most 2^32 - 2 rows. */
 int plx_reduce_quantile(plx_column col, double q, int32_t interpolation, plx_scalar* out_value, plx_dtype* out_dtype, int32_t* out_valid);
+/* Whole-column distinct count (PLX_AGG_N_UNIQUE): *out = the number of distinct values, a null counting as one; 0 for an empty column.  Three routes, named by
+ * plx_last_plan_description(): "n_unique[boolean]" (popcounts), "n_unique[bitmap range=R]" (integer columns whose exact value range R = max - min + 1 is at most
+ * max(64 * rows, 2^20): one bit per value, vector atomic OR) and "n_unique[sorted codes: passes=P, skipped=S]" (everything else: a key-only radix sort of the value
+ * codes and a count of the run heads).  PLX_NUNIQUE_ROUTE=sort in the environment forces the sorted-codes route (=bitmap is the default rule: the bitmap wherever it is legal).  Integer atomics only: the same column
+ * gives the same count every time.  At most 2^32 - 2 rows. */
+int plx_reduce_n_unique(plx_column col, uint32_t* out);
 
 /* Hash group-by with in-place aggregation.  n_keys >= 1 key columns (integer,
  * bool or float; a null key forms its own group; floats canonicalised).
@@ -356,6 +377,11 @@ int plx_groupby_agg_ddof(const plx_column* keys, int32_t n_keys, const plx_colum
 int plx_groupby_agg_params(const plx_column* keys, int32_t n_keys, const plx_column* values,
                            const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order, const int32_t* ddof,
                            const double* q, const int32_t* interpolation, plx_column* out_keys, plx_column* out_aggs);
+/* Row-order Boolean mask (no nulls) of the rows that unique() keeps: the n_keys (1..8: more is PLX_ERR_UNSUPPORTED) key columns of integer, float or Boolean dtype
+ * are sorted stably once, so the head of every run of equal rows is its first occurrence and the tail its last; keep is a plx_unique_keep (outside 0..3:
+ * PLX_ERR_INVALID).  Two rows are equal when every key is equal by the sort's equality, null == null.  Filtering any column of the same height by the mask
+ * (plx_filter) gives the distinct rows in row order. */
+int plx_distinct_mask(const plx_column* keys, int32_t n_keys, int32_t keep, plx_column* out_mask);
 
 /* Equi-join on one key column pair -> row-index pairs (PLX_U32). For LEFT joins the
  * right index column carries nulls for unmatched left rows. Null keys never match.
@@ -437,7 +463,7 @@ typedef struct plx_aexpr {
   int32_t dtype; /* literal dtype / cast target (plx_dtype) */
   int32_t is_null; /* literal is NULL */
   plx_scalar lit;   /* PLX_AE_LITERAL: the value; PLX_AE_BITMAP_LOOKUP: lit.u = the lookup bitmap's plx_column handle; PLX_AE_TEMPORAL: lit.u = the plx_time_unit;
-                     * PLX_AE_AGG of PLX_AGG_VAR / PLX_AGG_STD: lit.u = ddof; of PLX_AGG_QUANTILE: lit.f64 = q (and dtype = the plx_quantile_interpolation);
+                     * PLX_AE_AGG of PLX_AGG_VAR / PLX_AGG_STD: lit.u = ddof; of PLX_AGG_QUANTILE: lit.f64 = q (and dtype = the plx_quantile_interpolation); PLX_AGG_N_UNIQUE carries nothing;
                      * read for those kinds only */
   const char* name; /* column name / alias */
   int32_t cond;     /* PLX_AE_TERNARY: arena index of the predicate; read for that kind only (appended last: arenas of earlier callers never carry the kind) */
@@ -456,7 +482,10 @@ typedef enum plx_ir_kind {
                        * when the joint value ranges bit-pack into 63 bits, "wide_hash_join[words=N (why), ...]" / wide_hash_semi_join / wide_hash_anti_join
                        * otherwise (a table of row ids whose key words are compared column by column: any dtype mix, any value range). */
   PLX_IR_SORT = 6,    /* input, keys (by), sort_descending[n_keys], sort_nulls_last[n_keys] (IR::Sort; always stable) */
-  PLX_IR_SLICE = 7    /* input, slice_offset (negative: from the end), slice_len (IR::Slice); directly above a Sort it becomes top-k */
+  PLX_IR_SLICE = 7,   /* input, slice_offset (negative: from the end), slice_len (IR::Slice); directly above a Sort it becomes top-k */
+  PLX_IR_DISTINCT = 8 /* input, keys (the subset as column expressions, 1..8: more is PLX_ERR_UNSUPPORTED), how = the plx_unique_keep (outside 0..3: PLX_ERR_INVALID at
+                       * plan import), maintain_order 0 / 1 (IR::Distinct).  The rows that are distinct over the keys, ALWAYS in the input's row order: one stable sort of
+                       * the keys, a Boolean row mask, one filter of every column -- so maintain_order = 1 is honoured and 0 loses nothing. */
 } plx_ir_kind;
 
 /* Row order of a PLX_IR_JOIN's output (plx_ir.maintain_order of a join node; JoinArgs::maintain_order / MaintainOrderJoin of the reference).
@@ -495,8 +524,8 @@ typedef struct plx_ir {
   int32_t n_keys;
   const int32_t* keys_right;
   int32_t n_keys_right;
-  int32_t how; /* plx_join_how */
-  int32_t maintain_order; /* PLX_IR_GROUPBY / PLX_IR_SORT: 0 / 1; PLX_IR_JOIN: plx_join_order */
+  int32_t how; /* PLX_IR_JOIN: plx_join_how; PLX_IR_DISTINCT: plx_unique_keep */
+  int32_t maintain_order; /* PLX_IR_GROUPBY / PLX_IR_SORT / PLX_IR_DISTINCT: 0 / 1; PLX_IR_JOIN: plx_join_order */
   const char* suffix; /* join suffix, NULL = "_right" */
   const uint8_t* sort_descending; /* PLX_IR_SORT: n_keys flags, NULL = ascending */
   const uint8_t* sort_nulls_last; /* PLX_IR_SORT: n_keys flags, NULL = nulls first */
@@ -809,7 +838,7 @@ int plx_profile_clear(void);
  *   _polars_plugin_field_<name>(fields, n, out, kwargs, kwargs_len)   output field (minor 1 signature, plugin.rs:186-207)
  * Functions: plx_cmp / plx_arith (kwargs {"op": "gt" | ... | "add" | ...}) and one symbol per operator for callers
  * without kwargs: plx_eq ne lt le gt ge, plx_add sub mul truediv floordiv mod, plx_filter(values, mask),
- * plx_when_then_otherwise(mask, then, otherwise), plx_dt_part(values; kwargs part, unit), plx_sum mean min max (length-1 result), plx_var / plx_std (length-1 result; kwargs ddof), plx_median (length-1 result).  Python side: polars.plugins.register_plugin_function(
+ * plx_when_then_otherwise(mask, then, otherwise), plx_dt_part(values; kwargs part, unit), plx_sum mean min max (length-1 result), plx_var / plx_std (length-1 result; kwargs ddof), plx_median (length-1 result), plx_n_unique (length-1 result).  Python side: polars.plugins.register_plugin_function(
  *     plugin_path=".../libpolars_amd.so", function_name="plx_gt", args=[pl.col("a"), pl.lit(3)]).           */
 typedef struct plx_caller_context { uint64_t bitflags; } plx_caller_context;
 uint32_t _polars_plugin_get_version(void);
@@ -833,6 +862,9 @@ void _polars_plugin_field_plx_std(const struct ArrowSchema* fields, size_t n_fie
 /* plx_median (values): plx_reduce_quantile(0.5, PLX_QUANTILE_LINEAR); no kwargs; a length-1 result; the field is Float64, Float32 for a Float32 input */
 void _polars_plugin_plx_median(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
 void _polars_plugin_field_plx_median(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
+/* plx_n_unique (values): plx_reduce_n_unique; no kwargs; a length-1 result; the field is UInt32 under the input's name */
+void _polars_plugin_plx_n_unique(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
+void _polars_plugin_field_plx_n_unique(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,9 @@ ADD, SUB, MUL, TRUE_DIV, FLOOR_DIV, MOD = range(6)
 AND, OR, XOR = range(3)
 AGG_SUM, AGG_MEAN, AGG_MIN, AGG_MAX, AGG_COUNT, AGG_LEN, AGG_FIRST, AGG_VAR, AGG_STD = range(9)      # VAR / STD: ddof rides in plx_aexpr.lit.u
 AGG_QUANTILE = 9                                                          # q rides in plx_aexpr.lit.f64, the interpolation in plx_aexpr.dtype
+AGG_N_UNIQUE = 10                                                         # no parameters: UInt32 out, a null counts as one value
+UNIQUE_ANY, UNIQUE_FIRST, UNIQUE_LAST, UNIQUE_NONE = range(4)             # plx_unique_keep (rides in the `how` slot of an IR_DISTINCT node)
+UNIQUE_KEEPS = {"any": UNIQUE_ANY, "first": UNIQUE_FIRST, "last": UNIQUE_LAST, "none": UNIQUE_NONE}
 QUANTILE_NEAREST, QUANTILE_LOWER, QUANTILE_HIGHER, QUANTILE_MIDPOINT, QUANTILE_LINEAR = range(5)      # plx_quantile_interpolation
 QUANTILE_INTERPOLATIONS = {"nearest": QUANTILE_NEAREST, "lower": QUANTILE_LOWER, "higher": QUANTILE_HIGHER, "midpoint": QUANTILE_MIDPOINT, "linear": QUANTILE_LINEAR}
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI, JOIN_FULL, JOIN_RIGHT = range(6)
@@ -39,7 +42,7 @@ UNIT_DATE, UNIT_MS, UNIT_US, UNIT_NS = range(4)                          # plx_t
  PART_DATE) = range(10)                                                  # plx_temporal_part_kind
 (OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_PLUS, OP_MINUS, OP_MULTIPLY, OP_TRUE_DIVIDE,
  OP_FLOOR_DIVIDE, OP_MODULUS, OP_AND, OP_OR, OP_XOR) = range(15)
-IR_SCAN, IR_FILTER, IR_SELECT, IR_HSTACK, IR_GROUPBY, IR_JOIN, IR_SORT, IR_SLICE = range(8)
+IR_SCAN, IR_FILTER, IR_SELECT, IR_HSTACK, IR_GROUPBY, IR_JOIN, IR_SORT, IR_SLICE, IR_DISTINCT = range(9)
 PLAN_NO_FUSION = 1
 PLAN_NO_DIRECT_JOIN = 2
 PLAN_NO_PARTITION = 4
@@ -219,6 +222,8 @@ SIGNATURES = {
     "plx_datagen_zipf": (C.c_int, [C.c_int64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int64, _u64p]),
     "plx_datagen_zipf_host": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int64, C.c_void_p]),
     "plx_debug_program_json": (C.c_int, [C.POINTER(IR), C.c_int32, C.POINTER(AExpr), C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
+    "plx_reduce_n_unique": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint32)]),
+    "plx_distinct_mask": (C.c_int, [_u64p, C.c_int32, C.c_int32, _u64p]),
     "plx_sort_indices": (C.c_int, [_u64p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int64, _u64p]),
     "plx_hash_partition": (C.c_int, [C.c_uint64, C.c_int32, C.c_uint64, _u64p, _i64p]),
     "plx_frame_new": (C.c_int, [C.POINTER(C.c_char_p), _u64p, C.c_int32, _u64p]),

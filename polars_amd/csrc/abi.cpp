@@ -9,6 +9,7 @@
 
 #include "core.hpp"
 #include "datagen_device.hpp"
+#include "distinct.hpp"
 #include "encoded_inputs.hpp"
 #include "engine.hpp"
 #include "fused_shapes.hpp"
@@ -353,6 +354,7 @@ int plx_reduce(plx_agg_op op, plx_column col, plx_scalar* out_value, plx_dtype* 
   PLX_TRY
   PLX_REQUIRE(op != PLX_AGG_VAR && op != PLX_AGG_STD, PLX_ERR_INVALID, "plx_reduce: var / std take ddof: call plx_reduce_var");
   PLX_REQUIRE(op != PLX_AGG_QUANTILE, PLX_ERR_INVALID, "plx_reduce: a quantile takes q and an interpolation: call plx_reduce_quantile");
+  PLX_REQUIRE(op != PLX_AGG_N_UNIQUE, PLX_ERR_INVALID, "plx_reduce: a distinct count has routes of its own: call plx_reduce_n_unique");
   ops::ScalarValue r = ops::reduce(op, get_column(col));
   if (out_value) *out_value = r.v;
   if (out_dtype) *out_dtype = (plx_dtype)r.dtype;
@@ -375,6 +377,14 @@ int plx_reduce_quantile(plx_column col, double q, int32_t interpolation, plx_sca
   if (out_value) *out_value = r.v;
   if (out_dtype) *out_dtype = (plx_dtype)r.dtype;
   if (out_valid) *out_valid = r.valid ? 1 : 0;
+  PLX_CATCH
+}
+int plx_reduce_n_unique(plx_column col, uint32_t* out) {
+  PLX_TRY
+  std::string d;
+  ops::ScalarValue r = ops::reduce_n_unique(get_column(col), &d);
+  t_plan_desc = d;
+  if (out) *out = (uint32_t)r.v.u;
   PLX_CATCH
 }
 
@@ -408,6 +418,19 @@ int plx_groupby_agg_params(const plx_column* keys, int32_t n_keys, const plx_col
   t_plan_desc = d;
   for (int i = 0; i < n_keys; i++) out_keys[i] = register_column(ok[i]);
   for (int i = 0; i < n_aggs; i++) out_aggs[i] = register_column(oa[i]);
+  PLX_CATCH
+}
+
+int plx_distinct_mask(const plx_column* keys, int32_t n_keys, int32_t keep, plx_column* out_mask) {
+  PLX_TRY
+  PLX_REQUIRE(keys && n_keys >= 1 && out_mask, PLX_ERR_INVALID, "distinct_mask: need at least one key column");
+  std::vector<ColumnPtr> k;
+  for (int i = 0; i < n_keys; i++) k.push_back(get_column(keys[i]));
+  std::string sd;
+  int64_t kept = 0;
+  ColumnPtr mask = sort::distinct_rows(k, keep, &kept, &sd);
+  t_plan_desc = std::string("distinct_mask[keep=") + distinct::keep_name(distinct::keep_served(keep)) + (keep == PLX_UNIQUE_ANY ? " (asked: any)" : "") + ", " + sd + ", kept=" + std::to_string(kept) + " of " + std::to_string(mask->len) + "]";
+  *out_mask = register_column(mask);
   PLX_CATCH
 }
 
@@ -723,7 +746,7 @@ ColumnPtr plugin_arith(int op, std::vector<PluginInput>& in) {
 ColumnPtr plugin_reduce(int agg, std::vector<PluginInput>& in) { return ops::scalar_column(ops::reduce(agg, in[0].col)); }
 
 // output field of a plugin function: name of the first input, dtype by the rule of the operator
-enum FieldRule { FIELD_BOOL, FIELD_SAME, FIELD_ARITH, FIELD_SUM, FIELD_MEAN };
+enum FieldRule { FIELD_BOOL, FIELD_SAME, FIELD_ARITH, FIELD_SUM, FIELD_MEAN, FIELD_U32 };
 void plugin_field(const ArrowSchema* fields, size_t n, ArrowSchema* out, FieldRule rule, int arith_op) {
   try {
     PLX_REQUIRE(fields && n >= 1 && out, PLX_ERR_INVALID, "plugin field: bad arguments");
@@ -736,6 +759,7 @@ void plugin_field(const ArrowSchema* fields, size_t n, ArrowSchema* out, FieldRu
       case FIELD_ARITH: odt = (arith_op == PLX_TRUE_DIV && dtype_is_int(dt)) ? PLX_F64 : dt; break;
       case FIELD_SUM: odt = (dt == PLX_I8 || dt == PLX_I16 || dt == PLX_U8 || dt == PLX_U16) ? PLX_I64 : (dt == PLX_BOOL ? PLX_U32 : dt); break;   // sum_output_dtype, aggregate/mod.rs:55-64
       case FIELD_MEAN: odt = dt == PLX_F32 ? PLX_F32 : PLX_F64; break;
+      case FIELD_U32: odt = PLX_U32; break;
     }
     memset(out, 0, sizeof(*out));
     auto* nm = new std::string(fields[0].name ? fields[0].name : "");
@@ -800,6 +824,12 @@ void _polars_plugin_plx_median(PLX_PLUGIN_SIG) {
   plugin_call(inputs, n_inputs, out, ctx, 1, [&](std::vector<PluginInput>& in) { return ops::scalar_column(ops::reduce_quantile(in[0].col, 0.5, PLX_QUANTILE_LINEAR, nullptr)); });
 }
 void _polars_plugin_field_plx_median(PLX_FIELD_SIG) { (void)kwargs; (void)kwargs_len; plugin_field(fields, n_fields, out, FIELD_MEAN, 0); }
+// the distinct count of a series, a null counting as one: no kwargs; a length-1 UInt32 result under the input's name
+void _polars_plugin_plx_n_unique(PLX_PLUGIN_SIG) {
+  (void)kwargs; (void)kwargs_len;
+  plugin_call(inputs, n_inputs, out, ctx, 1, [&](std::vector<PluginInput>& in) { return ops::scalar_column(ops::reduce_n_unique(in[0].col, nullptr)); });
+}
+void _polars_plugin_field_plx_n_unique(PLX_FIELD_SIG) { (void)kwargs; (void)kwargs_len; plugin_field(fields, n_fields, out, FIELD_U32, 0); }
 void _polars_plugin_plx_filter(PLX_PLUGIN_SIG) {
   (void)kwargs; (void)kwargs_len;
   plugin_call(inputs, n_inputs, out, ctx, 2, [&](std::vector<PluginInput>& in) {

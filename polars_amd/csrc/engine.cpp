@@ -12,6 +12,7 @@
 #include <set>
 #include <sstream>
 
+#include "distinct.hpp"
 #include "encoded_inputs.hpp"
 #include "fused_shapes.hpp"
 #include "jit.hpp"
@@ -84,6 +85,13 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       PLX_REQUIRE(n.how >= PLX_JOIN_INNER && n.how <= PLX_JOIN_RIGHT, PLX_ERR_INVALID, "join: how outside 0..5 (plx_join_how)");
       n.coalesce = ir[i].coalesce;
       PLX_REQUIRE(n.coalesce >= 0 && n.coalesce <= 2, PLX_ERR_INVALID, "join: coalesce outside 0..2 (0 = the join kind's default, 1 = coalesce, 2 = keep both key columns)");
+    }
+    if (n.kind == PLX_IR_DISTINCT) {
+      PLX_REQUIRE(distinct::keep_ok(n.how), PLX_ERR_INVALID, "distinct: keep " + std::to_string(n.how) + " in the how slot is no plx_unique_keep (0 = any, 1 = first, 2 = last, 3 = none)");
+      PLX_REQUIRE(n.maintain_order == 0 || n.maintain_order == 1, PLX_ERR_INVALID, "distinct: maintain_order outside 0 / 1");
+      PLX_REQUIRE(n.input >= 0 && !n.keys.empty(), PLX_ERR_INVALID, "distinct needs an input and at least one subset column");
+      PLX_REQUIRE((int)n.keys.size() <= sort::kSegmentMaxKeys, PLX_ERR_UNSUPPORTED,
+                  "distinct: a subset of " + std::to_string(n.keys.size()) + " columns; the subset takes 1.." + std::to_string(sort::kSegmentMaxKeys) + " columns on this path");
     }
     if (ir[i].suffix) n.suffix = ir[i].suffix;
     if (n.kind == PLX_IR_SORT) {
@@ -160,7 +168,7 @@ int infer_dtype(const Plan& plan, int e, const Frame& schema) {
         case PLX_AGG_QUANTILE:
           PLX_REQUIRE(dtype_is_int(in) || dtype_is_float(in), PLX_ERR_UNSUPPORTED, std::string("median / quantile of a ") + dtype_name(in) + " expression: integer and float operands only");
           return in == PLX_F32 ? PLX_F32 : PLX_F64;
-        case PLX_AGG_COUNT: case PLX_AGG_LEN: return PLX_U32;
+        case PLX_AGG_COUNT: case PLX_AGG_LEN: case PLX_AGG_N_UNIQUE: return PLX_U32;
         default: return in;
       }
     }
@@ -282,6 +290,12 @@ static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<i
       if (x.op == PLX_AGG_QUANTILE) {
         std::string d;
         const ops::ScalarValue v = ops::reduce_quantile(c.col, x.lit.f64, x.dtype, &d);
+        t_node_notes += d + "; ";
+        return {ops::scalar_column(v), true};
+      }
+      if (x.op == PLX_AGG_N_UNIQUE) {
+        std::string d;
+        const ops::ScalarValue v = ops::reduce_n_unique(c.col, &d);
         t_node_notes += d + "; ";
         return {ops::scalar_column(v), true};
       }
@@ -609,8 +623,11 @@ class Compiler {
 
   // an order statistic is no sum of cells: a list that holds one is declined as a whole, before a var / std beside it spends its pivot pre-pass
   static constexpr const char* kOrderStatistic = "median / quantile: an order statistic (sorted-segment route)";
+  // ... and so is a distinct count; a list that holds both keeps the quantile's reason
+  static constexpr const char* kDistinctCount = "n_unique: a distinct count (sorted-segment route)";
   void decline_order_statistics(const std::vector<int>& agg_nodes) const {
     for (int a : agg_nodes) if (plan.ae.at(a).kind == PLX_AE_AGG && plan.ae[a].op == PLX_AGG_QUANTILE) throw Unsupported(kOrderStatistic);
+    for (int a : agg_nodes) if (plan.ae.at(a).kind == PLX_AE_AGG && plan.ae[a].op == PLX_AGG_N_UNIQUE) throw Unsupported(kDistinctCount);
   }
 
   // lowers one AGG / LEN node; returns how to finalise it
@@ -621,6 +638,7 @@ class Compiler {
     const int in_dt = infer_dtype(plan, x.lhs, *df);
     if (x.op == PLX_AGG_LEN) { fs.kind = FIN_TRUNC32; fs.a = (uint8_t)add_agg(AGG_LEN, -1); fs.out_dtype = PLX_U32; return fs; }
     if (x.op == PLX_AGG_QUANTILE) throw Unsupported(kOrderStatistic);
+    if (x.op == PLX_AGG_N_UNIQUE) throw Unsupported(kDistinctCount);
     // Boolean inputs: sum = number of true values (UInt32, sum_output_dtype) and mean = their fraction; a boolean slot holds 0 / 1,
     // so both reuse the integer cells.  min / max of booleans would need a bit-packed finalisation: per-node path.
     if (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD) infer_dtype(plan, e, *df);      // (fails, naming the dtype, when the operand is not numeric)
@@ -3217,6 +3235,30 @@ static FramePtr exec_slice(Plan& plan, const IRN& n) {
   return out;
 }
 
+// IR::Distinct: the rows that are distinct over the subset, in the input's row order -- one stable sort of the subset, a row-order mask of the rows to keep
+// (sort::distinct_rows), every column of the frame through the filter's compaction
+static FramePtr exec_distinct(Plan& plan, const IRN& n) {
+  FramePtr in = exec_node(plan, n.input);
+  std::vector<ColumnPtr> keys;
+  std::string subset;
+  for (int e : n.keys) {
+    keys.push_back(broadcast(eval(plan, e, *in, nullptr), in->height));
+    subset += (subset.empty() ? "" : ", ") + output_name(plan, e);
+  }
+  flush_node_notes(plan);
+  std::string sd;
+  ColumnPtr mask = sort::distinct_rows(keys, n.how, nullptr, &sd);      // (no count here: preparing the mask counts it)
+  auto pm = ops::prepare_mask(mask);
+  const int64_t kept = ops::prepared_rows(*pm);
+  auto out = std::make_shared<Frame>();
+  out->names = in->names;
+  out->height = kept;
+  for (auto& c : in->cols) out->cols.push_back(ops::filter_prepared(c, *pm));
+  plan.desc += std::string("Distinct{subset=[") + subset + "], keep=" + distinct::keep_name(distinct::keep_served(n.how)) + (n.how == PLX_UNIQUE_ANY ? " (asked: any)" : "") + ", order=rows, " + sd +
+               ", kept=" + std::to_string(kept) + " of " + std::to_string(in->height) + "}; ";
+  return out;
+}
+
 static FramePtr exec_node(Plan& plan, int node_id) {
   check_cancel();
   PLX_REQUIRE(node_id >= 0 && node_id < (int)plan.ir.size(), PLX_ERR_INVALID, "bad IR node index");
@@ -3312,6 +3354,7 @@ static FramePtr exec_node(Plan& plan, int node_id) {
     case PLX_IR_JOIN: return exec_join(plan, n);
     case PLX_IR_SORT: return exec_sort(plan, n, -1);
     case PLX_IR_SLICE: return exec_slice(plan, n);
+    case PLX_IR_DISTINCT: return exec_distinct(plan, n);
     default: fail(PLX_ERR_UNSUPPORTED, "IR node kind " + std::to_string(n.kind) + " is outside the hot path (run it on the CPU engine)");
   }
 }
@@ -3437,15 +3480,23 @@ static void groupby_cells(const std::vector<ColumnPtr>& keys, const std::vector<
 }
 
 // The aggregates that are sums of cells run through the synthesised fused plan (groupby_cells), which also owns the keys, the group order and maintain_order.  The
-// order statistics run over sorted segments, one sort per distinct source column, and are placed into the group frame by the rank of every group's key
-// (DESIGN.md 4.15).
+// order statistics and the distinct counts run over sorted segments, one sort per distinct source column whichever of the two read it, and are placed into the
+// group frame by the rank of every group's key.
 void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, bool maintain_order,
                      std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc, const std::vector<AggParams>* params) {
   PLX_REQUIRE(values.size() == aggs.size(), PLX_ERR_INVALID, "group_by: values/aggs length mismatch");
   PLX_REQUIRE(!params || params->size() == aggs.size(), PLX_ERR_INVALID, "group_by: params/aggs length mismatch");
   std::vector<ColumnPtr> cell_values;
   std::vector<int> cell_aggs, cell_ddof, cell_of(aggs.size(), -1);
-  std::vector<size_t> quantiles;
+  // one entry per distinct source column of the aggregates that leave the cell list, in the order they first appear
+  struct Source { ColumnPtr col; std::vector<size_t> quantiles, distincts; };
+  std::vector<Source> sources;
+  auto source_of = [&](const ColumnPtr& c) -> Source& {
+    for (Source& sc : sources) if (sc.col == c) return sc;
+    sources.push_back(Source{c, {}, {}});
+    return sources.back();
+  };
+  size_t n_quantiles = 0, n_distincts = 0;
   for (size_t i = 0; i < aggs.size(); i++) {
     const AggParams ap = params ? (*params)[i] : AggParams{};
     if (aggs[i] == PLX_AGG_QUANTILE) {
@@ -3453,13 +3504,21 @@ void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<Colum
       PLX_REQUIRE(quantile::interpolation_ok(ap.interpolation), PLX_ERR_INVALID, "group_by: interpolation " + std::to_string(ap.interpolation) + " is no plx_quantile_interpolation (0..4)");
       PLX_REQUIRE(values[i], PLX_ERR_INVALID, "group_by: median / quantile need a value column");
       if (!(dtype_is_int(values[i]->dtype) || dtype_is_float(values[i]->dtype))) fail(PLX_ERR_UNSUPPORTED, std::string("group_by: median / quantile of a ") + dtype_name(values[i]->dtype) + " column: integer and float columns only");
-      quantiles.push_back(i);
+      source_of(values[i]).quantiles.push_back(i);
+      n_quantiles++;
+      continue;
+    }
+    if (aggs[i] == PLX_AGG_N_UNIQUE) {
+      PLX_REQUIRE(values[i], PLX_ERR_INVALID, "group_by: n_unique needs a value column");
+      if (!(dtype_is_int(values[i]->dtype) || dtype_is_float(values[i]->dtype) || values[i]->dtype == PLX_BOOL)) fail(PLX_ERR_UNSUPPORTED, std::string("group_by: n_unique of a ") + dtype_name(values[i]->dtype) + " column: integer, float and Boolean columns only");
+      source_of(values[i]).distincts.push_back(i);
+      n_distincts++;
       continue;
     }
     cell_of[i] = (int)cell_aggs.size();
     cell_values.push_back(values[i]); cell_aggs.push_back(aggs[i]); cell_ddof.push_back(ap.ddof);
   }
-  if (quantiles.empty()) { groupby_cells(keys, values, aggs, maintain_order, out_keys, out_aggs, desc, &cell_ddof); return; }
+  if (sources.empty()) { groupby_cells(keys, values, aggs, maintain_order, out_keys, out_aggs, desc, &cell_ddof); return; }
   if (cell_aggs.empty()) { cell_values.push_back(nullptr); cell_aggs.push_back(PLX_AGG_LEN); cell_ddof.push_back(1); }      // the group frame has to exist
   std::vector<ColumnPtr> cells;
   std::string d;
@@ -3474,28 +3533,32 @@ void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<Colum
     place = sort::invert_permutation(sort::sort_indices(gk, -1, nullptr));
   }
   std::vector<ColumnPtr> placed(aggs.size());
-  std::string sorts;
-  int n_sources = 0;
-  std::vector<bool> done(aggs.size(), false);
-  for (size_t a = 0; a < quantiles.size(); a++) {
-    const size_t i = quantiles[a];
-    if (done[i]) continue;
-    std::vector<size_t> mine;
-    std::vector<sort::QuantileSpec> specs;
-    for (size_t b = a; b < quantiles.size(); b++) {
-      const size_t j = quantiles[b];
-      if (values[j] != values[i]) continue;
-      const AggParams ap = params ? (*params)[j] : AggParams{};
-      mine.push_back(j); specs.push_back({ap.q, ap.interpolation}); done[j] = true;
+  std::string q_sorts, d_sorts;
+  int q_sources = 0, d_sources = 0;
+  for (const Source& sc : sources) {
+    PLX_REQUIRE(sc.col->len == keys[0]->len, PLX_ERR_SHAPE, "group_by: value length mismatch");
+    const sort::SortedSegments seg = sort::sort_segments(keys, sc.col, G);
+    if (!sc.quantiles.empty()) {
+      std::vector<sort::QuantileSpec> specs;
+      for (size_t j : sc.quantiles) { const AggParams ap = params ? (*params)[j] : AggParams{}; specs.push_back({ap.q, ap.interpolation}); }
+      std::vector<ColumnPtr> cols = sort::segment_quantiles(seg, specs);
+      for (size_t m = 0; m < sc.quantiles.size(); m++) placed[sc.quantiles[m]] = place ? ops::gather(cols[m], place) : cols[m];
+      q_sorts += (q_sources ? " + " : "") + seg.sort_desc;
     }
-    PLX_REQUIRE(values[i]->len == keys[0]->len, PLX_ERR_SHAPE, "group_by: value length mismatch");
-    std::string sd;
-    std::vector<ColumnPtr> cols = sort::segment_quantiles(keys, values[i], specs, G, &sd);
-    for (size_t m = 0; m < mine.size(); m++) placed[mine[m]] = place ? ops::gather(cols[m], place) : cols[m];
-    sorts += (n_sources++ ? " + " : "") + sd;
+    if (!sc.distincts.empty()) {
+      ColumnPtr counts = sort::segment_distinct(seg);
+      if (place) counts = ops::gather(counts, place);
+      for (size_t j : sc.distincts) placed[j] = counts;
+      d_sorts += (d_sources ? " + " : "") + (sc.quantiles.empty() ? seg.sort_desc : "shares the sort of source " + std::to_string(q_sources));
+      d_sources++;
+    }
+    if (!sc.quantiles.empty()) q_sources++;
   }
   for (size_t i = 0; i < aggs.size(); i++) out_aggs.push_back(cell_of[i] >= 0 ? cells[(size_t)cell_of[i]] : placed[i]);
-  if (desc) *desc = d + "quantile[sorted segments: " + sorts + ", groups=" + std::to_string(G) + ", sources=" + std::to_string(n_sources) + ", outputs=" + std::to_string(quantiles.size()) + "]";
+  const std::string tail = ", groups=" + std::to_string(G) + ", sources=";
+  if (n_quantiles) d += "quantile[sorted segments: " + q_sorts + tail + std::to_string(q_sources) + ", outputs=" + std::to_string(n_quantiles) + "]";
+  if (n_distincts) d += std::string(n_quantiles ? "; " : "") + "n_unique[sorted segments: " + d_sorts + tail + std::to_string(d_sources) + ", outputs=" + std::to_string(n_distincts) + "]";
+  if (desc) *desc = d;
 }
 
 }  // namespace engine

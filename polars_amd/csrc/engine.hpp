@@ -60,8 +60,8 @@ int infer_dtype(const Plan& plan, int e, const Frame& schema);
 std::string output_name(const Plan& plan, int e);
 
 // generic group-by used by plx_groupby_agg* and the GroupBy executor (keys / values already columns).  params: one entry per aggregate -- ddof is read for
-// PLX_AGG_VAR / PLX_AGG_STD, q / interpolation for PLX_AGG_QUANTILE (null: the defaults everywhere).  Quantile entries over the SAME value column (pointer) share
-// one sort
+// PLX_AGG_VAR / PLX_AGG_STD, q / interpolation for PLX_AGG_QUANTILE (null: the defaults everywhere); PLX_AGG_N_UNIQUE reads none.  Quantile and n_unique entries
+// over the SAME value column (pointer) share one sort
 struct AggParams { int ddof = 1; double q = 0.5; int interpolation = PLX_QUANTILE_LINEAR; };
 void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, bool maintain_order,
                      std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc, const std::vector<AggParams>* params = nullptr);

@@ -20,10 +20,14 @@
 //            sorted -- same result as the full stable sort followed by head(limit).
 //   quantile: a whole column never sorts: the same MSD select finds the codes at two neighbouring ranks (select_ranks); a group-by sorts (keys, value) once per
 //            source, finds the segment heads through the permutation and picks two values per group (segment_quantiles).  The arithmetic is quantile.hpp's.
+//   distinct: n_unique of a whole column is two popcounts (Boolean), a bitmap over the value range (integers of a small range) or a key-only sort of the value
+//            codes and a count of the run heads; per group it is the difference of two ranks in a mask of run heads over the quantiles' sorted segments; unique()
+//            is one stable sort of the subset, the segment heads and a row-order mask (n_unique_column, segment_distinct, distinct_rows; distinct.hpp).
 // Everything is HBM-streaming integer work: 12 B read + 12 B written per row and pass.
 #include <algorithm>
 
 #include "dev.hpp"
+#include "distinct.hpp"
 #include "kernels.hpp"
 #include "ops.hpp"
 #include "quantile.hpp"
@@ -639,36 +643,42 @@ ColumnPtr invert_permutation(const ColumnPtr& perm) {
   return out;
 }
 
-std::vector<ColumnPtr> segment_quantiles(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, const std::vector<QuantileSpec>& specs, int64_t expect_groups, std::string* sort_desc) {
-  PLX_REQUIRE(!keys.empty() && (int)keys.size() <= kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, "grouped quantile: 1.." + std::to_string(kSegmentMaxKeys) + " key columns, got " + std::to_string(keys.size()));
-  const int64_t n = value->len;
-  const bool f32 = value->dtype == PLX_F32;
+SortedSegments sort_segments(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, int64_t expect_groups) {
+  PLX_REQUIRE(!keys.empty() && (int)keys.size() <= kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, "sorted segments: 1.." + std::to_string(kSegmentMaxKeys) + " key columns, got " + std::to_string(keys.size()));
+  SortedSegments seg;
+  seg.value = value;
+  const int64_t n = seg.n = value->len;
   std::vector<SortKey> sk;
   for (const ColumnPtr& kc : keys) { SortKey s; s.col = kc; s.nulls_last = true; sk.push_back(s); }
   { SortKey s; s.col = value; s.nulls_last = true; sk.push_back(s); }
-  ColumnPtr perm = sort_indices(sk, -1, sort_desc);
-  int64_t n_groups = 0;
-  Buf starts = dev_alloc(4);
+  seg.perm = sort_indices(sk, -1, &seg.sort_desc);
+  seg.starts = dev_alloc(4);
   if (n) {
     SegKeys segk{};
     segk.n = (int)keys.size();
     for (size_t j = 0; j < keys.size(); j++) segk.k[j] = key_col(keys[j]);
-    Buf mask = dev_alloc(bitmap_bytes(n));
+    seg.heads = dev_alloc(bitmap_bytes(n));
     {
       ProfileScope ps("segment_heads", (uint64_t)n * 4 + (uint64_t)n / 8, (uint64_t)n);
-      hipLaunchKernelGGL(segment_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), segk, perm->values->as<uint32_t>(), n, mask->as<uint64_t>());
+      hipLaunchKernelGGL(segment_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), segk, seg.perm->values->as<uint32_t>(), n, seg.heads->as<uint64_t>());
       PLX_HIP(hipGetLastError());
     }
-    k::FilterPlan fp = k::filter_prepare(mask->as<uint64_t>(), n);
-    n_groups = fp.n_out;
-    PLX_REQUIRE(n_groups == expect_groups, PLX_ERR_INVALID, "grouped quantile: segment count mismatch (" + std::to_string(n_groups) + " segments, " + std::to_string(expect_groups) + " groups)");
+    k::FilterPlan fp = k::filter_prepare(seg.heads->as<uint64_t>(), n);
+    seg.n_groups = fp.n_out;
+    PLX_REQUIRE(seg.n_groups == expect_groups, PLX_ERR_INVALID, "sorted segments: segment count mismatch (" + std::to_string(seg.n_groups) + " segments, " + std::to_string(expect_groups) + " groups)");
     Buf iota = dev_alloc((size_t)n * 4);
     k::fill_iota_u32(iota->as<uint32_t>(), n);
-    starts = dev_alloc((size_t)std::max<int64_t>(n_groups, 1) * 4);
-    k::filter_apply(fp, 4, iota->ptr, nullptr, starts->ptr, nullptr);
+    seg.starts = dev_alloc((size_t)std::max<int64_t>(seg.n_groups, 1) * 4);
+    k::filter_apply(fp, 4, iota->ptr, nullptr, seg.starts->ptr, nullptr);
   } else {
-    PLX_REQUIRE(expect_groups == 0, PLX_ERR_INVALID, "grouped quantile: segment count mismatch (0 segments, " + std::to_string(expect_groups) + " groups)");
+    PLX_REQUIRE(expect_groups == 0, PLX_ERR_INVALID, "sorted segments: segment count mismatch (0 segments, " + std::to_string(expect_groups) + " groups)");
   }
+  return seg;
+}
+
+std::vector<ColumnPtr> segment_quantiles(const SortedSegments& seg, const std::vector<QuantileSpec>& specs) {
+  const bool f32 = seg.value->dtype == PLX_F32;
+  const int64_t n_groups = seg.n_groups;
   std::vector<ColumnPtr> out;
   for (const QuantileSpec& sp : specs) {
     auto c = std::make_shared<Column>();
@@ -678,12 +688,233 @@ std::vector<ColumnPtr> segment_quantiles(const std::vector<ColumnPtr>& keys, con
     c->null_count = -1;
     if (n_groups) {
       ProfileScope ps("segment_quantile", (uint64_t)n_groups * 32, (uint64_t)n_groups);
-      hipLaunchKernelGGL(segment_quantile_kernel, dim3(k::grid_for(n_groups, kBlock)), dim3(kBlock), 0, stream(), key_col(value), perm->values->as<uint32_t>(), starts->as<uint32_t>(), n_groups, n,
+      hipLaunchKernelGGL(segment_quantile_kernel, dim3(k::grid_for(n_groups, kBlock)), dim3(kBlock), 0, stream(), key_col(seg.value), seg.perm->values->as<uint32_t>(), seg.starts->as<uint32_t>(), n_groups, seg.n,
                          sp.q, sp.interpolation, f32 ? 1 : 0, c->values->ptr, c->validity->as<uint64_t>());
       PLX_HIP(hipGetLastError());
     }
     out.push_back(c);
   }
+  return out;
+}
+
+// ------------------------------------------------------------------------------ n_unique / unique() ---
+// Both are runs of equal values in a sorted order; the arithmetic on the run-head masks is distinct.hpp's.  All atomics are vector atomics on integers (OR, ADD):
+// the same input gives the same bits every time.
+__device__ __forceinline__ bool mask_bit(const uint64_t* __restrict__ m, int64_t i) { return (m[i >> 6] >> (i & 63)) & 1; }
+// the value of row r of an integer column as i64 (every integer dtype but U64, whose range no i64 pair holds: the host never sends one)
+__device__ __forceinline__ int64_t int_value(const KeyCol& kc, int64_t r) {
+  const uint64_t e = encode_value(kc, r);
+  switch (kc.dtype) {
+    case PLX_I8: case PLX_I16: case PLX_I32: case PLX_I64: return (int64_t)(e ^ quantile::kSign);
+    default: return (int64_t)e;
+  }
+}
+
+// Whole column, bitmap route: bit (v - mn) of bits[] for every valid row; bits[] holds `range` zeroed bits (a row outside [mn, mn + range) sets nothing).  A lane
+// whose bit already shows in a plain load of the word issues no atomic (a stale load only costs a redundant OR); among the lanes left, one per distinct bit does --
+// the lowest, found by a readlane / ballot round per distinct value still pending, so a wave of equal values is one atomic and a wave of 64 new values 64 rounds.
+// 1..8 B read per row; the atomics land in L2.
+__global__ __launch_bounds__(kBlock) void distinct_bitmap_kernel(KeyCol kc, int64_t n, int64_t mn, uint64_t range, unsigned int* __restrict__ bits) {
+  const int64_t n_round = (n + 63) & ~63ll;
+  const int lane = threadIdx.x & 63;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * blockDim.x) {
+    bool need = false;
+    uint64_t off = 0;
+    if (i < n && row_valid(kc, i)) {
+      off = (uint64_t)int_value(kc, i) - (uint64_t)mn;
+      need = off < range && !((bits[off >> 5] >> (off & 31)) & 1u);
+    }
+    uint64_t todo = ballot(need);
+    while (todo) {
+      const int leader = __ffsll((long long)todo) - 1;      // wave-uniform
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)off, leader), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(off >> 32), leader);
+      const uint64_t same = ballot(need && off == (((uint64_t)hi << 32) | lo));
+      if (lane == leader) atomicOr(&bits[off >> 5], 1u << (off & 31));
+      todo &= ~same;
+    }
+  }
+}
+
+// Whole column, sorted-codes route: *out += positions i < m of the sorted codes that start a run (i == 0, or codes[i] != codes[i - 1]).  A ballot and a popcount per
+// wave and step, one LDS add per wave, one integer atomicAdd per block.  8 B read per position (the predecessor is the neighbouring lane's line).
+__global__ __launch_bounds__(kBlock) void run_heads_count_kernel(const uint64_t* __restrict__ codes, int64_t m, unsigned int* __restrict__ out) {
+  __shared__ unsigned int total;
+  if (threadIdx.x == 0) total = 0;
+  __syncthreads();
+  unsigned int c = 0;
+  const int64_t m_round = (m + 63) & ~63ll;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m_round; i += (int64_t)gridDim.x * blockDim.x) {
+    const bool head = i < m && (i == 0 || codes[i] != codes[i - 1]);
+    c += (unsigned int)popc64(ballot(head));
+  }
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(&total, c);
+  __syncthreads();
+  if (threadIdx.x == 0 && total) atomicAdd(out, total);
+}
+
+// Grouped: mask bit i = position i of the sorted order starts a segment (the segment-head mask) or its value differs from position i - 1 through the permutation: a
+// null and a value differ, two nulls do not, values by the sort's equality.  4 B of perm + a gathered value per position.
+__global__ __launch_bounds__(kBlock) void distinct_heads_kernel(KeyCol v, const uint32_t* __restrict__ perm, const uint64_t* __restrict__ seg_heads, int64_t n, uint64_t* __restrict__ mask) {
+  const int64_t n_round = (n + 63) & ~63ll;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * blockDim.x) {
+    bool head = false;
+    if (i < n) {
+      head = i == 0 || mask_bit(seg_heads, i);
+      if (!head) {
+        const int64_t r = (int64_t)perm[i], p = (int64_t)perm[i - 1];
+        const bool vr = row_valid(v, r), vp = row_valid(v, p);
+        head = vr != vp || (vr && encode_value(v, r) != encode_value(v, p));
+      }
+    }
+    const uint64_t m = ballot(head);
+    if ((threadIdx.x & 63) == 0) mask[i >> 6] = m;
+  }
+}
+// counts[w] = set bits of word w of a mask of n_bits bits (the input of the exclusive scan that gives distinct::rank_before its prefix)
+__global__ __launch_bounds__(kBlock) void mask_word_counts_kernel(const uint64_t* __restrict__ mask, int64_t n_bits, uint32_t* __restrict__ counts) {
+  const int64_t nwords = (n_bits + 63) >> 6;
+  for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nwords; w += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t x = mask[w];
+    if (w == nwords - 1 && (n_bits & 63)) x &= (~0ull) >> (64 - (n_bits & 63));
+    counts[w] = (uint32_t)popc64(x);
+  }
+}
+// one group per lane: the distinct values of the segment [starts[g], starts[g + 1]) (the last one ends at n) = the difference of two ranks in the mask of
+// distinct_heads_kernel.  O(1) per group whatever its size.
+__global__ __launch_bounds__(kBlock) void segment_distinct_kernel(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ prefix, const uint32_t* __restrict__ starts, int64_t n_groups,
+                                                                  int64_t n, uint32_t* __restrict__ out) {
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n_groups; g += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t s = starts[g], e = g + 1 < n_groups ? (uint64_t)starts[g + 1] : (uint64_t)n;
+    out[g] = (s <= e && e <= (uint64_t)n) ? (uint32_t)(distinct::rank_before(prefix, mask, e) - distinct::rank_before(prefix, mask, s)) : 0u;
+  }
+}
+
+// Distinct rows: position i of the stable sorted order is the first row of its class when the segment-head mask has bit i, the last when it has bit i + 1 (or
+// i + 1 == n); a kept position sets bit perm[i] of the ROW-ORDER mask out_bits (n zeroed bits) with a u32 atomic OR.  Only kept rows issue one.
+__global__ __launch_bounds__(kBlock) void distinct_keep_kernel(const uint64_t* __restrict__ heads, const uint32_t* __restrict__ perm, int64_t n, int keep, unsigned int* __restrict__ out_bits) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const bool is_head = mask_bit(heads, i), is_tail = i + 1 == n || mask_bit(heads, i + 1);
+    if (!distinct::keep_row(is_head, is_tail, keep)) continue;
+    const uint32_t r = perm[i];
+    if ((int64_t)r < n) atomicOr(&out_bits[r >> 5], 1u << (r & 31));
+  }
+}
+
+ColumnPtr segment_distinct(const SortedSegments& seg) {
+  const int64_t n = seg.n, n_groups = seg.n_groups;
+  ColumnPtr out = make_idx(n_groups);
+  if (!n_groups) return out;
+  const int64_t nwords = (n + 63) >> 6;
+  Buf mask = dev_alloc(bitmap_bytes(n));
+  {
+    ProfileScope ps("distinct_heads", (uint64_t)n * (4 + (dtype_width(seg.value->dtype) ? dtype_width(seg.value->dtype) : 1)) + (uint64_t)n / 4, (uint64_t)n);
+    hipLaunchKernelGGL(distinct_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), key_col(seg.value), seg.perm->values->as<uint32_t>(), seg.heads->as<uint64_t>(), n, mask->as<uint64_t>());
+    PLX_HIP(hipGetLastError());
+  }
+  Buf counts = dev_alloc((size_t)nwords * 4), prefix = dev_alloc(((size_t)nwords + 1) * 8);
+  hipLaunchKernelGGL(mask_word_counts_kernel, dim3(k::grid_for(nwords, kBlock * 4)), dim3(kBlock), 0, stream(), mask->as<uint64_t>(), n, counts->as<uint32_t>());
+  PLX_HIP(hipGetLastError());
+  k::exclusive_scan_u32(counts->as<uint32_t>(), prefix->as<uint64_t>(), nwords);
+  {
+    ProfileScope ps("segment_distinct", (uint64_t)n_groups * 44, (uint64_t)n_groups);
+    hipLaunchKernelGGL(segment_distinct_kernel, dim3(k::grid_for(n_groups, kBlock)), dim3(kBlock), 0, stream(), mask->as<uint64_t>(), prefix->as<uint64_t>(), seg.starts->as<uint32_t>(), n_groups, n,
+                       out->values->as<uint32_t>());
+    PLX_HIP(hipGetLastError());
+  }
+  return out;
+}
+
+uint32_t n_unique_column(const ColumnPtr& c, bool force_sort, std::string* desc) {
+  const int64_t n = c->len;
+  PLX_REQUIRE(n < 0xffffffffll, PLX_ERR_UNSUPPORTED, "n_unique: more rows than u32 IdxSize");
+  if (!(dtype_is_int(c->dtype) || dtype_is_float(c->dtype) || c->dtype == PLX_BOOL)) fail(PLX_ERR_UNSUPPORTED, std::string("n_unique of a ") + dtype_name(c->dtype) + " column: integer, float and Boolean columns only");
+  PLX_REQUIRE(c->values || n == 0, PLX_ERR_INVALID, "placeholder column has no data");
+  if (n == 0) { if (desc) *desc = "n_unique[empty]"; return 0; }
+  const int64_t nulls = column_null_count(c), n_valid = n - nulls;
+  const uint32_t null_class = nulls > 0 ? 1u : 0u;
+  if (c->dtype == PLX_BOOL) {
+    // two popcounts (true-and-valid, valid) and the null count
+    int64_t trues;
+    if (c->validity) {
+      Buf t = dev_alloc_zero(bitmap_bytes(n));
+      k::bitmap_op(0, c->values->as<uint64_t>(), c->validity->as<uint64_t>(), n, t->as<uint64_t>());
+      trues = k::bitmap_popcount(t->as<uint64_t>(), n);
+    } else trues = k::bitmap_popcount(c->values->as<uint64_t>(), n);
+    if (desc) *desc = "n_unique[boolean]";
+    return (trues > 0 ? 1u : 0u) + (n_valid - trues > 0 ? 1u : 0u) + null_class;
+  }
+  int64_t mn = 0, mx = 0;
+  uint64_t range = 0;
+  bool bitmap = false;
+  if (!force_sort && dtype_is_int(c->dtype) && c->dtype != PLX_U64 && ops::int_range(c, &mn, &mx)) {
+    range = (uint64_t)mx - (uint64_t)mn + 1;      // 0 when the column spans all of i64: no bitmap
+    bitmap = mx >= mn && distinct::bitmap_route_ok(range, (uint64_t)n);
+  }
+  if (bitmap) {
+    Buf bits = dev_alloc_zero((size_t)((range + 63) / 64) * 8 + 8);
+    {
+      ProfileScope ps("distinct_bitmap", (uint64_t)n * dtype_width(c->dtype) + range / 4, (uint64_t)n);
+      hipLaunchKernelGGL(distinct_bitmap_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), key_col(c), n, mn, range, bits->as<unsigned int>());
+      PLX_HIP(hipGetLastError());
+    }
+    const int64_t values = k::bitmap_popcount(bits->as<uint64_t>(), (int64_t)range);
+    if (desc) *desc = "n_unique[bitmap range=" + std::to_string(range) + "]";
+    return (uint32_t)values + null_class;
+  }
+  // the select's codes: nulls = ~0 behind every valid row.  A valid ~0 (INT64_MAX, UINT64_MAX) has the code of a null and sorts among them; the first n_valid sorted
+  // positions still hold every valid row's code, so the heads are counted there and the nulls added as one class of their own.
+  Buf enc = dev_alloc((size_t)n * 8);
+  SortKey key; key.col = c; key.descending = false; key.nulls_last = true;
+  encode(key, nullptr, n, ENC_SELECT, enc->as<uint64_t>());
+  int passes = 0, skipped = 0;
+  Buf sorted = sort_keys_u64(enc, n, 0, &passes, &skipped);
+  if (n <= 1) skipped = 8;      // (nothing to sort)
+  uint32_t values = 0;
+  if (n_valid > 0) {
+    Buf cnt = dev_alloc_zero(4);
+    {
+      ProfileScope ps("run_heads_count", (uint64_t)n_valid * 8, (uint64_t)n_valid);
+      hipLaunchKernelGGL(run_heads_count_kernel, dim3(k::grid_for(n_valid, kBlock * 8, 4)), dim3(kBlock), 0, stream(), sorted->as<uint64_t>(), n_valid, cnt->as<unsigned int>());
+      PLX_HIP(hipGetLastError());
+    }
+    d2h_sync(&values, cnt->ptr, 4);
+  }
+  if (desc) *desc = "n_unique[sorted codes: passes=" + std::to_string(passes) + ", skipped=" + std::to_string(skipped) + "]";
+  return values + null_class;
+}
+
+ColumnPtr distinct_rows(const std::vector<ColumnPtr>& keys, int keep, int64_t* kept, std::string* sort_desc) {
+  PLX_REQUIRE(distinct::keep_ok(keep), PLX_ERR_INVALID, "unique: keep " + std::to_string(keep) + " is no plx_unique_keep (0..3)");
+  PLX_REQUIRE(!keys.empty() && (int)keys.size() <= kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, "unique: the subset takes 1.." + std::to_string(kSegmentMaxKeys) + " columns, got " + std::to_string(keys.size()));
+  const int64_t n = keys[0]->len;
+  for (const ColumnPtr& kc : keys) {
+    PLX_REQUIRE(kc->len == n, PLX_ERR_SHAPE, "unique: subset columns have different lengths");
+    if (!(dtype_is_int(kc->dtype) || dtype_is_float(kc->dtype) || kc->dtype == PLX_BOOL)) fail(PLX_ERR_UNSUPPORTED, std::string("unique over a ") + dtype_name(kc->dtype) + " column: integer, float and Boolean columns only");
+    PLX_REQUIRE(kc->values || n == 0, PLX_ERR_INVALID, "placeholder column has no data");
+  }
+  auto out = std::make_shared<Column>();
+  out->dtype = PLX_BOOL; out->len = n; out->values = dev_alloc_zero(bitmap_bytes(n)); out->null_count = 0;
+  if (kept) *kept = 0;
+  if (n == 0) { if (sort_desc) *sort_desc = "sort[empty]"; return out; }
+  std::vector<SortKey> sk;
+  for (const ColumnPtr& kc : keys) { SortKey s; s.col = kc; s.nulls_last = true; sk.push_back(s); }
+  ColumnPtr perm = sort_indices(sk, -1, sort_desc);      // stable: the head of a segment is its first occurrence, the tail its last
+  SegKeys segk{};
+  segk.n = (int)keys.size();
+  for (size_t j = 0; j < keys.size(); j++) segk.k[j] = key_col(keys[j]);
+  Buf heads = dev_alloc(bitmap_bytes(n));
+  {
+    ProfileScope ps("segment_heads", (uint64_t)n * 4 + (uint64_t)n / 8, (uint64_t)n);
+    hipLaunchKernelGGL(segment_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), segk, perm->values->as<uint32_t>(), n, heads->as<uint64_t>());
+    PLX_HIP(hipGetLastError());
+  }
+  {
+    ProfileScope ps("distinct_keep", (uint64_t)n * 4 + (uint64_t)n / 4, (uint64_t)n);
+    hipLaunchKernelGGL(distinct_keep_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), heads->as<uint64_t>(), perm->values->as<uint32_t>(), n, distinct::keep_served(keep),
+                       out->values->as<unsigned int>());
+    PLX_HIP(hipGetLastError());
+  }
+  if (kept) *kept = k::bitmap_popcount(out->values->as<uint64_t>(), n);
   return out;
 }
 

@@ -4,6 +4,7 @@
 #include "variance.hpp"
 
 #include <cmath>
+#include <cstdlib>
 
 #include "kernels.hpp"
 #include "quantile.hpp"
@@ -348,6 +349,17 @@ ScalarValue reduce_quantile(const ColumnPtr& c, double q, int interpolation, std
   const double v = quantile::combine(quantile::decode(c->dtype, sel.code_lo), quantile::decode(c->dtype, sel.code_hi), rk.frac, interpolation);
   r.valid = true;
   if (r.dtype == PLX_F32) r.v.f32 = (float)v; else r.v.f64 = v;
+  return r;
+}
+
+// n_unique of a whole column (reference: ChunkUnique::n_unique, polars-core/src/chunked_array/ops/unique/mod.rs): the routes live beside the sort
+// (sort::n_unique_column), the switch that forces one is read at every call (the tests set it)
+ScalarValue reduce_n_unique(const ColumnPtr& c, std::string* desc) {
+  const char* e = getenv("PLX_NUNIQUE_ROUTE");
+  // "bitmap" asks for what the rule gives already (the bitmap route wherever it is legal): only "sort" changes a route
+  const bool force_sort = e && std::string(e) == "sort";
+  ScalarValue r; r.v.u = 0; r.valid = true; r.dtype = PLX_U32;
+  r.v.u = sort::n_unique_column(c, force_sort, desc);
   return r;
 }
 

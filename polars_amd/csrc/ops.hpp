@@ -36,6 +36,10 @@ ScalarValue reduce_var(const ColumnPtr& c, int ddof, bool want_std);
 // quantile q in [0, 1] of the valid rows with a plx_quantile_interpolation (the median: 0.5, linear): Float64 (Float32 for a Float32 column), null without a valid
 // row; *desc (may be null) names the radix select's rounds
 ScalarValue reduce_quantile(const ColumnPtr& c, double q, int interpolation, std::string* desc);
+// the number of distinct values, a null counting as one: UInt32, never null, 0 for an empty column (integer, float and Boolean columns); *desc (may be null) names
+// the route.  PLX_NUNIQUE_ROUTE=sort in the environment forces the sorted-codes route (tests, measurement); =bitmap is accepted and is the default rule,
+// which takes the bitmap route wherever it is legal
+ScalarValue reduce_n_unique(const ColumnPtr& c, std::string* desc);
 ColumnPtr scalar_column(const ScalarValue& s);                 // length-1 column
 ColumnPtr full_column(int dtype, plx_scalar v, bool valid, int64_t len);  // broadcast literal
 ColumnPtr fill_null(const ColumnPtr& c, plx_scalar v);                     // valid ? value : literal (same dtype)

@@ -35,13 +35,38 @@ Buf sort_keys_u64(Buf keys, int64_t m, int first_digit, int* passes, int* skippe
 struct SelectedRanks { uint64_t code_lo = 0, code_hi = 0; };
 SelectedRanks select_ranks(const ColumnPtr& col, int64_t n_valid, uint64_t lo, uint64_t hi, std::string* desc);
 
-// Quantiles per group over sorted segments: one sort_indices(keys..., value; ascending, nulls last) whatever the number of (q, interpolation) pairs, the segment
-// heads found through the permutation (segment_heads_kernel) and compacted into starts[G], one lane per group picking two values (segment_quantile_kernel).  One
-// column per spec (Float64; Float32 for a Float32 value column; null for a group without a valid value), G rows in KEY-SORTED order -- the order of
-// sort_indices(group keys; ascending, nulls last).  G must equal expect_groups (PLX_ERR_INVALID naming both otherwise).
+// ---- sorted segments: what the grouped order statistics and the grouped distinct counts share ----
+// The sorted order of ONE source column under the group keys: one sort_indices(keys..., value; ascending, nulls last), the segment heads found through the
+// permutation (segment_heads_kernel) and compacted into starts[G].  The rows of a group are the positions [starts[g], starts[g + 1]) (the last segment ends at n),
+// its valid values in order in front of its nulls; the G segments come in KEY-SORTED order -- the order of sort_indices(group keys; ascending, nulls last).  G must
+// equal expect_groups (PLX_ERR_INVALID naming both otherwise).  Built once per distinct source column: `x.median(), x.n_unique()` run one sort.
 constexpr int kSegmentMaxKeys = 8;
+struct SortedSegments {
+  ColumnPtr value;        // the source column
+  ColumnPtr perm;         // PLX_U32[n]
+  Buf heads;              // the segment-head mask, bitmap_bytes(n) (null when n == 0)
+  Buf starts;             // u32[max(G, 1)]
+  int64_t n = 0, n_groups = 0;
+  std::string sort_desc;
+};
+SortedSegments sort_segments(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, int64_t expect_groups);
+// Quantiles per group: one lane per group picking two values (segment_quantile_kernel).  One column per spec (Float64; Float32 for a Float32 value column; null for
+// a group without a valid value), G rows in the segments' order.
 struct QuantileSpec { double q; int interpolation; };
-std::vector<ColumnPtr> segment_quantiles(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, const std::vector<QuantileSpec>& specs, int64_t expect_groups, std::string* sort_desc);
+std::vector<ColumnPtr> segment_quantiles(const SortedSegments& seg, const std::vector<QuantileSpec>& specs);
+// Distinct values per group, a null counting as one: distinct_heads_kernel marks the positions that start a segment or whose value differs from the position before
+// (null and value differ, two nulls do not), a per-word exclusive prefix of that mask's popcounts, and one lane per group taking the difference of two ranks
+// (segment_distinct_kernel: O(1) per group).  PLX_U32 without validity, G rows in the segments' order.
+ColumnPtr segment_distinct(const SortedSegments& seg);
+
+// ---- n_unique of a whole column / distinct rows (distinct.hpp holds the arithmetic) ----
+// The number of distinct values of `col` (integer, float or Boolean), a null counting as one.  *desc names the route: "n_unique[boolean]",
+// "n_unique[bitmap range=R]" or "n_unique[sorted codes: passes=P, skipped=S]".  The rule takes the bitmap route wherever it is legal, so the only route there is
+// to force is the sort's: force_sort sends an integer column that would take the bitmap through the sorted codes (Boolean and empty columns have one route).
+uint32_t n_unique_column(const ColumnPtr& col, bool force_sort, std::string* desc);
+// Row-order Boolean mask (no validity) of the rows unique(keep) keeps over 1..kSegmentMaxKeys key columns: one stable sort_indices over the keys, segment_heads_kernel,
+// distinct_keep_kernel.  *kept (may be null: no count, no synchronisation) = the number of set bits; *sort_desc = the sort's description.
+ColumnPtr distinct_rows(const std::vector<ColumnPtr>& keys, int keep, int64_t* kept, std::string* sort_desc);
 // inv[perm[i]] = i
 ColumnPtr invert_permutation(const ColumnPtr& perm);
 

@@ -115,6 +115,11 @@ class Expr:
         """quantile(0.5, "linear")."""
         return Expr("agg", F.AGG_QUANTILE, self, value=(0.5, "linear"))
 
+    def n_unique(self) -> "Expr":
+        """The number of distinct values, a null counting as one value of its own (py-polars expr.n_unique): UInt32, never null.  Values are equal by the sort's
+        equality (every NaN equals every NaN, -0 == +0).  Any integer, float, Boolean, Date / Datetime or Categorical expression."""
+        return Expr("agg", F.AGG_N_UNIQUE, self)
+
     # -- misc -----------------------------------------------------------------------------
     @property
     def str(self) -> "ExprStringNameSpace":
@@ -136,6 +141,7 @@ class Expr:
         if self.kind == "agg" and self.op in (F.AGG_VAR, F.AGG_STD): return f"{self.lhs!r}.{'var' if self.op == F.AGG_VAR else 'std'}(ddof={self.value})"
         if self.kind == "agg" and self.op == F.AGG_QUANTILE:
             return f"{self.lhs!r}.median()" if self.value == (0.5, "linear") else f"{self.lhs!r}.quantile({self.value[0]!r}, {self.value[1]!r})"
+        if self.kind == "agg" and self.op == F.AGG_N_UNIQUE: return f"{self.lhs!r}.n_unique()"
         if self.kind == "agg": return f"{self.lhs!r}.agg{self.op}()"
         if self.kind == "alias": return f"{self.lhs!r}.alias({self.name!r})"
         if self.kind == "cast": return f"{self.lhs!r}.cast({self.dtype})"
@@ -164,6 +170,13 @@ def check_quantile(q: Any) -> float:
     if isinstance(q, (bool, np.bool_)) or not isinstance(q, (int, float, np.integer, np.floating)) or not 0.0 <= float(q) <= 1.0:
         raise ValueError(f"quantile takes a real number in [0, 1], got {q!r}")
     return float(q)
+
+
+def check_keep(keep: Any) -> str:
+    """The keep strategy of unique(): one of "any", "first", "last", "none"."""
+    if not isinstance(keep, str) or keep not in F.UNIQUE_KEEPS:
+        raise ValueError(f"keep must be one of {list(F.UNIQUE_KEEPS)}, got {keep!r}")
+    return keep
 
 
 def check_interpolation(interpolation: Any) -> str:
@@ -357,6 +370,10 @@ def median(name: str) -> Expr:
 
 def quantile(name: str, quantile: float, interpolation: str = "nearest") -> Expr:  # noqa: A002
     return col(name).quantile(quantile, interpolation)
+
+
+def n_unique(name: str) -> Expr:
+    return col(name).n_unique()
 
 
 _EPOCH = _dt.date(1970, 1, 1)

@@ -431,6 +431,26 @@ class Series:
         """quantile(0.5, "linear")."""
         return self.quantile(0.5, "linear")
 
+    def n_unique(self) -> int:
+        """The number of distinct values, a null counting as one (Series.n_unique); 0 for an empty column.  `last_plan()` names the route: two popcounts for a
+        Boolean column, a bitmap over the value range for integers of a small range, a key-only sort of the value codes otherwise."""
+        F.ensure_init()
+        F.set_plan_note(None)
+        out = C.c_uint32()
+        F.check(F.lib().plx_reduce_n_unique(self._h, C.byref(out)))
+        return int(out.value)
+
+    def unique(self, maintain_order: bool = False) -> "Series":
+        """The distinct values in first-occurrence order (Series.unique): plx_distinct_mask plus a filter, so both values of `maintain_order` get row order."""
+        F.ensure_init()
+        F.set_plan_note(None)
+        keys, h = (C.c_uint64 * 1)(self._h), C.c_uint64()
+        F.check(F.lib().plx_distinct_mask(keys, 1, F.UNIQUE_FIRST, C.byref(h)))
+        plan = F.last_plan()
+        out = self.filter(Series._from_handle("", h.value, T.Boolean))
+        F.set_plan_note(plan)
+        return out
+
     @property
     def str(self) -> "SeriesStringNameSpace":
         """String predicates (starts_with / ends_with / contains of a literal) on a dictionary column or on a column of raw views."""
@@ -760,6 +780,9 @@ class DataFrame:
     def drop(self, *columns) -> "DataFrame":
         return self.lazy().drop(*columns).collect()
 
+    def unique(self, subset=None, *, keep: str = "any", maintain_order: bool = False) -> "DataFrame":
+        return self.lazy().unique(subset, keep=keep, maintain_order=maintain_order).collect()
+
     def rename(self, mapping: Dict[str, str]) -> "DataFrame":
         return self.lazy().rename(mapping).collect()
 
@@ -953,6 +976,19 @@ class LazyFrame:
             raise KeyError(f"column not found: {sorted(missing)[0]}")
         return self.select(*[_col(n).alias(mapping[n]) if n in mapping else _col(n) for n in have])
 
+    def unique(self, subset=None, *, keep: str = "any", maintain_order: bool = False) -> "LazyFrame":
+        """The rows that are distinct over `subset` (a name, a list of names, None = all columns; 1..8 columns) -- LazyFrame.unique.  keep: "first" / "last" keep
+        the first / last row of every class of equal rows in row order, "none" only the rows of classes of one row, "any" is served as "first".  Rows are equal
+        when every subset column is equal by the sort's equality (null == null, NaN == NaN, -0 == +0).  The result is always in the input's row order, so
+        maintain_order=True is honoured and False loses nothing."""
+        from .expr import check_keep
+        keep = check_keep(keep)
+        if subset is not None:
+            subset = [subset] if isinstance(subset, str) else list(subset)
+            if not subset or not all(isinstance(x, str) for x in subset):
+                raise ValueError(f"subset must be a column name, a non-empty list of column names or None, got {subset!r}")
+        return LazyFrame(P.Node("unique", input=self._node, subset=subset, keep=keep, maintain_order=bool(maintain_order)))
+
     def slice(self, offset: int, length: Optional[int] = None) -> "LazyFrame":
         if length is not None and length < 0:
             raise ValueError(f"negative slice lengths ({length!r}) are invalid for LazyFrame")
@@ -1031,6 +1067,7 @@ class LazyFrame:
         from . import io as _io
         lines = [F.last_plan()] if F._lib is not None and F.last_plan() else []
         lines += P.describe_join_orders(self._node)
+        lines += P.describe_distincts(self._node)
         if _io.has_file_scan(self._node):
             self._lower()
             lines += _io.describe_scans(self._node)
@@ -1156,3 +1193,4 @@ class GroupBy:
     def max(self): return self._all("max")
     def count(self): return self._all("count")
     def median(self): return self._all("median")
+    def n_unique(self): return self._all("n_unique")

@@ -759,7 +759,7 @@ def output_names(n: P.Node) -> List[str]:
     k = n.kind
     if k == "scan":
         return list(n.frame.schema)
-    if k in ("filter", "sort", "slice"):
+    if k in ("filter", "sort", "slice", "unique"):
         return output_names(n.input)
     if k == "select":
         return [P.expr_output_name(e) for e in n.exprs]
@@ -860,6 +860,9 @@ def push_down(node: P.Node, needed: Optional[Set[str]] = None, preds: Optional[L
         return
     if k == "slice":
         push_down(node.input, needed, None, (int(node.offset), int(node.length)))
+        return
+    if k == "unique":          # the subset is read whatever the plan above keeps; no subset: every column decides
+        push_down(node.input, None if (needed is None or node.subset is None) else needed | set(node.subset), None)
         return
     if k == "join":
         lnames, rnames = output_names(node.left), output_names(node.right)

@@ -58,6 +58,20 @@ def join_schema(how: str, coalesce, left_on, right_on, ls: Schema, rs: Schema, s
     return out
 
 
+def describe_distincts(node: Node) -> List[str]:
+    """One line per unique() under `node` (LazyFrame.explain): the Distinct node as it is lowered."""
+    out: List[str] = []
+    for attr in ("input", "left", "right"):
+        child = getattr(node, attr, None)
+        if isinstance(child, Node):
+            out += describe_distincts(child)
+    if node.kind == "unique":
+        subset = "all columns" if node.subset is None else "[" + ", ".join(node.subset) + "]"
+        keep = "first (asked: any)" if node.keep == "any" else node.keep
+        out.append(f"Distinct[subset={subset}, keep={keep}, order=rows]")
+    return out
+
+
 def describe_join_orders(node: Node) -> List[str]:
     """One line per join under `node` that was asked to keep a row order (LazyFrame.explain)."""
     out: List[str] = []
@@ -189,7 +203,7 @@ class Lowering:
                 out = sum_dtype(dt)
             elif e.op == F.AGG_MEAN:
                 out = T.Float32 if dt == T.Float32 else T.Float64
-            elif e.op in (F.AGG_COUNT, F.AGG_LEN):
+            elif e.op in (F.AGG_COUNT, F.AGG_LEN, F.AGG_N_UNIQUE):      # n_unique: any operand dtype, nothing rides in the node
                 out = T.UInt32
             elif e.op in (F.AGG_VAR, F.AGG_STD):
                 what = "var" if e.op == F.AGG_VAR else "std"
@@ -473,6 +487,14 @@ class Lowering:
             keys = [self.lower_expr(e, schema)[0] for e in n.by]
             return push(kind=F.IR_SORT, input=inp, keys=keys, sort_descending=[int(bool(x)) for x in n.descending],
                         sort_nulls_last=[int(bool(x)) for x in n.nulls_last], maintain_order=int(n.maintain_order)), schema
+        if k == "unique":
+            inp, schema = self.lower_node(n.input)
+            names = list(schema) if n.subset is None else list(n.subset)
+            if n.keep not in F.UNIQUE_KEEPS:
+                raise ValueError(f"keep must be one of {list(F.UNIQUE_KEEPS)}, got {n.keep!r}")
+            keys = [self.lower_expr(Expr("col", name=name), schema)[0] for name in names]          # KeyError: column not found
+            # the keep strategy rides in the otherwise unread `how` slot of the node (plx_unique_keep); both values of maintain_order are served in row order
+            return push(kind=F.IR_DISTINCT, input=inp, keys=keys, how=F.UNIQUE_KEEPS[n.keep], maintain_order=int(bool(n.maintain_order))), schema
         if k == "slice":
             inp, schema = self.lower_node(n.input)
             offset = int(n.offset)

@@ -47,6 +47,14 @@ def h2o_median_sd(lf):
     return lf.group_by("id4", "id5").agg(E.col("v3").median().alias("v3_median"), E.col("v3").std().alias("v3_sd"))
 
 
+def lineitem_distinct(lineitem):
+    """group_by(l_returnflag, l_linestatus).agg(l_quantity.n_unique(), l_shipdate.n_unique(), len) -- the shape of TPC-H Q16's `count(distinct ps_suppkey)` over the
+    columns the lineitem generator has: distinct quantities and ship dates per flag and status.  The count of rows runs through the fused scan's cells, each distinct
+    count over the sorted segments of its source"""
+    return lineitem.group_by("l_returnflag", "l_linestatus").agg(E.col("l_quantity").n_unique().alias("n_quantities"), E.col("l_shipdate").n_unique().alias("n_shipdates"),
+                                                                  E.len().alias("count_order"))
+
+
 def q1(lineitem, cutoff=Q1_CUTOFF):
     """TPC-H Q1; the final sort by (flag, status) happens on the host."""
     c = E.col
