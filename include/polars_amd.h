@@ -377,6 +377,15 @@ int plx_groupby_agg_ddof(const plx_column* keys, int32_t n_keys, const plx_colum
 int plx_groupby_agg_params(const plx_column* keys, int32_t n_keys, const plx_column* values,
                            const plx_agg_op* aggs, int32_t n_aggs, int32_t maintain_order, const int32_t* ddof,
                            const double* q, const int32_t* interpolation, plx_column* out_keys, plx_column* out_aggs);
+/* Window aggregates (PLX_AE_WINDOW as a column call): aggregate i of `aggs` over values[i] per partition of the n_keys (1..8: more is PLX_ERR_UNSUPPORTED) key columns,
+ * given back on every row -- out_cols[i] has the height and row order of the keys, the dtype and validity the aggregate has in plx_groupby_agg_params.  keys, values,
+ * aggs, ddof, q and interpolation follow plx_groupby_agg_params (values[i] may be 0 for PLX_AGG_LEN; NULL ddof / q / interpolation: the defaults).  One group-by, one
+ * row -> group map and one broadcast launch per 8 outputs.  The map takes one of two routes, named by plx_last_plan_description(): "window[direct range=R]" (integer,
+ * Boolean, temporal and Categorical keys but PLX_U64 whose joint code range R keeps 4 R <= max(8 rows, 4 MiB): a table of R group ids) and "window[sorted rows: ...]"
+ * (everything else: one sort of the rows).  PLX_WINDOW_ROUTE=sort in the environment forces the sorted route (=direct is the default rule: the direct route wherever it
+ * is legal).  At most 2^32 - 2 rows. */
+int plx_window_agg(const plx_column* keys, int32_t n_keys, const plx_column* values, const plx_agg_op* aggs, int32_t n_aggs, const int32_t* ddof,
+                   const double* q, const int32_t* interpolation, plx_column* out_cols);
 /* Row-order Boolean mask (no nulls) of the rows that unique() keeps: the n_keys (1..8: more is PLX_ERR_UNSUPPORTED) key columns of integer, float or Boolean dtype
  * are sorted stably once, so the head of every run of equal rows is its first occurrence and the tail its last; keep is a plx_unique_keep (outside 0..3:
  * PLX_ERR_INVALID).  Two rows are equal when every key is equal by the sort's equality, null == null.  Filtering any column of the same height by the mask
@@ -441,11 +450,20 @@ typedef enum plx_aexpr_kind {
                            * the plan has run).  Result: Boolean, bit `value` of the bitmap, false outside [0, len(bitmap)), null where lhs is null: set membership over a
                            * dense code range.  Fused pipelines test the bit inside their scan (at most 2 bitmaps per program, semi-join membership bitmaps included; a
                            * plan that needs more runs per node), the per-node path with plx_bitmap_lookup's kernel.  Output name: that of lhs */
-  PLX_AE_TEMPORAL = 13    /* lhs = a Date (PLX_I32 days) or Datetime (PLX_I64 ticks) expression, op = the part (plx_temporal_part), lit.u = the unit (plx_time_unit).
+  PLX_AE_TEMPORAL = 13,   /* lhs = a Date (PLX_I32 days) or Datetime (PLX_I64 ticks) expression, op = the part (plx_temporal_part), lit.u = the unit (plx_time_unit).
                            * Result: the part in its own dtype (plx_temporal_part), null exactly where lhs is null.  Fused pipelines compute it inside their scan
                            * (OP_DATEPART), the per-node path with plx_temporal_part's kernel.  As a group key month, day, quarter, weekday, ordinal_day, hour, minute and
                            * second have a range known without a pass over the data; year and date take theirs from the operand column's range, which costs one min / max
                            * pass over that column (cached on it) when nobody knows it yet.  Output name: that of lhs */
+  PLX_AE_WINDOW = 14,     /* lhs = the function, rhs = arena index of the first PLX_AE_WINDOW_KEY link (Expr.over with mapping_strategy "group_to_rows").  The function reduces
+                           * to one value per partition: it holds at least one PLX_AE_AGG / PLX_AE_LEN and every column reference in it sits below one (anything else is
+                           * PLX_ERR_UNSUPPORTED: window functions that do not aggregate are not built).  Result: on every row the value of the row's partition, with that
+                           * value's validity, in the dtype the aggregate has in a group-by; height and row order are the input's.  Partitions form as group-by groups do
+                           * (a null key is a partition of its own, NaN == NaN, -0 == +0).  Legal in the expressions of PLX_IR_SELECT / PLX_IR_HSTACK and in the predicate
+                           * of PLX_IR_FILTER, anywhere inside them; in the keys or aggregates of a PLX_IR_GROUPBY it is PLX_ERR_INVALID.  Windows of one node that share
+                           * their key list run one group-by, one row -> group map and one broadcast; fused pipelines decline the kind by name.  Output name: that of lhs */
+  PLX_AE_WINDOW_KEY = 15  /* one link of a window's key list: lhs = a key expression (no aggregate inside: PLX_ERR_INVALID), rhs = the next link or -1.  1..8 links
+                           * (more is PLX_ERR_UNSUPPORTED).  A link anywhere but below a PLX_AE_WINDOW, and a window without a link, are PLX_ERR_INVALID at plan import */
 } plx_aexpr_kind;
 
 /* polars_plan::dsl::Operator subset */
@@ -865,6 +883,11 @@ void _polars_plugin_field_plx_median(const struct ArrowSchema* fields, size_t n_
 /* plx_n_unique (values): plx_reduce_n_unique; no kwargs; a length-1 result; the field is UInt32 under the input's name */
 void _polars_plugin_plx_n_unique(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
 void _polars_plugin_field_plx_n_unique(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
+/* plx_window_agg (values, key, key...): plx_window_agg of one aggregate; kwargs {"agg": "sum" | "mean" | "min" | "max" | "count" | "len" | "var" | "std" | "quantile" |
+ * "median" | "n_unique", "ddof": 0..255, "q": [0, 1], "interpolation": "nearest" | ...}; a result of the inputs' height; the field is the aggregate's group-by dtype
+ * under the first input's name */
+void _polars_plugin_plx_window_agg(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
+void _polars_plugin_field_plx_window_agg(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,8 @@ JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI, JOIN_FULL, JOIN_RIGHT = range(6)
 JOIN_COALESCE_DEFAULT, JOIN_COALESCE, JOIN_KEEP_BOTH = range(3)          # plx_ir.coalesce
 JOIN_ORDER_NONE, JOIN_ORDER_LEFT, JOIN_ORDER_RIGHT, JOIN_ORDER_LEFT_RIGHT, JOIN_ORDER_RIGHT_LEFT = range(5)   # plx_join_order
 AE_COLUMN, AE_LITERAL, AE_BINARY, AE_CAST, AE_AGG, AE_LEN, AE_ALIAS, AE_NOT, AE_IS_NULL, AE_IS_NOT_NULL, AE_FILL_NULL, AE_TERNARY, AE_BITMAP_LOOKUP, AE_TEMPORAL = range(14)
+AE_WINDOW, AE_WINDOW_KEY = 14, 15                                          # f.over(keys): lhs = the function, rhs = the first key link; a link: lhs = a key, rhs = the next link or -1
+WINDOW_MAX_KEYS = 8
 STR_STARTS_WITH, STR_ENDS_WITH, STR_CONTAINS = range(3)                 # plx_str_match_kind
 STR_MATCH_MAX_PATTERN = 64
 UNIT_DATE, UNIT_MS, UNIT_US, UNIT_NS = range(4)                          # plx_time_unit
@@ -209,6 +211,7 @@ SIGNATURES = {
     "plx_groupby_agg_ddof": (C.c_int, [_u64p, C.c_int32, _u64p, _i32p, C.c_int32, C.c_int32, _i32p, _u64p, _u64p]),
     "plx_reduce_quantile": (C.c_int, [C.c_uint64, C.c_double, C.c_int32, C.POINTER(Scalar), _i32p, _i32p]),
     "plx_groupby_agg_params": (C.c_int, [_u64p, C.c_int32, _u64p, _i32p, C.c_int32, C.c_int32, _i32p, C.POINTER(C.c_double), _i32p, _u64p, _u64p]),
+    "plx_window_agg": (C.c_int, [_u64p, C.c_int32, _u64p, _i32p, C.c_int32, _i32p, C.POINTER(C.c_double), _i32p, _u64p]),
     "plx_join_indices": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _u64p, _u64p]),
     "plx_datagen_lineitem_q1": (C.c_int, [C.c_int64, C.c_uint64, _u64p]),
     "plx_datagen_lineitem_q1_host": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

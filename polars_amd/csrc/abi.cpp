@@ -18,6 +18,7 @@
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
 #include "ops.hpp"
+#include "quantile.hpp"
 #include "scan.hpp"
 #include "sort.hpp"
 #include "strmatch.hpp"
@@ -418,6 +419,28 @@ int plx_groupby_agg_params(const plx_column* keys, int32_t n_keys, const plx_col
   t_plan_desc = d;
   for (int i = 0; i < n_keys; i++) out_keys[i] = register_column(ok[i]);
   for (int i = 0; i < n_aggs; i++) out_aggs[i] = register_column(oa[i]);
+  PLX_CATCH
+}
+
+int plx_window_agg(const plx_column* keys, int32_t n_keys, const plx_column* values, const plx_agg_op* aggs, int32_t n_aggs, const int32_t* ddof, const double* q,
+                   const int32_t* interpolation, plx_column* out_cols) {
+  PLX_TRY
+  PLX_REQUIRE(keys && n_keys >= 1 && n_aggs >= 1 && values && aggs && out_cols, PLX_ERR_INVALID, "window_agg: need at least one key column and one aggregate");
+  std::vector<ColumnPtr> k, v, oc;
+  std::vector<int> a;
+  std::vector<engine::AggParams> ap;
+  for (int i = 0; i < n_keys; i++) k.push_back(get_column(keys[i]));
+  for (int i = 0; i < n_aggs; i++) {
+    engine::AggParams p;
+    if (ddof) p.ddof = ddof[i];
+    if (q) p.q = q[i];
+    if (interpolation) p.interpolation = interpolation[i];
+    a.push_back(aggs[i]); ap.push_back(p); v.push_back((aggs[i] == PLX_AGG_LEN || values[i] == 0) ? nullptr : get_column(values[i]));
+  }
+  std::string d;
+  engine::window_columns(k, v, a, &ap, oc, &d);
+  t_plan_desc = d;
+  for (int i = 0; i < n_aggs; i++) out_cols[i] = register_column(oc[i]);
   PLX_CATCH
 }
 
@@ -830,6 +853,73 @@ void _polars_plugin_plx_n_unique(PLX_PLUGIN_SIG) {
   plugin_call(inputs, n_inputs, out, ctx, 1, [&](std::vector<PluginInput>& in) { return ops::scalar_column(ops::reduce_n_unique(in[0].col, nullptr)); });
 }
 void _polars_plugin_field_plx_n_unique(PLX_FIELD_SIG) { (void)kwargs; (void)kwargs_len; plugin_field(fields, n_fields, out, FIELD_U32, 0); }
+// an aggregate of the first series over the partitions of the others, given back on every row (plx_window_agg): kwargs {"agg": name, "ddof": 0..255, "q": [0, 1],
+// "interpolation": name}, read like those of plx_var / plx_n_unique; a result of the inputs' height under the first input's name
+extern "C++" {
+namespace {
+int window_agg_of(const std::string& s) {
+  static const char* names[] = {"sum", "mean", "min", "max", "count", "len", "first", "var", "std", "quantile", "n_unique"};
+  if (s == "median") return PLX_AGG_QUANTILE;
+  for (int i = 0; i < 11; i++) if (s == names[i] && i != PLX_AGG_FIRST) return i;
+  return -1;
+}
+// value of a float-valued key in a pickled dict: the key's str token, an optional memo op, then BINFLOAT ('G', 8 bytes big-endian); an integer value counts too
+double pickle_float_value(const uint8_t* kw, size_t n, const char* key, double absent) {
+  const size_t klen = strlen(key);
+  for (size_t i = 0; i + 2 + klen <= n; i++) {
+    if (!((kw[i] == 0x8c || kw[i] == 'U') && kw[i + 1] == klen && !memcmp(kw + i + 2, key, klen))) continue;
+    size_t j = i + 2 + klen;
+    if (j < n && kw[j] == 0x94) j += 1; else if (j < n && kw[j] == 'q') j += 2; else if (j < n && kw[j] == 'r') j += 5;
+    if (j + 8 < n && kw[j] == 'G') {
+      uint64_t bits = 0;
+      for (int b = 0; b < 8; b++) bits = (bits << 8) | kw[j + 1 + b];
+      double v; memcpy(&v, &bits, 8);
+      return v;
+    }
+    return (double)pickle_int_value(kw, n, key, -1);
+  }
+  return absent;
+}
+FieldRule window_field_rule(int agg) {
+  switch (agg) {
+    case PLX_AGG_SUM: return FIELD_SUM;
+    case PLX_AGG_MEAN: case PLX_AGG_VAR: case PLX_AGG_STD: case PLX_AGG_QUANTILE: return FIELD_MEAN;
+    case PLX_AGG_COUNT: case PLX_AGG_LEN: case PLX_AGG_N_UNIQUE: return FIELD_U32;
+    default: return FIELD_SAME;
+  }
+}
+}  // namespace
+}  // extern "C++"
+void _polars_plugin_plx_window_agg(PLX_PLUGIN_SIG) {
+  const std::string name = pickle_str_value(kwargs, kwargs_len, "agg");
+  const int agg = window_agg_of(name);
+  const long long ddof = pickle_int_value(kwargs, kwargs_len, "ddof", 1);
+  const double q = name == "median" ? 0.5 : pickle_float_value(kwargs, kwargs_len, "q", 0.5);
+  const std::string ip = pickle_str_value(kwargs, kwargs_len, "interpolation");
+  plugin_call(inputs, n_inputs, out, ctx, n_inputs, [&](std::vector<PluginInput>& in) {
+    PLX_REQUIRE(agg >= 0, PLX_ERR_INVALID, "plx_window_agg: kwargs must carry agg in {sum, mean, min, max, count, len, var, std, quantile, median, n_unique}");
+    PLX_REQUIRE(in.size() >= 2, PLX_ERR_INVALID, "plx_window_agg: the value series, then 1..8 key series");
+    PLX_REQUIRE(ddof >= 0 && ddof <= 255, PLX_ERR_INVALID, "plx_window_agg: kwargs ddof must be an integer 0..255");
+    PLX_REQUIRE(quantile::q_ok(q), PLX_ERR_INVALID, "plx_window_agg: kwargs q must be a real number in [0, 1]");
+    static const char* ips[] = {"nearest", "lower", "higher", "midpoint", "linear"};
+    int interpolation = name == "median" || ip.empty() ? PLX_QUANTILE_LINEAR : -1;
+    for (int i = 0; i < 5; i++) if (ip == ips[i] && name != "median") interpolation = i;
+    PLX_REQUIRE(interpolation >= 0, PLX_ERR_INVALID, "plx_window_agg: kwargs interpolation must be one of nearest, lower, higher, midpoint, linear");
+    std::vector<ColumnPtr> cols;
+    for (PluginInput& x : in) cols.push_back(x.col ? x.col : ops::full_column(x.dtype, x.scalar, x.scalar_valid, 1));      // (a frame of one row: every series is a literal)
+    std::vector<ColumnPtr> keys(cols.begin() + 1, cols.end()), oc;
+    std::vector<engine::AggParams> ap(1);
+    ap[0].ddof = (int)ddof; ap[0].q = q; ap[0].interpolation = interpolation;
+    engine::window_columns(keys, {cols[0]}, {agg}, &ap, oc, nullptr);
+    return oc[0];
+  });
+}
+void _polars_plugin_field_plx_window_agg(PLX_FIELD_SIG) {
+  const std::string name = pickle_str_value(kwargs, kwargs_len, "agg");
+  const int agg = window_agg_of(name);
+  if (agg < 0) { t_plugin_error = "plx_window_agg: kwargs must carry agg in {sum, mean, min, max, count, len, var, std, quantile, median, n_unique}"; if (out) out->release = nullptr; return; }
+  plugin_field(fields, n_fields, out, window_field_rule(agg), 0);
+}
 void _polars_plugin_plx_filter(PLX_PLUGIN_SIG) {
   (void)kwargs; (void)kwargs_len;
   plugin_call(inputs, n_inputs, out, ctx, 2, [&](std::vector<PluginInput>& in) {

@@ -66,7 +66,25 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       PLX_REQUIRE(e.lhs >= 0 && quantile::q_ok(e.lit.f64) && quantile::interpolation_ok(e.dtype), PLX_ERR_INVALID,
                   "quantile: the node carries q in [0, 1] in lit.f64 and a plx_quantile_interpolation 0..4 in its dtype slot, got q=" + std::to_string(e.lit.f64) + ", interpolation=" + std::to_string(e.dtype));
     PLX_REQUIRE(e.lhs < i && e.rhs < i && e.cond < i, PLX_ERR_INVALID, "AExpr arena must be topologically ordered (children before parents)");
+    if (e.kind == PLX_AE_WINDOW_KEY) {
+      PLX_REQUIRE(e.lhs >= 0, PLX_ERR_INVALID, "window key link needs a key expression (lhs)");
+      PLX_REQUIRE(e.rhs < 0 || ae[e.rhs].kind == PLX_AE_WINDOW_KEY, PLX_ERR_INVALID, "window key link: rhs must be the next link or -1");
+    }
+    if (e.kind == PLX_AE_WINDOW) {
+      PLX_REQUIRE(e.lhs >= 0, PLX_ERR_INVALID, "window expression needs a function (lhs)");
+      PLX_REQUIRE(e.rhs >= 0 && ae[e.rhs].kind == PLX_AE_WINDOW_KEY, PLX_ERR_INVALID, "window expression without a key: rhs must be the first PLX_AE_WINDOW_KEY link");
+      int n_links = 0;
+      for (int l = e.rhs; l >= 0; l = ae[l].rhs) n_links++;
+      PLX_REQUIRE(n_links <= window::kMaxKeys, PLX_ERR_UNSUPPORTED, "window over " + std::to_string(n_links) + " keys; a window takes 1.." + std::to_string(window::kMaxKeys) + " keys on this path");
+    }
     p.ae.push_back(std::move(e));
+  }
+  // a key link stands below a window (as its rhs) or below another link (as its rhs), nowhere else
+  for (int i = 0; i < n_ae; i++) {
+    const AE& e = p.ae[i];
+    auto is_link = [&](int c) { return c >= 0 && p.ae[c].kind == PLX_AE_WINDOW_KEY; };
+    const bool takes_links = e.kind == PLX_AE_WINDOW || e.kind == PLX_AE_WINDOW_KEY;
+    PLX_REQUIRE(!is_link(e.lhs) && !is_link(e.cond) && (takes_links || !is_link(e.rhs)), PLX_ERR_INVALID, "window key link outside a window expression's key list");
   }
   for (int i = 0; i < n_ir; i++) {
     IRN n;
@@ -106,6 +124,16 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
     for (int e : n.keys) chk(e);
     for (int e : n.keys_right) chk(e);
     if (n.kind == PLX_IR_FILTER) chk(n.predicate);
+    auto no_link = [&](int e) { PLX_REQUIRE(e < 0 || p.ae[e].kind != PLX_AE_WINDOW_KEY, PLX_ERR_INVALID, "window key link outside a window expression's key list"); };
+    for (int e : n.exprs) no_link(e);
+    for (int e : n.keys) no_link(e);
+    for (int e : n.keys_right) no_link(e);
+    no_link(n.predicate);
+    if (n.kind == PLX_IR_GROUPBY) {
+      std::function<bool(int)> has_window = [&](int e) { return e >= 0 && (p.ae[e].kind == PLX_AE_WINDOW || has_window(p.ae[e].lhs) || has_window(p.ae[e].rhs) || has_window(p.ae[e].cond)); };
+      for (int e : n.keys) PLX_REQUIRE(!has_window(e), PLX_ERR_INVALID, "group_by: a window expression (.over) cannot stand in the keys of a group_by");
+      for (int e : n.exprs) PLX_REQUIRE(!has_window(e), PLX_ERR_INVALID, "group_by: a window expression (.over) cannot stand in the aggregate list of a group_by; aggregate first, or use the window in select / with_columns");
+    }
     PLX_REQUIRE(n.input < i && n.input_right < i, PLX_ERR_INVALID, "IR arena must be topologically ordered (inputs before consumers)");
     p.ir.push_back(std::move(n));
   }
@@ -157,6 +185,7 @@ int infer_dtype(const Plan& plan, int e, const Frame& schema) {
       return l;
     }
     case PLX_AE_LEN: return PLX_U32;
+    case PLX_AE_WINDOW: return infer_dtype(plan, x.lhs, schema);      // the dtype the function has in a group-by
     case PLX_AE_AGG: {
       int in = infer_dtype(plan, x.lhs, schema);
       switch (x.op) {
@@ -194,15 +223,24 @@ std::string output_name(const Plan& plan, int e) {
   }
 }
 
+// A window (PLX_AE_WINDOW) is a row-level value to everything around it: it does not reduce its node (no aggregate), it reads columns (a column outside an
+// aggregate), and the aggregates inside it belong to its own group-by (collect_aggs stops at it).
 static bool contains_agg(const Plan& plan, int e) {
   if (e < 0) return false;
   const AE& x = plan.ae[e];
+  if (x.kind == PLX_AE_WINDOW) return false;
   if (x.kind == PLX_AE_AGG || x.kind == PLX_AE_LEN) return true;
   return contains_agg(plan, x.lhs) || contains_agg(plan, x.rhs) || contains_agg(plan, x.cond);
+}
+static bool contains_window(const Plan& plan, int e) {
+  if (e < 0) return false;
+  const AE& x = plan.ae[e];
+  return x.kind == PLX_AE_WINDOW || contains_window(plan, x.lhs) || contains_window(plan, x.rhs) || contains_window(plan, x.cond);
 }
 static bool contains_column_outside_agg(const Plan& plan, int e) {
   if (e < 0) return false;
   const AE& x = plan.ae[e];
+  if (x.kind == PLX_AE_WINDOW) return true;
   if (x.kind == PLX_AE_AGG || x.kind == PLX_AE_LEN) return false;
   if (x.kind == PLX_AE_COLUMN) return true;
   return contains_column_outside_agg(plan, x.lhs) || contains_column_outside_agg(plan, x.rhs) || contains_column_outside_agg(plan, x.cond);
@@ -216,6 +254,7 @@ static bool contains_column(const Plan& plan, int e) {
 static void collect_aggs(const Plan& plan, int e, std::vector<int>& out) {
   if (e < 0) return;
   const AE& x = plan.ae[e];
+  if (x.kind == PLX_AE_WINDOW) return;
   if (x.kind == PLX_AE_AGG || x.kind == PLX_AE_LEN) { if (std::find(out.begin(), out.end(), e) == out.end()) out.push_back(e); return; }
   collect_aggs(plan, x.lhs, out);
   collect_aggs(plan, x.rhs, out);
@@ -284,6 +323,9 @@ static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<i
       return {ops::if_then_else(p.col, a.col, b.col), p.scalar && a.scalar && b.scalar};
     }
     case PLX_AE_LEN: { ops::ScalarValue s; s.dtype = PLX_U32; s.valid = true; s.v.u = (uint32_t)df.height; return {ops::scalar_column(s), true}; }
+    // a window's column is finished before the node's expressions are evaluated (run_windows) and found in `overrides` above; one that is not there stands where no
+    // executor collects windows
+    case PLX_AE_WINDOW: fail(PLX_ERR_UNSUPPORTED, "window expression (.over): only the expressions of select / with_columns and the predicate of filter take one");
     case PLX_AE_AGG: {
       Evaluated c = eval(plan, x.lhs, df, overrides);
       if (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD) return {ops::scalar_column(ops::reduce_var(c.col, (int)x.lit.u, x.op == PLX_AGG_STD)), true};
@@ -570,6 +612,7 @@ class Compiler {
           default: throw Unsupported("operator inside a fused program");
         }
       }
+      case PLX_AE_WINDOW: case PLX_AE_WINDOW_KEY: throw Unsupported("window expression: per-node route");
       default: throw Unsupported("aggregation nested inside a row expression");
     }
   }
@@ -1735,6 +1778,7 @@ static int and_predicates(Compiler& c, const std::vector<int>& preds) {
 // Select(aggregations) over [Filter]* over `src`
 static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& preds, const FramePtr& src, FramePtr& out, Shape* shape_out, int* sid_out,
                          std::string* why, bool compile_only) {
+  for (int e : node.exprs) if (contains_window(plan, e)) { if (why) *why = "window expression: per-node route"; return false; }
   for (int e : node.exprs) if (!contains_agg(plan, e) || contains_column_outside_agg(plan, e)) { if (why) *why = "select mixes row expressions and aggregations"; return false; }
   // select(lit(2.5).sum()) aggregates a one-row literal (sum 2.5, count 1, whatever the filter keeps), as the per-node evaluator does: a fused program would
   // repeat the constant on every row it scans
@@ -1788,6 +1832,7 @@ static bool forget_assumed_bounds(const std::vector<ColumnPtr>& cols) {
 // GroupBy(keys, aggregations) over [Filter]* over `src`
 static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& preds, const FramePtr& src, FramePtr& out, Shape* shape_out, int* sid_out,
                           std::string* why, bool compile_only) {
+  for (int e : node.exprs) if (contains_window(plan, e)) { if (why) *why = "window expression: per-node route"; return false; }
   for (int e : node.exprs) if (!contains_agg(plan, e) || contains_column_outside_agg(plan, e)) { if (why) *why = "group_by aggregation list contains a non-aggregated column"; return false; }
   Compiler c(plan, *src);
   c.device_pivot = !compile_only;
@@ -2756,6 +2801,159 @@ static bool filter_phrase(Plan& plan, const std::vector<int>& preds, const Frame
   return true;
 }
 
+// ------------------------------------------------------------ window expressions ----
+// `f.over(keys)` (WindowExpr, mapping group_to_rows): the windows of a node's expression list are collected, bucketed by key list, and every bucket runs ONE
+// group-by with the union of its aggregates (groupby_columns: all eleven kinds, shared cells and sorted segments), evaluates each function over the group frame the
+// way exec_groupby_materialised evaluates an aggregate list, and sends the G-row columns back to the rows through one row -> group map and one broadcast
+// (kernels_window.hip).  eval() then finds the finished columns in the override map.  DESIGN.md 4.17.
+static void collect_windows(const Plan& plan, int e, std::vector<int>& out) {
+  if (e < 0) return;
+  const AE& x = plan.ae[e];
+  if (x.kind == PLX_AE_WINDOW) { if (std::find(out.begin(), out.end(), e) == out.end()) out.push_back(e); return; }
+  collect_windows(plan, x.lhs, out);
+  collect_windows(plan, x.rhs, out);
+  collect_windows(plan, x.cond, out);
+}
+// the same expression, node by node (the arena holds one copy per place an expression was written)
+static bool same_expr(const Plan& plan, int a, int b) {
+  if (a == b) return true;
+  if (a < 0 || b < 0) return false;
+  const AE &x = plan.ae[a], &y = plan.ae[b];
+  if (x.kind != y.kind || x.op != y.op || x.dtype != y.dtype || x.is_null != y.is_null || x.lit.u != y.lit.u || x.name != y.name || x.lut != y.lut) return false;
+  return same_expr(plan, x.lhs, y.lhs) && same_expr(plan, x.rhs, y.rhs) && same_expr(plan, x.cond, y.cond);
+}
+static std::vector<int> window_keys(const Plan& plan, int w) {
+  std::vector<int> keys;
+  for (int l = plan.ae[w].rhs; l >= 0; l = plan.ae[l].rhs) keys.push_back(plan.ae[l].lhs);
+  return keys;
+}
+// the group-by, the functions over the group frame, the map and the broadcast of one bucket: keys (N rows), values / aggs / params as groupby_columns takes them,
+// finish(oaggs, G) -> the G-row columns to send back.  *desc = "Window{...}"
+template <class Finish>
+static std::vector<ColumnPtr> window_bucket(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, const std::vector<AggParams>& params,
+                                            const std::string& key_names, Finish&& finish, std::string* desc) {
+  std::vector<ColumnPtr> okeys, oaggs;
+  std::string gd;
+  groupby_columns(keys, values, aggs, false, okeys, oaggs, &gd, &params);
+  const int64_t G = okeys.empty() ? 0 : okeys[0]->len;
+  std::vector<ColumnPtr> gcols = finish(oaggs, G);
+  const window::RowMap map = window::map_rows(keys, okeys);
+  std::vector<ColumnPtr> out = window::broadcast(map, gcols);
+  if (desc) *desc = "Window{keys=[" + key_names + "], aggs=" + std::to_string(aggs.size()) + ", groups=" + std::to_string(G) + ", rows=" + std::to_string(keys[0]->len) + ", route=" + map.desc + "; " + gd + "}; ";
+  return out;
+}
+static ColumnPtr empty_column(int dtype) {
+  auto c = std::make_shared<Column>();
+  c->dtype = dtype; c->len = 0; c->null_count = 0; c->values = dev_alloc(values_bytes(dtype, 1) + 8);
+  return c;
+}
+static void run_windows(Plan& plan, const std::vector<int>& exprs, const Frame& in, std::map<int, ColumnPtr>& done) {
+  std::vector<int> wins;
+  for (int e : exprs) collect_windows(plan, e, wins);
+  if (wins.empty()) return;
+  struct Bucket { std::vector<int> keys, wins; };
+  std::vector<Bucket> buckets;
+  for (int w : wins) {
+    const int f = plan.ae[w].lhs;
+    const std::vector<int> keys = window_keys(plan, w);
+    PLX_REQUIRE(!contains_window(plan, f), PLX_ERR_UNSUPPORTED, "window expression: a window inside the function of another window is not built");
+    PLX_REQUIRE(contains_agg(plan, f) && !contains_column_outside_agg(plan, f), PLX_ERR_UNSUPPORTED,
+                "window expression over [" + output_name(plan, keys[0]) + (keys.size() > 1 ? ", ..." : "") + "]: its function does not reduce to one value per partition (a column outside an aggregate, or no aggregate at all); "
+                "window functions that do not aggregate (a bare column, cumulative and ranking functions) are not built");
+    for (int kx : keys) {
+      PLX_REQUIRE(!contains_window(plan, kx), PLX_ERR_INVALID, "window expression: a key that holds a window");
+      PLX_REQUIRE(!contains_agg(plan, kx), PLX_ERR_INVALID, "window expression: a key that holds an aggregate (" + output_name(plan, kx) + "); keys are row expressions");
+    }
+    Bucket* b = nullptr;
+    for (Bucket& c : buckets) {
+      bool same = c.keys.size() == keys.size();
+      for (size_t j = 0; same && j < keys.size(); j++) same = same_expr(plan, c.keys[j], keys[j]);
+      if (same) { b = &c; break; }
+    }
+    if (!b) { buckets.push_back(Bucket{keys, {}}); b = &buckets.back(); }
+    b->wins.push_back(w);
+  }
+  for (const Bucket& b : buckets) {
+    std::vector<ColumnPtr> keys, values;
+    std::vector<int> aggs, agg_nodes;
+    std::vector<AggParams> params;
+    std::map<int, ColumnPtr> by_expr;
+    std::string key_names;
+    for (int kx : b.keys) key_names += (key_names.empty() ? "" : ", ") + output_name(plan, kx);
+    for (int w : b.wins) collect_aggs(plan, plan.ae[w].lhs, agg_nodes);
+    if (in.height == 0) {      // an empty frame: an empty column of the function's dtype, the plan text in the shape of every other
+      for (int kx : b.keys) infer_dtype(plan, kx, in);      // (a key that names no column is still refused)
+      for (int w : b.wins) done[w] = empty_column(infer_dtype(plan, plan.ae[w].lhs, in));
+      plan.desc += "Window{keys=[" + key_names + "], aggs=" + std::to_string(agg_nodes.size()) + ", groups=0, rows=0, route=window[empty]}; ";
+      continue;
+    }
+    for (int kx : b.keys) keys.push_back(broadcast(eval(plan, kx, in, nullptr), in.height));
+    for (int a : agg_nodes) {
+      const AE& x = plan.ae[a];
+      AggParams ap;
+      if (x.kind == PLX_AE_AGG && (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD)) ap.ddof = (int)x.lit.u;
+      if (x.kind == PLX_AE_AGG && x.op == PLX_AGG_QUANTILE) { ap.q = x.lit.f64; ap.interpolation = x.dtype; }
+      params.push_back(ap);
+      if (x.kind == PLX_AE_LEN) { aggs.push_back(PLX_AGG_LEN); values.push_back(nullptr); continue; }
+      // one column per source expression, the same source written twice included: aggregates over one source share cells and sorted segments
+      ColumnPtr src;
+      for (auto& kv : by_expr) if (same_expr(plan, kv.first, x.lhs)) { src = kv.second; break; }
+      if (!src) src = by_expr.emplace(x.lhs, broadcast(eval(plan, x.lhs, in, nullptr), in.height)).first->second;
+      aggs.push_back(x.op); values.push_back(src);
+    }
+    flush_node_notes(plan);
+    std::string d;
+    std::vector<ColumnPtr> cols = window_bucket(keys, values, aggs, params, key_names, [&](const std::vector<ColumnPtr>& oaggs, int64_t G) {
+      std::map<int, ColumnPtr> overrides;
+      for (size_t i = 0; i < agg_nodes.size(); i++) overrides[agg_nodes[i]] = oaggs[i];
+      Frame gframe; gframe.height = G;
+      std::vector<ColumnPtr> g;
+      for (int w : b.wins) g.push_back(broadcast(eval(plan, plan.ae[w].lhs, gframe, &overrides), G));
+      return g;
+    }, &d);
+    for (size_t i = 0; i < b.wins.size(); i++) done[b.wins[i]] = cols[i];
+    plan.desc += d;
+  }
+}
+
+// plx_window_agg: one window per aggregate over the same key columns
+void window_columns(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, const std::vector<AggParams>* params,
+                    std::vector<ColumnPtr>& out_cols, std::string* desc) {
+  PLX_REQUIRE(!keys.empty(), PLX_ERR_INVALID, "window: need at least one key column");
+  PLX_REQUIRE((int)keys.size() <= window::kMaxKeys, PLX_ERR_UNSUPPORTED, "window over " + std::to_string(keys.size()) + " keys; a window takes 1.." + std::to_string(window::kMaxKeys) + " keys on this path");
+  PLX_REQUIRE(values.size() == aggs.size() && !aggs.empty(), PLX_ERR_INVALID, "window: values/aggs length mismatch");
+  const int64_t n = keys[0]->len;
+  for (auto& kc : keys) PLX_REQUIRE(kc->len == n, PLX_ERR_SHAPE, "window: key length mismatch");
+  for (auto& v : values) PLX_REQUIRE(!v || v->len == n, PLX_ERR_SHAPE, "window: value length mismatch");
+  PLX_REQUIRE(!params || params->size() == aggs.size(), PLX_ERR_INVALID, "window: params/aggs length mismatch");
+  std::vector<AggParams> ps = params ? *params : std::vector<AggParams>(aggs.size());
+  // the parameters are checked here, by name, whatever the height: an empty frame never reaches the group-by that checks them otherwise
+  for (size_t i = 0; i < aggs.size(); i++) {
+    PLX_REQUIRE(aggs[i] >= PLX_AGG_SUM && aggs[i] <= PLX_AGG_N_UNIQUE && aggs[i] != PLX_AGG_FIRST, PLX_ERR_INVALID, "window: aggregate " + std::to_string(aggs[i]) + " is no window aggregate (plx_agg_op but FIRST)");
+    if (aggs[i] == PLX_AGG_VAR || aggs[i] == PLX_AGG_STD) PLX_REQUIRE(ps[i].ddof >= 0 && ps[i].ddof <= 255, PLX_ERR_INVALID, "window: ddof must be 0..255");
+    if (aggs[i] == PLX_AGG_QUANTILE) {
+      PLX_REQUIRE(quantile::q_ok(ps[i].q), PLX_ERR_INVALID, "window: quantile q must be a real number in [0, 1], got " + std::to_string(ps[i].q));
+      PLX_REQUIRE(quantile::interpolation_ok(ps[i].interpolation), PLX_ERR_INVALID, "window: interpolation " + std::to_string(ps[i].interpolation) + " is no plx_quantile_interpolation (0..4)");
+    }
+  }
+  if (n == 0) {
+    for (size_t i = 0; i < aggs.size(); i++) {
+      const int in = values[i] ? values[i]->dtype : PLX_U32;
+      int dt = in;
+      switch (aggs[i]) {
+        case PLX_AGG_SUM: dt = sum_out_dtype(in); break;
+        case PLX_AGG_MEAN: case PLX_AGG_VAR: case PLX_AGG_STD: case PLX_AGG_QUANTILE: dt = in == PLX_F32 ? PLX_F32 : PLX_F64; break;
+        case PLX_AGG_COUNT: case PLX_AGG_LEN: case PLX_AGG_N_UNIQUE: dt = PLX_U32; break;
+        default: break;
+      }
+      out_cols.push_back(empty_column(dt));
+    }
+    if (desc) *desc = "Window{keys=[" + std::to_string(keys.size()) + " columns], aggs=" + std::to_string(aggs.size()) + ", groups=0, rows=0, route=window[empty]}; ";
+    return;
+  }
+  out_cols = window_bucket(keys, values, aggs, ps, std::to_string(keys.size()) + " columns", [](const std::vector<ColumnPtr>& oaggs, int64_t) { return oaggs; }, desc);
+}
+
 static FramePtr exec_filter(Plan& plan, const IRN& n) {
   if (!(plan.flags & PLX_PLAN_NO_FUSION)) {
     std::vector<int> preds;
@@ -2768,7 +2966,9 @@ static FramePtr exec_filter(Plan& plan, const IRN& n) {
     plan.memo[src_node] = src;
   }
   FramePtr in = exec_node(plan, n.input);
-  Evaluated m = eval(plan, n.predicate, *in, nullptr);
+  std::map<int, ColumnPtr> wins;
+  run_windows(plan, {n.predicate}, *in, wins);
+  Evaluated m = eval(plan, n.predicate, *in, wins.empty() ? nullptr : &wins);
   ColumnPtr mask = broadcast(m, in->height);
   PLX_REQUIRE(mask->dtype == PLX_BOOL, PLX_ERR_INVALID, "filter predicate must be boolean");
   auto pm = ops::prepare_mask(mask);
@@ -2785,7 +2985,9 @@ static FramePtr exec_select(Plan& plan, const IRN& n, bool hstack, FramePtr in_g
   auto out = std::make_shared<Frame>();
   std::vector<Evaluated> evs;
   bool all_scalar = true;
-  for (int e : n.exprs) { evs.push_back(eval(plan, e, *in, nullptr)); all_scalar = all_scalar && evs.back().scalar; }
+  std::map<int, ColumnPtr> wins;
+  run_windows(plan, n.exprs, *in, wins);
+  for (int e : n.exprs) { evs.push_back(eval(plan, e, *in, wins.empty() ? nullptr : &wins)); all_scalar = all_scalar && evs.back().scalar; }
   if (hstack) {
     *out = *in;
     for (size_t i = 0; i < n.exprs.size(); i++) {

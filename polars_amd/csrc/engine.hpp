@@ -66,6 +66,11 @@ struct AggParams { int ddof = 1; double q = 0.5; int interpolation = PLX_QUANTIL
 void groupby_columns(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, bool maintain_order,
                      std::vector<ColumnPtr>& out_keys, std::vector<ColumnPtr>& out_aggs, std::string* desc, const std::vector<AggParams>* params = nullptr);
 
+// window aggregates used by plx_window_agg (keys / values already columns): aggregate i over values[i] per partition of the keys, given back on every row.  One
+// groupby_columns, one row -> group map, one broadcast (the path a PLX_AE_WINDOW takes in select / with_columns / filter).  *desc = "Window{...}"
+void window_columns(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& values, const std::vector<int>& aggs, const std::vector<AggParams>* params,
+                    std::vector<ColumnPtr>& out_cols, std::string* desc);
+
 // compile-only entry used by tests: lowers `Filter*(pred) -> Select/GroupBy` rooted at
 // `root` and reports the fused shape (and whether an AOT specialisation matches)
 // without touching the GPU.  Returns false if the plan is not fusable.

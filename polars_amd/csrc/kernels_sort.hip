@@ -626,6 +626,18 @@ __global__ __launch_bounds__(kBlock) void segment_quantile_kernel(KeyCol v, cons
   }
 }
 
+// the segment-head mask of a sorted order (`perm`: a sort_indices of n >= 1 rows by `keys`): what sort_segments, distinct_rows and segment_head_ranks start from
+static Buf segment_heads_of(const std::vector<ColumnPtr>& keys, const ColumnPtr& perm, int64_t n) {
+  SegKeys segk{};
+  segk.n = (int)keys.size();
+  for (size_t j = 0; j < keys.size(); j++) segk.k[j] = key_col(keys[j]);
+  Buf heads = dev_alloc(bitmap_bytes(n));
+  ProfileScope ps("segment_heads", (uint64_t)n * 4 + (uint64_t)n / 8, (uint64_t)n);
+  hipLaunchKernelGGL(segment_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), segk, perm->values->as<uint32_t>(), n, heads->as<uint64_t>());
+  PLX_HIP(hipGetLastError());
+  return heads;
+}
+
 __global__ __launch_bounds__(kBlock) void invert_permutation_kernel(const uint32_t* __restrict__ perm, int64_t n, uint32_t* __restrict__ inv) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t p = perm[i];
@@ -654,15 +666,7 @@ SortedSegments sort_segments(const std::vector<ColumnPtr>& keys, const ColumnPtr
   seg.perm = sort_indices(sk, -1, &seg.sort_desc);
   seg.starts = dev_alloc(4);
   if (n) {
-    SegKeys segk{};
-    segk.n = (int)keys.size();
-    for (size_t j = 0; j < keys.size(); j++) segk.k[j] = key_col(keys[j]);
-    seg.heads = dev_alloc(bitmap_bytes(n));
-    {
-      ProfileScope ps("segment_heads", (uint64_t)n * 4 + (uint64_t)n / 8, (uint64_t)n);
-      hipLaunchKernelGGL(segment_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), segk, seg.perm->values->as<uint32_t>(), n, seg.heads->as<uint64_t>());
-      PLX_HIP(hipGetLastError());
-    }
+    seg.heads = segment_heads_of(keys, seg.perm, n);
     k::FilterPlan fp = k::filter_prepare(seg.heads->as<uint64_t>(), n);
     seg.n_groups = fp.n_out;
     PLX_REQUIRE(seg.n_groups == expect_groups, PLX_ERR_INVALID, "sorted segments: segment count mismatch (" + std::to_string(seg.n_groups) + " segments, " + std::to_string(expect_groups) + " groups)");
@@ -800,21 +804,27 @@ __global__ __launch_bounds__(kBlock) void distinct_keep_kernel(const uint64_t* _
   }
 }
 
+// the exclusive prefix of a mask's per-word popcounts (words + 1 entries, the last the total): what distinct::rank_before reads
+static Buf mask_rank_prefix(const Buf& mask, int64_t n_bits) {
+  const int64_t nwords = (n_bits + 63) >> 6;
+  Buf counts = dev_alloc((size_t)nwords * 4), prefix = dev_alloc(((size_t)nwords + 1) * 8);
+  hipLaunchKernelGGL(mask_word_counts_kernel, dim3(k::grid_for(nwords, kBlock * 4)), dim3(kBlock), 0, stream(), mask->as<uint64_t>(), n_bits, counts->as<uint32_t>());
+  PLX_HIP(hipGetLastError());
+  k::exclusive_scan_u32(counts->as<uint32_t>(), prefix->as<uint64_t>(), nwords);
+  return prefix;
+}
+
 ColumnPtr segment_distinct(const SortedSegments& seg) {
   const int64_t n = seg.n, n_groups = seg.n_groups;
   ColumnPtr out = make_idx(n_groups);
   if (!n_groups) return out;
-  const int64_t nwords = (n + 63) >> 6;
   Buf mask = dev_alloc(bitmap_bytes(n));
   {
     ProfileScope ps("distinct_heads", (uint64_t)n * (4 + (dtype_width(seg.value->dtype) ? dtype_width(seg.value->dtype) : 1)) + (uint64_t)n / 4, (uint64_t)n);
     hipLaunchKernelGGL(distinct_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), key_col(seg.value), seg.perm->values->as<uint32_t>(), seg.heads->as<uint64_t>(), n, mask->as<uint64_t>());
     PLX_HIP(hipGetLastError());
   }
-  Buf counts = dev_alloc((size_t)nwords * 4), prefix = dev_alloc(((size_t)nwords + 1) * 8);
-  hipLaunchKernelGGL(mask_word_counts_kernel, dim3(k::grid_for(nwords, kBlock * 4)), dim3(kBlock), 0, stream(), mask->as<uint64_t>(), n, counts->as<uint32_t>());
-  PLX_HIP(hipGetLastError());
-  k::exclusive_scan_u32(counts->as<uint32_t>(), prefix->as<uint64_t>(), nwords);
+  Buf prefix = mask_rank_prefix(mask, n);
   {
     ProfileScope ps("segment_distinct", (uint64_t)n_groups * 44, (uint64_t)n_groups);
     hipLaunchKernelGGL(segment_distinct_kernel, dim3(k::grid_for(n_groups, kBlock)), dim3(kBlock), 0, stream(), mask->as<uint64_t>(), prefix->as<uint64_t>(), seg.starts->as<uint32_t>(), n_groups, n,
@@ -899,15 +909,7 @@ ColumnPtr distinct_rows(const std::vector<ColumnPtr>& keys, int keep, int64_t* k
   std::vector<SortKey> sk;
   for (const ColumnPtr& kc : keys) { SortKey s; s.col = kc; s.nulls_last = true; sk.push_back(s); }
   ColumnPtr perm = sort_indices(sk, -1, sort_desc);      // stable: the head of a segment is its first occurrence, the tail its last
-  SegKeys segk{};
-  segk.n = (int)keys.size();
-  for (size_t j = 0; j < keys.size(); j++) segk.k[j] = key_col(keys[j]);
-  Buf heads = dev_alloc(bitmap_bytes(n));
-  {
-    ProfileScope ps("segment_heads", (uint64_t)n * 4 + (uint64_t)n / 8, (uint64_t)n);
-    hipLaunchKernelGGL(segment_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), segk, perm->values->as<uint32_t>(), n, heads->as<uint64_t>());
-    PLX_HIP(hipGetLastError());
-  }
+  Buf heads = segment_heads_of(keys, perm, n);
   {
     ProfileScope ps("distinct_keep", (uint64_t)n * 4 + (uint64_t)n / 4, (uint64_t)n);
     hipLaunchKernelGGL(distinct_keep_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), heads->as<uint64_t>(), perm->values->as<uint32_t>(), n, distinct::keep_served(keep),
@@ -916,6 +918,21 @@ ColumnPtr distinct_rows(const std::vector<ColumnPtr>& keys, int keep, int64_t* k
   }
   if (kept) *kept = k::bitmap_popcount(out->values->as<uint64_t>(), n);
   return out;
+}
+
+HeadRanks segment_head_ranks(const std::vector<ColumnPtr>& keys, const ColumnPtr& perm) {
+  PLX_REQUIRE(!keys.empty() && (int)keys.size() <= kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, "sorted segments: 1.." + std::to_string(kSegmentMaxKeys) + " key columns, got " + std::to_string(keys.size()));
+  const int64_t n = perm->len;
+  PLX_REQUIRE(n > 0 && perm->dtype == PLX_U32 && !perm->validity, PLX_ERR_INVALID, "segment heads: a u32 permutation of at least one row");
+  for (const ColumnPtr& kc : keys) PLX_REQUIRE(kc->len == n, PLX_ERR_SHAPE, "segment heads: key length mismatch");
+  HeadRanks hr;
+  const int64_t nwords = (n + 63) >> 6;
+  hr.heads = segment_heads_of(keys, perm, n);
+  hr.prefix = mask_rank_prefix(hr.heads, n);
+  uint64_t total = 0;
+  d2h_sync(&total, hr.prefix->as<uint64_t>() + nwords, 8);
+  hr.n_segments = (int64_t)total;
+  return hr;
 }
 
 }  // namespace sort

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "core.hpp"
+#include "window.hpp"
 
 namespace plx {
 namespace sort {
@@ -69,6 +70,30 @@ uint32_t n_unique_column(const ColumnPtr& col, bool force_sort, std::string* des
 ColumnPtr distinct_rows(const std::vector<ColumnPtr>& keys, int keep, int64_t* kept, std::string* sort_desc);
 // inv[perm[i]] = i
 ColumnPtr invert_permutation(const ColumnPtr& perm);
+// The segments of a sorted order by themselves: the head mask of `perm` (a sort_indices of all rows by `keys`; segment_heads_kernel), the exclusive prefix of its
+// per-word popcounts (words + 1 entries: what distinct::rank_before reads) and the number of segments (one small download).  At least one row.
+struct HeadRanks { Buf heads, prefix; int64_t n_segments = 0; };
+HeadRanks segment_head_ranks(const std::vector<ColumnPtr>& keys, const ColumnPtr& perm);
 
 }  // namespace sort
+
+// ---- window expressions: the way back from a group frame to the rows (kernels_window.hip; window.hpp holds the arithmetic) ----
+namespace window {
+// The map row -> group of `keys` (N rows) against the keys of their group frame (G rows, any order).  direct: `table` = slot[R], read at the row's key code;
+// sorted: `table` = gid[N].  desc = "window[direct range=R]" | "window[sorted rows: <sort description>]" | "window[empty]".  PLX_WINDOW_ROUTE=sort in the environment
+// forces the sorted route.  On the sorted route the number of segments must be G (PLX_ERR_INVALID naming both otherwise).
+struct RowMap {
+  bool direct = false;
+  int64_t n = 0, n_groups = 0;
+  Keys keys{};                       // direct: the key parts of the rows
+  std::vector<ColumnPtr> key_cols;   // ... and the columns they point into
+  Buf table, flag;
+  unsigned int* flag_ptr = nullptr;  // raised by a row or group without a place; read once by broadcast()
+  std::string desc;
+};
+RowMap map_rows(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>& group_keys);
+// One N-row column per G-row group column: row r holds the value and validity of its group (window_broadcast_kernel, one launch per kMaxOutputs columns).  A result
+// has a validity bitmap only when its group column holds a null.  PLX_ERR_INVALID when a row has no group.
+std::vector<ColumnPtr> broadcast(const RowMap& m, const std::vector<ColumnPtr>& group_cols);
+}  // namespace window
 }  // namespace plx

@@ -23,7 +23,7 @@ class Expr:
 
     def children(self):
         """The expressions this one reads, for walkers: lhs, rhs and a ternary's predicate."""
-        return [c for c in (self.lhs, self.rhs, self.cond) if c is not None]
+        return [c for c in (self.lhs, self.rhs, self.cond) if c is not None] + (list(self.value) if self.kind == "window" else [])
 
     # -- operators ---------------------------------------------------------------------
     def _bin(self, op: int, other: Any, swap: bool = False) -> "Expr":
@@ -120,6 +120,15 @@ class Expr:
         equality (every NaN equals every NaN, -0 == +0).  Any integer, float, Boolean, Date / Datetime or Categorical expression."""
         return Expr("agg", F.AGG_N_UNIQUE, self)
 
+    # -- windows --------------------------------------------------------------------------
+    def over(self, *partition_by: Any, order_by: Any = None, mapping_strategy: str = "group_to_rows") -> "Expr":
+        """The aggregate per partition of the keys, given back on every row (py-polars expr.over with mapping_strategy="group_to_rows"): height and row order stay
+        the frame's, row r holds the value of the partition of row r.  `self` must reduce to one value per partition (every column below an aggregate); 1..8 keys,
+        strings or expressions, given one by one or as one list.  Partitions form as group_by groups do (a null key is a partition of its own).  order_by and the
+        "join" / "explode" mappings are not built: they raise instead of being ignored."""
+        keys = check_over(partition_by, order_by, mapping_strategy)
+        return Expr("window", lhs=self, value=keys)
+
     # -- misc -----------------------------------------------------------------------------
     @property
     def str(self) -> "ExprStringNameSpace":
@@ -143,6 +152,7 @@ class Expr:
             return f"{self.lhs!r}.median()" if self.value == (0.5, "linear") else f"{self.lhs!r}.quantile({self.value[0]!r}, {self.value[1]!r})"
         if self.kind == "agg" and self.op == F.AGG_N_UNIQUE: return f"{self.lhs!r}.n_unique()"
         if self.kind == "agg": return f"{self.lhs!r}.agg{self.op}()"
+        if self.kind == "window": return f"{self.lhs!r}.over([{', '.join(repr(k) for k in self.value)}])"
         if self.kind == "alias": return f"{self.lhs!r}.alias({self.name!r})"
         if self.kind == "cast": return f"{self.lhs!r}.cast({self.dtype})"
         if self.kind == "not": return f"~{self.lhs!r}"
@@ -177,6 +187,30 @@ def check_keep(keep: Any) -> str:
     if not isinstance(keep, str) or keep not in F.UNIQUE_KEEPS:
         raise ValueError(f"keep must be one of {list(F.UNIQUE_KEEPS)}, got {keep!r}")
     return keep
+
+
+def check_over(partition_by: Any, order_by: Any = None, mapping_strategy: Any = "group_to_rows") -> tuple:
+    """The keys of Expr.over as a tuple of expressions: strings name columns, one list / tuple argument is the key list itself.  ValueError for no key, for a
+    mapping other than "group_to_rows" and for order_by (every aggregate here is order-insensitive; the argument is refused, not ignored); TypeError for a key
+    that is neither a string nor an expression."""
+    if mapping_strategy != "group_to_rows":
+        raise ValueError(f"over(mapping_strategy={mapping_strategy!r}): only 'group_to_rows' is on this path ('join' and 'explode' are not built)")
+    if order_by is not None:
+        raise ValueError("over(order_by=...): ordered windows are not built on this path (every aggregate here is order-insensitive)")
+    keys = list(partition_by)
+    if keys and not keys[1:] and isinstance(keys[0], (list, tuple)):      # (len is pl.len() in this module)
+        keys = list(keys[0])
+    if not keys:
+        raise ValueError("over() needs at least one partition key")
+    out = []
+    for k in keys:
+        if isinstance(k, str):
+            out.append(col(k))
+        elif isinstance(k, Expr):
+            out.append(k)
+        else:
+            raise TypeError(f"over(): a partition key is a column name or an expression, got {type(k).__name__}")
+    return tuple(out)
 
 
 def check_interpolation(interpolation: Any) -> str:

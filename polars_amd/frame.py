@@ -1068,6 +1068,7 @@ class LazyFrame:
         lines = [F.last_plan()] if F._lib is not None and F.last_plan() else []
         lines += P.describe_join_orders(self._node)
         lines += P.describe_distincts(self._node)
+        lines += P.describe_windows(self._node)
         if _io.has_file_scan(self._node):
             self._lower()
             lines += _io.describe_scans(self._node)

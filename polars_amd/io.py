@@ -809,6 +809,11 @@ def _row_preserving(exprs) -> bool:
     return all(walk(e) for e in exprs) and any(expr_columns(e) for e in exprs)
 
 
+def _has_window(e: Optional[Expr]) -> bool:
+    """a window expression (f.over(keys)) anywhere in `e`"""
+    return e is not None and (e.kind == "window" or any(_has_window(c) for c in e.children()))
+
+
 def scan_under(node: P.Node):
     """The file scan a Slice node's window reaches: through row-preserving select / with_columns nodes only."""
     while True:
@@ -831,6 +836,11 @@ def push_down(node: P.Node, needed: Optional[Set[str]] = None, preds: Optional[L
     if k == "filter":
         cols = expr_columns(node.predicate)
         below = preds if preds is not None else []
+        if _has_window(node.predicate):
+            # a window reads EVERY row of this filter's input: neither its own conjuncts nor the filters above it may drop a row group below it (a filter
+            # under it still prunes: those rows never reach the window)
+            push_down(node.input, None if needed is None else needed | cols, [])
+            return
         push_down(node.input, None if needed is None else needed | cols, below + simple_predicates(node.predicate))
         return
     if k == "select":

@@ -72,6 +72,27 @@ def describe_distincts(node: Node) -> List[str]:
     return out
 
 
+def describe_windows(node: Node) -> List[str]:
+    """One line per window expression under `node` (LazyFrame.explain): the function and its keys as written.  The route each one took is in the physical plan
+    of the last collect (`Window{... route=window[direct range=R] | window[sorted rows: ...]}`)."""
+    out: List[str] = []
+    for attr in ("input", "left", "right"):
+        child = getattr(node, attr, None)
+        if isinstance(child, Node):
+            out += describe_windows(child)
+
+    def walk(e):
+        if e is None:
+            return
+        if e.kind == "window":
+            out.append(f"Window[{e.lhs!r} over [{', '.join(repr(k) for k in e.value)}], mapping=group_to_rows] in {node.kind}")
+        for c in e.children():
+            walk(c)
+    for e in list(getattr(node, "exprs", None) or []) + [getattr(node, "predicate", None)]:
+        walk(e)
+    return out
+
+
 def describe_join_orders(node: Node) -> List[str]:
     """One line per join under `node` that was asked to keep a row order (LazyFrame.explain)."""
     out: List[str] = []
@@ -221,6 +242,15 @@ class Lowering:
             else:
                 out = dt
             return self._push(kind=F.AE_AGG, op=e.op, lhs=idx), out
+        if k == "window":
+            # f.over(k1, k2, ...): AE_WINDOW with the function in lhs and the first link of the key chain in rhs; one AE_WINDOW_KEY link per key (lhs = the key,
+            # rhs = the next link or -1).  The arena is topological, so the links are pushed last key first.  The engine checks that f aggregates and the keys do not
+            fi, fdt = self.lower_expr(e.lhs, schema)
+            key_nodes = [self.lower_expr(key, schema)[0] for key in e.value]
+            link = -1
+            for ki in reversed(key_nodes):
+                link = self._push(kind=F.AE_WINDOW_KEY, lhs=ki, rhs=link)
+            return self._push(kind=F.AE_WINDOW, lhs=fi, rhs=link), fdt
         if k == "binary":
             return self._lower_binary(e, schema)
         if k == "ternary":

@@ -175,6 +175,21 @@ class Translator:
                 raise NotSupported("Ternary node without predicate / truthy / falsy")
             cond, truthy, falsy = (self.expr(p) for p in parts)
             return E.Expr("ternary", lhs=truthy, rhs=falsy, cond=cond)
+        if kind == "Window":
+            # visitor/expr_nodes.rs Window: function, partition_by (expression node ids), order_by (a node id or None), options = the mapping of an `over`
+            # (an object whose `kind` is "groups_to_rows" / "join" / "explode") or the options of a rolling window.  An order or another mapping is refused by
+            # name, never ignored
+            if getattr(x, "order_by", None) is not None:
+                raise NotSupported("window expression with order_by: ordered windows are not built")
+            opts = getattr(x, "options", None)
+            mapping = getattr(opts, "kind", opts)
+            mapping = str(mapping() if callable(mapping) else mapping).lower().split(".")[-1]
+            if mapping not in ("groups_to_rows", "group_to_rows", "groupstorows"):
+                raise NotSupported(f"window expression with mapping {mapping}: only group_to_rows is built")
+            keys = [self.expr(k) for k in (x.partition_by or [])]
+            if not keys:
+                raise NotSupported("window expression without partition_by")
+            return E.Expr("window", lhs=self.expr(x.function), value=tuple(keys))
         raise NotSupported(f"expression node {kind}")
 
     def named(self, e: Any) -> E.Expr:

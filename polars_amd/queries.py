@@ -55,6 +55,15 @@ def lineitem_distinct(lineitem):
                                                                   E.len().alias("count_order"))
 
 
+def share_of_flag_total(lineitem):
+    """with_columns((l_extendedprice / l_extendedprice.sum().over(l_returnflag, l_linestatus)).alias("share")).filter(l_quantity > l_quantity.median().over(l_returnflag))
+    -- every line's share of the revenue of its (flag, status), kept where its quantity lies above the median quantity of its flag.  Two window expressions: each runs
+    one group-by over its keys and goes back to the rows through one row -> group map and one broadcast; height and row order stay the frame's until the filter"""
+    c = E.col
+    return (lineitem.with_columns((c("l_extendedprice") / c("l_extendedprice").sum().over("l_returnflag", "l_linestatus")).alias("share"))
+            .filter(c("l_quantity") > c("l_quantity").median().over("l_returnflag")))
+
+
 def q1(lineitem, cutoff=Q1_CUTOFF):
     """TPC-H Q1; the final sort by (flag, status) happens on the host."""
     c = E.col
