@@ -155,6 +155,28 @@ typedef enum plx_unique_keep {
   PLX_UNIQUE_NONE = 3
 } plx_unique_keep;
 
+/* The cumulative functions (PLX_AE_CUMULATIVE, plx_cumulative): each keeps one value per row.  A null row stays null (COUNT has no nulls) and adds nothing; the
+ * running value carries over it.  SUM: the sum aggregate's dtype (narrow integers -> PLX_I64, PLX_BOOL -> PLX_U32), integers wrap, PLX_F32 accumulates in f64 like
+ * the sum aggregate; MIN / MAX keep the dtype and ignore a NaN unless every valid value so far is NaN (the min / max aggregates' rule); COUNT: PLX_U32, the number of
+ * non-null values up to and including the row. */
+typedef enum plx_cum_op {
+  PLX_CUM_SUM = 0,
+  PLX_CUM_MIN = 1,
+  PLX_CUM_MAX = 2,
+  PLX_CUM_COUNT = 3
+} plx_cum_op;
+
+/* The ranking methods (PLX_AE_RANK, plx_rank).  Values rank in the sort's order (NaN greatest, all NaNs tie, -0 == +0); a null row's rank is null and nulls take no
+ * part.  Among equal values AVERAGE gives the mean of their ordinal ranks (PLX_F64), MIN the smallest, MAX the largest, DENSE the number of distinct values up to
+ * theirs, ORDINAL their ordinal ranks in row order (also when descending); the last four are PLX_U32. */
+typedef enum plx_rank_method {
+  PLX_RANK_AVERAGE = 0,
+  PLX_RANK_MIN = 1,
+  PLX_RANK_MAX = 2,
+  PLX_RANK_DENSE = 3,
+  PLX_RANK_ORDINAL = 4
+} plx_rank_method;
+
 /* With pos = (n - 1) * q over the n valid values in order and a, b the values at ranks floor(pos), ceil(pos): NEAREST = the value at rank floor(pos + 0.5),
  * LOWER = a, HIGHER = b, MIDPOINT = a == b ? a : (a + b) / 2, LINEAR = a == b ? a : (pos - floor(pos)) * (b - a) + a. */
 typedef enum plx_quantile_interpolation {
@@ -386,6 +408,15 @@ int plx_groupby_agg_params(const plx_column* keys, int32_t n_keys, const plx_col
  * is legal).  At most 2^32 - 2 rows. */
 int plx_window_agg(const plx_column* keys, int32_t n_keys, const plx_column* values, const plx_agg_op* aggs, int32_t n_aggs, const int32_t* ddof,
                    const double* q, const int32_t* interpolation, plx_column* out_cols);
+/* Cumulative functions and ranks over plain columns (PLX_AE_CUMULATIVE / PLX_AE_RANK as column calls).  n_keys == 0 (keys may be NULL): the whole
+ * column is one partition; 1..8 key columns (more is PLX_ERR_UNSUPPORTED): the partitions of a window over them, each scanned / ranked in row order.  op is a
+ * plx_cum_op, method a plx_rank_method, reverse / descending 0 or 1: anything else is PLX_ERR_INVALID naming the parameter, checked before anything runs, an empty
+ * input included.  The result has the height and row order of `value`, the dtype of plx_cum_op / plx_rank_method and the validity of `value` (PLX_CUM_COUNT: none).
+ * plx_last_plan_description() names the route: "Cumulative{... route=cumulative[whole column] | cumulative[sorted rows: ...]}" (a segmented inclusive scan in three
+ * launches: tile aggregates, their scan, the tiles with their carry) and "Rank{... route=rank[sorted segments: ...]}" (one sort by (keys, value), two head masks, O(1) per row).
+ * At most 2^32 - 2 rows. */
+int plx_cumulative(const plx_column* keys, int32_t n_keys, plx_column value, int32_t op, int32_t reverse, plx_column* out);
+int plx_rank(const plx_column* keys, int32_t n_keys, plx_column value, int32_t method, int32_t descending, plx_column* out);
 /* Row-order Boolean mask (no nulls) of the rows that unique() keeps: the n_keys (1..8: more is PLX_ERR_UNSUPPORTED) key columns of integer, float or Boolean dtype
  * are sorted stably once, so the head of every run of equal rows is its first occurrence and the tail its last; keep is a plx_unique_keep (outside 0..3:
  * PLX_ERR_INVALID).  Two rows are equal when every key is equal by the sort's equality, null == null.  Filtering any column of the same height by the mask
@@ -462,8 +493,17 @@ typedef enum plx_aexpr_kind {
                            * (a null key is a partition of its own, NaN == NaN, -0 == +0).  Legal in the expressions of PLX_IR_SELECT / PLX_IR_HSTACK and in the predicate
                            * of PLX_IR_FILTER, anywhere inside them; in the keys or aggregates of a PLX_IR_GROUPBY it is PLX_ERR_INVALID.  Windows of one node that share
                            * their key list run one group-by, one row -> group map and one broadcast; fused pipelines decline the kind by name.  Output name: that of lhs */
-  PLX_AE_WINDOW_KEY = 15  /* one link of a window's key list: lhs = a key expression (no aggregate inside: PLX_ERR_INVALID), rhs = the next link or -1.  1..8 links
+  PLX_AE_WINDOW_KEY = 15, /* one link of a window's key list: lhs = a key expression (no aggregate inside: PLX_ERR_INVALID), rhs = the next link or -1.  1..8 links
                            * (more is PLX_ERR_UNSUPPORTED).  A link anywhere but below a PLX_AE_WINDOW, and a window without a link, are PLX_ERR_INVALID at plan import */
+  PLX_AE_CUMULATIVE = 16, /* lhs = a row-level operand (no aggregate, window, cumulative or ranking node inside: PLX_ERR_UNSUPPORTED naming it), op = the plx_cum_op
+                           * (outside 0..3: PLX_ERR_INVALID at import), lit.u = reverse (0 / 1: the scan runs from the last row to the first).  Result: one value per
+                           * row in the dtype of plx_cum_op, the operand's validity (COUNT: none), height and row order the input's.  The partition is the whole column, or,
+                           * as the lhs of a PLX_AE_WINDOW, each partition of its keys in the frame's row order.  Legal where a window is; in the keys or aggregates of a
+                           * PLX_IR_GROUPBY it is PLX_ERR_INVALID.  Nodes of one select / with_columns / filter that share their key list share one stable sort of the
+                           * rows and one head mask; fused pipelines decline the kind by name.  Output name: that of lhs */
+  PLX_AE_RANK = 17        /* lhs = a row-level operand (as for PLX_AE_CUMULATIVE), op = the plx_rank_method (outside 0..4: PLX_ERR_INVALID at import), lit.u = descending
+                           * (0 / 1).  Result: PLX_F64 (AVERAGE) or PLX_U32 with the operand's validity; whole column, or per partition as the lhs of a PLX_AE_WINDOW.
+                           * Nodes that share (keys, operand, descending) share one sort.  Output name: that of lhs */
 } plx_aexpr_kind;
 
 /* polars_plan::dsl::Operator subset */
@@ -475,14 +515,14 @@ typedef enum plx_operator {
 
 typedef struct plx_aexpr {
   int32_t kind; /* plx_aexpr_kind */
-  int32_t op;   /* plx_operator or plx_agg_op */
+  int32_t op;   /* plx_operator or plx_agg_op; PLX_AE_CUMULATIVE: plx_cum_op; PLX_AE_RANK: plx_rank_method */
   int32_t lhs;  /* arena index of the (left) input, -1 if none */
   int32_t rhs;  /* arena index of the right input, -1 if none */
   int32_t dtype; /* literal dtype / cast target (plx_dtype) */
   int32_t is_null; /* literal is NULL */
   plx_scalar lit;   /* PLX_AE_LITERAL: the value; PLX_AE_BITMAP_LOOKUP: lit.u = the lookup bitmap's plx_column handle; PLX_AE_TEMPORAL: lit.u = the plx_time_unit;
                      * PLX_AE_AGG of PLX_AGG_VAR / PLX_AGG_STD: lit.u = ddof; of PLX_AGG_QUANTILE: lit.f64 = q (and dtype = the plx_quantile_interpolation); PLX_AGG_N_UNIQUE carries nothing;
-                     * read for those kinds only */
+                     * PLX_AE_CUMULATIVE: lit.u = reverse; PLX_AE_RANK: lit.u = descending; read for those kinds only */
   const char* name; /* column name / alias */
   int32_t cond;     /* PLX_AE_TERNARY: arena index of the predicate; read for that kind only (appended last: arenas of earlier callers never carry the kind) */
 } plx_aexpr;
@@ -888,6 +928,14 @@ void _polars_plugin_field_plx_n_unique(const struct ArrowSchema* fields, size_t 
  * under the first input's name */
 void _polars_plugin_plx_window_agg(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
 void _polars_plugin_field_plx_window_agg(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
+/* plx_cum (values, key...): plx_cumulative; kwargs {"op": "sum" | "min" | "max" | "count", "reverse": bool}; zero keys: the whole column.  A result of the inputs'
+ * height; the field is the plx_cum_op dtype under the first input's name */
+void _polars_plugin_plx_cum(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
+void _polars_plugin_field_plx_cum(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
+/* plx_rank (values, key...): plx_rank; kwargs {"method": "average" | "min" | "max" | "dense" | "ordinal", "descending": bool}; the field is Float64 for "average",
+ * UInt32 otherwise, under the first input's name */
+void _polars_plugin_plx_rank(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
+void _polars_plugin_field_plx_rank(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
 
 #ifdef __cplusplus
 }

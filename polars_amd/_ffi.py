@@ -37,6 +37,11 @@ JOIN_ORDER_NONE, JOIN_ORDER_LEFT, JOIN_ORDER_RIGHT, JOIN_ORDER_LEFT_RIGHT, JOIN_
 AE_COLUMN, AE_LITERAL, AE_BINARY, AE_CAST, AE_AGG, AE_LEN, AE_ALIAS, AE_NOT, AE_IS_NULL, AE_IS_NOT_NULL, AE_FILL_NULL, AE_TERNARY, AE_BITMAP_LOOKUP, AE_TEMPORAL = range(14)
 AE_WINDOW, AE_WINDOW_KEY = 14, 15                                          # f.over(keys): lhs = the function, rhs = the first key link; a link: lhs = a key, rhs = the next link or -1
 WINDOW_MAX_KEYS = 8
+AE_CUMULATIVE, AE_RANK = 16, 17                                            # x.cum_sum() / x.rank(): lhs = the operand, op = the plx_cum_op / plx_rank_method, lit.u = reverse / descending
+CUM_SUM, CUM_MIN, CUM_MAX, CUM_COUNT = range(4)                            # plx_cum_op
+CUM_OPS = {"cum_sum": CUM_SUM, "cum_min": CUM_MIN, "cum_max": CUM_MAX, "cum_count": CUM_COUNT}
+RANK_AVERAGE, RANK_MIN, RANK_MAX, RANK_DENSE, RANK_ORDINAL = range(5)      # plx_rank_method
+RANK_METHODS = {"average": RANK_AVERAGE, "min": RANK_MIN, "max": RANK_MAX, "dense": RANK_DENSE, "ordinal": RANK_ORDINAL}
 STR_STARTS_WITH, STR_ENDS_WITH, STR_CONTAINS = range(3)                 # plx_str_match_kind
 STR_MATCH_MAX_PATTERN = 64
 UNIT_DATE, UNIT_MS, UNIT_US, UNIT_NS = range(4)                          # plx_time_unit
@@ -212,6 +217,8 @@ SIGNATURES = {
     "plx_reduce_quantile": (C.c_int, [C.c_uint64, C.c_double, C.c_int32, C.POINTER(Scalar), _i32p, _i32p]),
     "plx_groupby_agg_params": (C.c_int, [_u64p, C.c_int32, _u64p, _i32p, C.c_int32, C.c_int32, _i32p, C.POINTER(C.c_double), _i32p, _u64p, _u64p]),
     "plx_window_agg": (C.c_int, [_u64p, C.c_int32, _u64p, _i32p, C.c_int32, _i32p, C.POINTER(C.c_double), _i32p, _u64p]),
+    "plx_cumulative": (C.c_int, [_u64p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _u64p]),
+    "plx_rank": (C.c_int, [_u64p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _u64p]),
     "plx_join_indices": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _u64p, _u64p]),
     "plx_datagen_lineitem_q1": (C.c_int, [C.c_int64, C.c_uint64, _u64p]),
     "plx_datagen_lineitem_q1_host": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -18,6 +18,7 @@
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
 #include "ops.hpp"
+#include "cumulative.hpp"
 #include "quantile.hpp"
 #include "scan.hpp"
 #include "sort.hpp"
@@ -444,6 +445,59 @@ int plx_window_agg(const plx_column* keys, int32_t n_keys, const plx_column* val
   PLX_CATCH
 }
 
+// the parameters of plx_cumulative / plx_rank and of their plugin twins, checked by name before anything runs (an empty input included)
+extern "C++" {
+namespace {
+std::vector<ColumnPtr> rowfn_inputs(const char* what, const plx_column* keys, int32_t n_keys, const ColumnPtr& value) {
+  PLX_REQUIRE(n_keys >= 0 && (n_keys == 0 || keys), PLX_ERR_INVALID, std::string(what) + ": n_keys must be 0 (the whole column) or the number of key columns given");
+  PLX_REQUIRE(n_keys <= sort::kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, std::string(what) + " over " + std::to_string(n_keys) + " keys; a window takes 1.." + std::to_string(sort::kSegmentMaxKeys) + " keys on this path");
+  std::vector<ColumnPtr> k;
+  for (int i = 0; i < n_keys; i++) k.push_back(get_column(keys[i]));
+  for (auto& kc : k) PLX_REQUIRE(kc->len == value->len, PLX_ERR_SHAPE, std::string(what) + ": key length mismatch");
+  return k;
+}
+ColumnPtr cumulative_call(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, int op, int reverse, std::string* desc) {
+  PLX_REQUIRE(cumulative::op_ok(op), PLX_ERR_INVALID, "cumulative: op " + std::to_string(op) + " is no plx_cum_op (0 = sum, 1 = min, 2 = max, 3 = count)");
+  PLX_REQUIRE(reverse == 0 || reverse == 1, PLX_ERR_INVALID, "cumulative: reverse must be 0 or 1, got " + std::to_string(reverse));
+  if (cumulative::result_dtype(op, value->dtype) < 0) fail(PLX_ERR_UNSUPPORTED, std::string(cumulative::op_name(op)) + " of a " + dtype_name(value->dtype) + " column: integer, float and Boolean columns only");
+  const cumulative::ScanOrder order = cumulative::scan_order(keys, value->len);
+  ColumnPtr out = cumulative::scan_column(order, value, op, reverse != 0);
+  if (desc) *desc = "Cumulative{keys=[" + std::to_string(keys.size()) + " columns], fns=1, rows=" + std::to_string(value->len) + ", route=" + order.desc + "}; ";
+  return out;
+}
+ColumnPtr rank_call(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, int method, int descending, std::string* desc) {
+  PLX_REQUIRE(cumulative::method_ok(method), PLX_ERR_INVALID, "rank: method " + std::to_string(method) + " is no plx_rank_method (0 = average, 1 = min, 2 = max, 3 = dense, 4 = ordinal)");
+  PLX_REQUIRE(descending == 0 || descending == 1, PLX_ERR_INVALID, "rank: descending must be 0 or 1, got " + std::to_string(descending));
+  const cumulative::RankOrder order = cumulative::rank_order(keys, value, descending != 0);
+  ColumnPtr out = cumulative::rank_column(order, method);
+  if (desc) *desc = "Rank{keys=[" + std::to_string(keys.size()) + " columns], fns=1, rows=" + std::to_string(value->len) + ", method=" + cumulative::method_name(method) + (descending ? ", descending" : "") + ", route=" + order.desc + "}; ";
+  return out;
+}
+}  // namespace
+}  // extern "C++"
+
+int plx_cumulative(const plx_column* keys, int32_t n_keys, plx_column value, int32_t op, int32_t reverse, plx_column* out) {
+  PLX_TRY
+  PLX_REQUIRE(out, PLX_ERR_INVALID, "cumulative: null output");
+  ColumnPtr v = get_column(value);
+  std::string d;
+  ColumnPtr r = cumulative_call(rowfn_inputs("cumulative", keys, n_keys, v), v, op, reverse, &d);
+  t_plan_desc = d;
+  *out = register_column(r);
+  PLX_CATCH
+}
+
+int plx_rank(const plx_column* keys, int32_t n_keys, plx_column value, int32_t method, int32_t descending, plx_column* out) {
+  PLX_TRY
+  PLX_REQUIRE(out, PLX_ERR_INVALID, "rank: null output");
+  ColumnPtr v = get_column(value);
+  std::string d;
+  ColumnPtr r = rank_call(rowfn_inputs("rank", keys, n_keys, v), v, method, descending, &d);
+  t_plan_desc = d;
+  *out = register_column(r);
+  PLX_CATCH
+}
+
 int plx_distinct_mask(const plx_column* keys, int32_t n_keys, int32_t keep, plx_column* out_mask) {
   PLX_TRY
   PLX_REQUIRE(keys && n_keys >= 1 && out_mask, PLX_ERR_INVALID, "distinct_mask: need at least one key column");
@@ -769,7 +823,7 @@ ColumnPtr plugin_arith(int op, std::vector<PluginInput>& in) {
 ColumnPtr plugin_reduce(int agg, std::vector<PluginInput>& in) { return ops::scalar_column(ops::reduce(agg, in[0].col)); }
 
 // output field of a plugin function: name of the first input, dtype by the rule of the operator
-enum FieldRule { FIELD_BOOL, FIELD_SAME, FIELD_ARITH, FIELD_SUM, FIELD_MEAN, FIELD_U32 };
+enum FieldRule { FIELD_BOOL, FIELD_SAME, FIELD_ARITH, FIELD_SUM, FIELD_MEAN, FIELD_U32, FIELD_F64 };
 void plugin_field(const ArrowSchema* fields, size_t n, ArrowSchema* out, FieldRule rule, int arith_op) {
   try {
     PLX_REQUIRE(fields && n >= 1 && out, PLX_ERR_INVALID, "plugin field: bad arguments");
@@ -783,6 +837,7 @@ void plugin_field(const ArrowSchema* fields, size_t n, ArrowSchema* out, FieldRu
       case FIELD_SUM: odt = (dt == PLX_I8 || dt == PLX_I16 || dt == PLX_U8 || dt == PLX_U16) ? PLX_I64 : (dt == PLX_BOOL ? PLX_U32 : dt); break;   // sum_output_dtype, aggregate/mod.rs:55-64
       case FIELD_MEAN: odt = dt == PLX_F32 ? PLX_F32 : PLX_F64; break;
       case FIELD_U32: odt = PLX_U32; break;
+      case FIELD_F64: odt = PLX_F64; break;
     }
     memset(out, 0, sizeof(*out));
     auto* nm = new std::string(fields[0].name ? fields[0].name : "");
@@ -919,6 +974,78 @@ void _polars_plugin_field_plx_window_agg(PLX_FIELD_SIG) {
   const int agg = window_agg_of(name);
   if (agg < 0) { t_plugin_error = "plx_window_agg: kwargs must carry agg in {sum, mean, min, max, count, len, var, std, quantile, median, n_unique}"; if (out) out->release = nullptr; return; }
   plugin_field(fields, n_fields, out, window_field_rule(agg), 0);
+}
+// cumulative functions and ranks of the first series, per partition of the others when there are any (plx_cumulative / plx_rank): kwargs {"op": name, "reverse":
+// bool} and {"method": name, "descending": bool}, read like those of plx_window_agg
+extern "C++" {
+namespace {
+int cum_op_of(const std::string& s) {
+  static const char* names[] = {"sum", "min", "max", "count"};
+  for (int i = 0; i < 4; i++) if (s == names[i] || s == std::string("cum_") + names[i]) return i;
+  return -1;
+}
+int rank_method_of(const std::string& s) {
+  static const char* names[] = {"average", "min", "max", "dense", "ordinal"};
+  for (int i = 0; i < 5; i++) if (s == names[i]) return i;
+  return -1;
+}
+// value of a Boolean key in a pickled dict: the key's str token, an optional memo op, then NEWTRUE (0x88) / NEWFALSE (0x89); an integer 0 / 1 counts too.  -1: the
+// value is neither
+int pickle_bool_value(const uint8_t* kw, size_t n, const char* key, int absent) {
+  const size_t klen = strlen(key);
+  for (size_t i = 0; i + 2 + klen <= n; i++) {
+    if (!((kw[i] == 0x8c || kw[i] == 'U') && kw[i + 1] == klen && !memcmp(kw + i + 2, key, klen))) continue;
+    size_t j = i + 2 + klen;
+    if (j < n && kw[j] == 0x94) j += 1; else if (j < n && kw[j] == 'q') j += 2; else if (j < n && kw[j] == 'r') j += 5;
+    if (j < n && kw[j] == 0x88) return 1;
+    if (j < n && kw[j] == 0x89) return 0;
+    const long long v = pickle_int_value(kw, n, key, -1);
+    return v == 0 || v == 1 ? (int)v : -1;
+  }
+  return absent;
+}
+ColumnPtr plugin_column(PluginInput& x) { return x.col ? x.col : ops::full_column(x.dtype, x.scalar, x.scalar_valid, 1); }      // (a frame of one row: every series is a literal)
+const char* kCumKwargs = "plx_cum: kwargs must carry op in {sum, min, max, count}";
+const char* kRankKwargs = "plx_rank: kwargs must carry method in {average, min, max, dense, ordinal}";
+}  // namespace
+}  // extern "C++"
+void _polars_plugin_plx_cum(PLX_PLUGIN_SIG) {
+  const int op = cum_op_of(pickle_str_value(kwargs, kwargs_len, "op"));
+  const int reverse = pickle_bool_value(kwargs, kwargs_len, "reverse", 0);
+  plugin_call(inputs, n_inputs, out, ctx, n_inputs, [&](std::vector<PluginInput>& in) {
+    PLX_REQUIRE(op >= 0, PLX_ERR_INVALID, kCumKwargs);
+    PLX_REQUIRE(reverse >= 0, PLX_ERR_INVALID, "plx_cum: kwargs reverse must be a bool");
+    PLX_REQUIRE(in.size() >= 1, PLX_ERR_INVALID, "plx_cum: the value series, then 0..8 key series");
+    std::vector<ColumnPtr> cols;
+    for (PluginInput& x : in) cols.push_back(plugin_column(x));
+    PLX_REQUIRE((int)cols.size() - 1 <= sort::kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, "plx_cum over " + std::to_string(cols.size() - 1) + " keys; a window takes 1.." + std::to_string(sort::kSegmentMaxKeys) + " keys on this path");
+    for (auto& c : cols) PLX_REQUIRE(c->len == cols[0]->len, PLX_ERR_SHAPE, "plx_cum: key length mismatch");
+    return cumulative_call(std::vector<ColumnPtr>(cols.begin() + 1, cols.end()), cols[0], op, reverse, nullptr);
+  });
+}
+void _polars_plugin_field_plx_cum(PLX_FIELD_SIG) {
+  const int op = cum_op_of(pickle_str_value(kwargs, kwargs_len, "op"));
+  if (op < 0) { t_plugin_error = kCumKwargs; if (out) out->release = nullptr; return; }
+  plugin_field(fields, n_fields, out, op == PLX_CUM_SUM ? FIELD_SUM : op == PLX_CUM_COUNT ? FIELD_U32 : FIELD_SAME, 0);
+}
+void _polars_plugin_plx_rank(PLX_PLUGIN_SIG) {
+  const int method = rank_method_of(pickle_str_value(kwargs, kwargs_len, "method"));
+  const int descending = pickle_bool_value(kwargs, kwargs_len, "descending", 0);
+  plugin_call(inputs, n_inputs, out, ctx, n_inputs, [&](std::vector<PluginInput>& in) {
+    PLX_REQUIRE(method >= 0, PLX_ERR_INVALID, kRankKwargs);
+    PLX_REQUIRE(descending >= 0, PLX_ERR_INVALID, "plx_rank: kwargs descending must be a bool");
+    PLX_REQUIRE(in.size() >= 1, PLX_ERR_INVALID, "plx_rank: the value series, then 0..8 key series");
+    std::vector<ColumnPtr> cols;
+    for (PluginInput& x : in) cols.push_back(plugin_column(x));
+    PLX_REQUIRE((int)cols.size() - 1 <= sort::kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, "plx_rank over " + std::to_string(cols.size() - 1) + " keys; a window takes 1.." + std::to_string(sort::kSegmentMaxKeys) + " keys on this path");
+    for (auto& c : cols) PLX_REQUIRE(c->len == cols[0]->len, PLX_ERR_SHAPE, "plx_rank: key length mismatch");
+    return rank_call(std::vector<ColumnPtr>(cols.begin() + 1, cols.end()), cols[0], method, descending, nullptr);
+  });
+}
+void _polars_plugin_field_plx_rank(PLX_FIELD_SIG) {
+  const int method = rank_method_of(pickle_str_value(kwargs, kwargs_len, "method"));
+  if (method < 0) { t_plugin_error = kRankKwargs; if (out) out->release = nullptr; return; }
+  plugin_field(fields, n_fields, out, method == PLX_RANK_AVERAGE ? FIELD_F64 : FIELD_U32, 0);
 }
 void _polars_plugin_plx_filter(PLX_PLUGIN_SIG) {
   (void)kwargs; (void)kwargs_len;

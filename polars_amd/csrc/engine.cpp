@@ -12,6 +12,7 @@
 #include <set>
 #include <sstream>
 
+#include "cumulative.hpp"
 #include "distinct.hpp"
 #include "encoded_inputs.hpp"
 #include "fused_shapes.hpp"
@@ -77,6 +78,16 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       for (int l = e.rhs; l >= 0; l = ae[l].rhs) n_links++;
       PLX_REQUIRE(n_links <= window::kMaxKeys, PLX_ERR_UNSUPPORTED, "window over " + std::to_string(n_links) + " keys; a window takes 1.." + std::to_string(window::kMaxKeys) + " keys on this path");
     }
+    if (e.kind == PLX_AE_CUMULATIVE) {
+      PLX_REQUIRE(e.lhs >= 0, PLX_ERR_INVALID, "cumulative expression needs an operand (lhs)");
+      PLX_REQUIRE(cumulative::op_ok(e.op), PLX_ERR_INVALID, "cumulative expression: op " + std::to_string(e.op) + " is no plx_cum_op (0 = sum, 1 = min, 2 = max, 3 = count)");
+      PLX_REQUIRE(e.lit.u <= 1, PLX_ERR_INVALID, "cumulative expression: reverse rides in lit.u as 0 / 1, got " + std::to_string((long long)e.lit.i));
+    }
+    if (e.kind == PLX_AE_RANK) {
+      PLX_REQUIRE(e.lhs >= 0, PLX_ERR_INVALID, "rank expression needs an operand (lhs)");
+      PLX_REQUIRE(cumulative::method_ok(e.op), PLX_ERR_INVALID, "rank expression: method " + std::to_string(e.op) + " is no plx_rank_method (0 = average, 1 = min, 2 = max, 3 = dense, 4 = ordinal)");
+      PLX_REQUIRE(e.lit.u <= 1, PLX_ERR_INVALID, "rank expression: descending rides in lit.u as 0 / 1, got " + std::to_string((long long)e.lit.i));
+    }
     p.ae.push_back(std::move(e));
   }
   // a key link stands below a window (as its rhs) or below another link (as its rhs), nowhere else
@@ -133,6 +144,9 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       std::function<bool(int)> has_window = [&](int e) { return e >= 0 && (p.ae[e].kind == PLX_AE_WINDOW || has_window(p.ae[e].lhs) || has_window(p.ae[e].rhs) || has_window(p.ae[e].cond)); };
       for (int e : n.keys) PLX_REQUIRE(!has_window(e), PLX_ERR_INVALID, "group_by: a window expression (.over) cannot stand in the keys of a group_by");
       for (int e : n.exprs) PLX_REQUIRE(!has_window(e), PLX_ERR_INVALID, "group_by: a window expression (.over) cannot stand in the aggregate list of a group_by; aggregate first, or use the window in select / with_columns");
+      std::function<bool(int)> has_rowfn = [&](int e) { return e >= 0 && (p.ae[e].kind == PLX_AE_CUMULATIVE || p.ae[e].kind == PLX_AE_RANK || has_rowfn(p.ae[e].lhs) || has_rowfn(p.ae[e].rhs) || has_rowfn(p.ae[e].cond)); };
+      for (int e : n.keys) PLX_REQUIRE(!has_rowfn(e), PLX_ERR_INVALID, "group_by: a cumulative / ranking expression (cum_sum, cum_min, cum_max, cum_count, rank) cannot stand in the keys of a group_by; compute it in with_columns first");
+      for (int e : n.exprs) PLX_REQUIRE(!has_rowfn(e), PLX_ERR_INVALID, "group_by: a cumulative / ranking expression (cum_sum, cum_min, cum_max, cum_count, rank) cannot stand in the aggregate list of a group_by; it keeps one value per row -- use it in select / with_columns, with .over(keys) for partitions");
     }
     PLX_REQUIRE(n.input < i && n.input_right < i, PLX_ERR_INVALID, "IR arena must be topologically ordered (inputs before consumers)");
     p.ir.push_back(std::move(n));
@@ -186,6 +200,13 @@ int infer_dtype(const Plan& plan, int e, const Frame& schema) {
     }
     case PLX_AE_LEN: return PLX_U32;
     case PLX_AE_WINDOW: return infer_dtype(plan, x.lhs, schema);      // the dtype the function has in a group-by
+    case PLX_AE_CUMULATIVE: {
+      const int in = infer_dtype(plan, x.lhs, schema);
+      const int out = cumulative::result_dtype(x.op, in);
+      if (out < 0) fail(PLX_ERR_UNSUPPORTED, std::string(cumulative::op_name(x.op)) + " of a " + dtype_name(in) + " expression: integer, float and Boolean operands only");
+      return out;
+    }
+    case PLX_AE_RANK: infer_dtype(plan, x.lhs, schema); return cumulative::rank_dtype(x.op);
     case PLX_AE_AGG: {
       int in = infer_dtype(plan, x.lhs, schema);
       switch (x.op) {
@@ -225,10 +246,12 @@ std::string output_name(const Plan& plan, int e) {
 
 // A window (PLX_AE_WINDOW) is a row-level value to everything around it: it does not reduce its node (no aggregate), it reads columns (a column outside an
 // aggregate), and the aggregates inside it belong to its own group-by (collect_aggs stops at it).
+// A cumulative or ranking node (PLX_AE_CUMULATIVE / PLX_AE_RANK) is row-level in the same way: one value per row, its operand is its own business.
+static bool is_rowfn(const AE& x) { return x.kind == PLX_AE_CUMULATIVE || x.kind == PLX_AE_RANK; }
 static bool contains_agg(const Plan& plan, int e) {
   if (e < 0) return false;
   const AE& x = plan.ae[e];
-  if (x.kind == PLX_AE_WINDOW) return false;
+  if (x.kind == PLX_AE_WINDOW || is_rowfn(x)) return false;
   if (x.kind == PLX_AE_AGG || x.kind == PLX_AE_LEN) return true;
   return contains_agg(plan, x.lhs) || contains_agg(plan, x.rhs) || contains_agg(plan, x.cond);
 }
@@ -237,10 +260,15 @@ static bool contains_window(const Plan& plan, int e) {
   const AE& x = plan.ae[e];
   return x.kind == PLX_AE_WINDOW || contains_window(plan, x.lhs) || contains_window(plan, x.rhs) || contains_window(plan, x.cond);
 }
+static bool contains_rowfn(const Plan& plan, int e) {
+  if (e < 0) return false;
+  const AE& x = plan.ae[e];
+  return is_rowfn(x) || contains_rowfn(plan, x.lhs) || contains_rowfn(plan, x.rhs) || contains_rowfn(plan, x.cond);
+}
 static bool contains_column_outside_agg(const Plan& plan, int e) {
   if (e < 0) return false;
   const AE& x = plan.ae[e];
-  if (x.kind == PLX_AE_WINDOW) return true;
+  if (x.kind == PLX_AE_WINDOW || is_rowfn(x)) return true;
   if (x.kind == PLX_AE_AGG || x.kind == PLX_AE_LEN) return false;
   if (x.kind == PLX_AE_COLUMN) return true;
   return contains_column_outside_agg(plan, x.lhs) || contains_column_outside_agg(plan, x.rhs) || contains_column_outside_agg(plan, x.cond);
@@ -254,7 +282,7 @@ static bool contains_column(const Plan& plan, int e) {
 static void collect_aggs(const Plan& plan, int e, std::vector<int>& out) {
   if (e < 0) return;
   const AE& x = plan.ae[e];
-  if (x.kind == PLX_AE_WINDOW) return;
+  if (x.kind == PLX_AE_WINDOW || is_rowfn(x)) return;
   if (x.kind == PLX_AE_AGG || x.kind == PLX_AE_LEN) { if (std::find(out.begin(), out.end(), e) == out.end()) out.push_back(e); return; }
   collect_aggs(plan, x.lhs, out);
   collect_aggs(plan, x.rhs, out);
@@ -326,6 +354,9 @@ static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<i
     // a window's column is finished before the node's expressions are evaluated (run_windows) and found in `overrides` above; one that is not there stands where no
     // executor collects windows
     case PLX_AE_WINDOW: fail(PLX_ERR_UNSUPPORTED, "window expression (.over): only the expressions of select / with_columns and the predicate of filter take one");
+    // ... and so is a cumulative or ranking node's
+    case PLX_AE_CUMULATIVE: case PLX_AE_RANK:
+      fail(PLX_ERR_UNSUPPORTED, std::string(x.kind == PLX_AE_RANK ? "rank" : cumulative::op_name(x.op)) + ": a cumulative / ranking expression stands in the expressions of select / with_columns and the predicate of filter only");
     case PLX_AE_AGG: {
       Evaluated c = eval(plan, x.lhs, df, overrides);
       if (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD) return {ops::scalar_column(ops::reduce_var(c.col, (int)x.lit.u, x.op == PLX_AGG_STD)), true};
@@ -612,7 +643,8 @@ class Compiler {
           default: throw Unsupported("operator inside a fused program");
         }
       }
-      case PLX_AE_WINDOW: case PLX_AE_WINDOW_KEY: throw Unsupported("window expression: per-node route");
+      case PLX_AE_WINDOW: case PLX_AE_WINDOW_KEY: throw Unsupported(contains_rowfn(plan, x.lhs) ? "cumulative / ranking expression: per-node route" : "window expression: per-node route");
+      case PLX_AE_CUMULATIVE: case PLX_AE_RANK: throw Unsupported("cumulative / ranking expression: per-node route");
       default: throw Unsupported("aggregation nested inside a row expression");
     }
   }
@@ -1778,6 +1810,7 @@ static int and_predicates(Compiler& c, const std::vector<int>& preds) {
 // Select(aggregations) over [Filter]* over `src`
 static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& preds, const FramePtr& src, FramePtr& out, Shape* shape_out, int* sid_out,
                          std::string* why, bool compile_only) {
+  for (int e : node.exprs) if (contains_rowfn(plan, e)) { if (why) *why = "cumulative / ranking expression: per-node route"; return false; }
   for (int e : node.exprs) if (contains_window(plan, e)) { if (why) *why = "window expression: per-node route"; return false; }
   for (int e : node.exprs) if (!contains_agg(plan, e) || contains_column_outside_agg(plan, e)) { if (why) *why = "select mixes row expressions and aggregations"; return false; }
   // select(lit(2.5).sum()) aggregates a one-row literal (sum 2.5, count 1, whatever the filter keeps), as the per-node evaluator does: a fused program would
@@ -1832,6 +1865,7 @@ static bool forget_assumed_bounds(const std::vector<ColumnPtr>& cols) {
 // GroupBy(keys, aggregations) over [Filter]* over `src`
 static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& preds, const FramePtr& src, FramePtr& out, Shape* shape_out, int* sid_out,
                           std::string* why, bool compile_only) {
+  for (int e : node.exprs) if (contains_rowfn(plan, e)) { if (why) *why = "cumulative / ranking expression: per-node route"; return false; }
   for (int e : node.exprs) if (contains_window(plan, e)) { if (why) *why = "window expression: per-node route"; return false; }
   for (int e : node.exprs) if (!contains_agg(plan, e) || contains_column_outside_agg(plan, e)) { if (why) *why = "group_by aggregation list contains a non-aggregated column"; return false; }
   Compiler c(plan, *src);
@@ -2809,7 +2843,8 @@ static bool filter_phrase(Plan& plan, const std::vector<int>& preds, const Frame
 static void collect_windows(const Plan& plan, int e, std::vector<int>& out) {
   if (e < 0) return;
   const AE& x = plan.ae[e];
-  if (x.kind == PLX_AE_WINDOW) { if (std::find(out.begin(), out.end(), e) == out.end()) out.push_back(e); return; }
+  // (a cumulative or ranking node that stands by itself is collected with the windows: its partition is the whole column)
+  if (x.kind == PLX_AE_WINDOW || is_rowfn(x)) { if (std::find(out.begin(), out.end(), e) == out.end()) out.push_back(e); return; }
   collect_windows(plan, x.lhs, out);
   collect_windows(plan, x.rhs, out);
   collect_windows(plan, x.cond, out);
@@ -2847,9 +2882,113 @@ static ColumnPtr empty_column(int dtype) {
   c->dtype = dtype; c->len = 0; c->null_count = 0; c->values = dev_alloc(values_bytes(dtype, 1) + 8);
   return c;
 }
+// ---- cumulative and ranking functions ----
+// One per-row function of a node: `id` is the node eval() will look up (the PLX_AE_CUMULATIVE / PLX_AE_RANK itself, or the PLX_AE_WINDOW around it), `fn` the
+// function, `keys` the window's keys (none: the whole column).
+struct RowFn { int id, fn; std::vector<int> keys; };
+static std::string rowfn_name(const AE& x) { return x.kind == PLX_AE_RANK ? "rank" : cumulative::op_name(x.op); }
+// Buckets by key list: the cumulative functions of a bucket share one stable sort of the rows by the keys and one head mask (cumulative::scan_order); its ranks
+// share one sort_segments per (operand, descending) (cumulative::rank_order).  Every finished column goes into `done` under the function's id.
+static void run_rowfns(Plan& plan, const std::vector<RowFn>& fns, const Frame& in, std::map<int, ColumnPtr>& done) {
+  struct Bucket { std::vector<int> keys; std::vector<RowFn> fns; };
+  std::vector<Bucket> buckets;
+  for (const RowFn& r : fns) {
+    const AE& f = plan.ae[r.fn];
+    const std::string name = rowfn_name(f);
+    PLX_REQUIRE(!contains_rowfn(plan, f.lhs), PLX_ERR_UNSUPPORTED, name + ": a cumulative / ranking expression inside the operand of another one is not built; compute the inner one in with_columns first");
+    PLX_REQUIRE(!contains_window(plan, f.lhs), PLX_ERR_UNSUPPORTED, name + ": a window expression (.over) inside the operand of a cumulative / ranking expression is not built; compute it in with_columns first");
+    PLX_REQUIRE(!contains_agg(plan, f.lhs), PLX_ERR_UNSUPPORTED, name + ": an aggregate inside the operand of a cumulative / ranking expression is not built; the operand is a row-level expression");
+    for (int kx : r.keys) {
+      PLX_REQUIRE(!contains_window(plan, kx) && !contains_rowfn(plan, kx), PLX_ERR_INVALID, "window expression: a key that holds a window");
+      PLX_REQUIRE(!contains_agg(plan, kx), PLX_ERR_INVALID, "window expression: a key that holds an aggregate (" + output_name(plan, kx) + "); keys are row expressions");
+    }
+    Bucket* b = nullptr;
+    for (Bucket& c : buckets) {
+      bool same = c.keys.size() == r.keys.size();
+      for (size_t j = 0; same && j < r.keys.size(); j++) same = same_expr(plan, c.keys[j], r.keys[j]);
+      if (same) { b = &c; break; }
+    }
+    if (!b) { buckets.push_back(Bucket{r.keys, {}}); b = &buckets.back(); }
+    b->fns.push_back(r);
+  }
+  for (const Bucket& b : buckets) {
+    std::string key_names;
+    for (int kx : b.keys) key_names += (key_names.empty() ? "" : ", ") + output_name(plan, kx);
+    std::vector<RowFn> cums, ranks;
+    for (const RowFn& r : b.fns) (plan.ae[r.fn].kind == PLX_AE_RANK ? ranks : cums).push_back(r);
+    const std::string rows = ", rows=" + std::to_string(in.height);
+    if (in.height == 0) {      // an empty frame: empty columns of the right dtype, the plan text in the shape of every other
+      for (int kx : b.keys) infer_dtype(plan, kx, in);
+      for (const RowFn& r : b.fns) done[r.id] = empty_column(infer_dtype(plan, r.fn, in));
+      if (!cums.empty()) plan.desc += "Cumulative{keys=[" + key_names + "], fns=" + std::to_string(cums.size()) + rows + ", route=cumulative[empty]}; ";
+      if (!ranks.empty()) plan.desc += "Rank{keys=[" + key_names + "], fns=" + std::to_string(ranks.size()) + rows + ", route=rank[empty]}; ";
+      continue;
+    }
+    std::vector<ColumnPtr> keys;
+    for (int kx : b.keys) keys.push_back(broadcast(eval(plan, kx, in, nullptr), in.height));
+    // one column per operand expression, the same operand written twice included
+    std::vector<std::pair<int, ColumnPtr>> operands;
+    auto operand = [&](int e) {
+      for (auto& kv : operands) if (same_expr(plan, kv.first, e)) return kv.second;
+      operands.emplace_back(e, broadcast(eval(plan, e, in, nullptr), in.height));
+      return operands.back().second;
+    };
+    flush_node_notes(plan);
+    if (!cums.empty()) {
+      const cumulative::ScanOrder order = cumulative::scan_order(keys, in.height);
+      for (size_t i = 0; i < cums.size(); i++) {
+        const RowFn& r = cums[i];
+        const AE& f = plan.ae[r.fn];
+        infer_dtype(plan, r.fn, in);      // (the operand's dtype is refused by name before anything runs)
+        size_t twin = i;                  // the same function written twice is scanned once
+        for (size_t j = 0; j < i && twin == i; j++) if (same_expr(plan, cums[j].fn, r.fn)) twin = j;
+        done[r.id] = twin < i ? done[cums[twin].id] : cumulative::scan_column(order, operand(f.lhs), f.op, f.lit.u != 0);
+      }
+      plan.desc += "Cumulative{keys=[" + key_names + "], fns=" + std::to_string(cums.size()) + rows + ", route=" + order.desc + "}; ";
+    }
+    std::vector<bool> ranked(ranks.size(), false);
+    for (size_t i = 0; i < ranks.size(); i++) {
+      if (ranked[i]) continue;
+      const AE& f = plan.ae[ranks[i].fn];
+      const cumulative::RankOrder order = cumulative::rank_order(keys, operand(f.lhs), f.lit.u != 0);
+      std::string methods;
+      int n_fns = 0;
+      for (size_t j = i; j < ranks.size(); j++) {
+        const AE& g = plan.ae[ranks[j].fn];
+        if (ranked[j] || !same_expr(plan, f.lhs, g.lhs) || (f.lit.u != 0) != (g.lit.u != 0)) continue;
+        ranked[j] = true; n_fns++;
+        size_t twin = j;
+        for (size_t t = i; t < j && twin == j; t++) if (ranked[t] && same_expr(plan, ranks[t].fn, ranks[j].fn)) twin = t;
+        done[ranks[j].id] = twin < j ? done[ranks[twin].id] : cumulative::rank_column(order, g.op);
+        const std::string m = cumulative::method_name(g.op);
+        if (methods.find(m) == std::string::npos) methods += (methods.empty() ? "" : "+") + m;
+      }
+      plan.desc += "Rank{keys=[" + key_names + "], fns=" + std::to_string(n_fns) + rows + ", method=" + methods + (f.lit.u ? ", descending" : "") + ", route=" + order.desc + "}; ";
+    }
+  }
+}
+// the function a window wraps, through its aliases
+static int window_function(const Plan& plan, int w) {
+  int f = plan.ae[w].lhs;
+  while (f >= 0 && plan.ae[f].kind == PLX_AE_ALIAS) f = plan.ae[f].lhs;
+  return f;
+}
+
 static void run_windows(Plan& plan, const std::vector<int>& exprs, const Frame& in, std::map<int, ColumnPtr>& done) {
-  std::vector<int> wins;
-  for (int e : exprs) collect_windows(plan, e, wins);
+  std::vector<int> collected, wins;
+  for (int e : exprs) collect_windows(plan, e, collected);
+  if (collected.empty()) return;
+  // the cumulative and ranking functions first: plain ones, and windows whose function is one
+  std::vector<RowFn> rowfns;
+  for (int w : collected) {
+    if (is_rowfn(plan.ae[w])) { rowfns.push_back(RowFn{w, w, {}}); continue; }
+    const int f = window_function(plan, w);
+    if (f >= 0 && is_rowfn(plan.ae[f])) { rowfns.push_back(RowFn{w, f, window_keys(plan, w)}); continue; }
+    PLX_REQUIRE(!contains_rowfn(plan, plan.ae[w].lhs), PLX_ERR_UNSUPPORTED,
+                "window expression: its function mixes a cumulative / ranking expression with something else; .over(keys) goes directly on the cumulative / ranking expression (and on each aggregate), the arithmetic outside");
+    wins.push_back(w);
+  }
+  if (!rowfns.empty()) run_rowfns(plan, rowfns, in, done);
   if (wins.empty()) return;
   struct Bucket { std::vector<int> keys, wins; };
   std::vector<Bucket> buckets;
@@ -2859,7 +2998,7 @@ static void run_windows(Plan& plan, const std::vector<int>& exprs, const Frame& 
     PLX_REQUIRE(!contains_window(plan, f), PLX_ERR_UNSUPPORTED, "window expression: a window inside the function of another window is not built");
     PLX_REQUIRE(contains_agg(plan, f) && !contains_column_outside_agg(plan, f), PLX_ERR_UNSUPPORTED,
                 "window expression over [" + output_name(plan, keys[0]) + (keys.size() > 1 ? ", ..." : "") + "]: its function does not reduce to one value per partition (a column outside an aggregate, or no aggregate at all); "
-                "window functions that do not aggregate (a bare column, cumulative and ranking functions) are not built");
+                "window functions that do not aggregate (a bare column) are not built");
     for (int kx : keys) {
       PLX_REQUIRE(!contains_window(plan, kx), PLX_ERR_INVALID, "window expression: a key that holds a window");
       PLX_REQUIRE(!contains_agg(plan, kx), PLX_ERR_INVALID, "window expression: a key that holds an aggregate (" + output_name(plan, kx) + "); keys are row expressions");

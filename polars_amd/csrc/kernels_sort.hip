@@ -655,27 +655,27 @@ ColumnPtr invert_permutation(const ColumnPtr& perm) {
   return out;
 }
 
-SortedSegments sort_segments(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, int64_t expect_groups) {
-  PLX_REQUIRE(!keys.empty() && (int)keys.size() <= kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, "sorted segments: 1.." + std::to_string(kSegmentMaxKeys) + " key columns, got " + std::to_string(keys.size()));
+SortedSegments sort_segments(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, int64_t expect_groups, bool descending) {
+  PLX_REQUIRE((int)keys.size() <= kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, "sorted segments: 1.." + std::to_string(kSegmentMaxKeys) + " key columns, got " + std::to_string(keys.size()));
   SortedSegments seg;
   seg.value = value;
   const int64_t n = seg.n = value->len;
   std::vector<SortKey> sk;
   for (const ColumnPtr& kc : keys) { SortKey s; s.col = kc; s.nulls_last = true; sk.push_back(s); }
-  { SortKey s; s.col = value; s.nulls_last = true; sk.push_back(s); }
+  { SortKey s; s.col = value; s.nulls_last = true; s.descending = descending; sk.push_back(s); }
   seg.perm = sort_indices(sk, -1, &seg.sort_desc);
   seg.starts = dev_alloc(4);
   if (n) {
-    seg.heads = segment_heads_of(keys, seg.perm, n);
+    seg.heads = segment_heads_of(keys, seg.perm, n);      // (no key: position 0 alone)
     k::FilterPlan fp = k::filter_prepare(seg.heads->as<uint64_t>(), n);
     seg.n_groups = fp.n_out;
-    PLX_REQUIRE(seg.n_groups == expect_groups, PLX_ERR_INVALID, "sorted segments: segment count mismatch (" + std::to_string(seg.n_groups) + " segments, " + std::to_string(expect_groups) + " groups)");
+    PLX_REQUIRE(expect_groups < 0 || seg.n_groups == expect_groups, PLX_ERR_INVALID, "sorted segments: segment count mismatch (" + std::to_string(seg.n_groups) + " segments, " + std::to_string(expect_groups) + " groups)");
     Buf iota = dev_alloc((size_t)n * 4);
     k::fill_iota_u32(iota->as<uint32_t>(), n);
     seg.starts = dev_alloc((size_t)std::max<int64_t>(seg.n_groups, 1) * 4);
     k::filter_apply(fp, 4, iota->ptr, nullptr, seg.starts->ptr, nullptr);
   } else {
-    PLX_REQUIRE(expect_groups == 0, PLX_ERR_INVALID, "sorted segments: segment count mismatch (0 segments, " + std::to_string(expect_groups) + " groups)");
+    PLX_REQUIRE(expect_groups <= 0, PLX_ERR_INVALID, "sorted segments: segment count mismatch (0 segments, " + std::to_string(expect_groups) + " groups)");
   }
   return seg;
 }
@@ -805,7 +805,7 @@ __global__ __launch_bounds__(kBlock) void distinct_keep_kernel(const uint64_t* _
 }
 
 // the exclusive prefix of a mask's per-word popcounts (words + 1 entries, the last the total): what distinct::rank_before reads
-static Buf mask_rank_prefix(const Buf& mask, int64_t n_bits) {
+Buf mask_rank_prefix(const Buf& mask, int64_t n_bits) {
   const int64_t nwords = (n_bits + 63) >> 6;
   Buf counts = dev_alloc((size_t)nwords * 4), prefix = dev_alloc(((size_t)nwords + 1) * 8);
   hipLaunchKernelGGL(mask_word_counts_kernel, dim3(k::grid_for(nwords, kBlock * 4)), dim3(kBlock), 0, stream(), mask->as<uint64_t>(), n_bits, counts->as<uint32_t>());
@@ -814,16 +814,20 @@ static Buf mask_rank_prefix(const Buf& mask, int64_t n_bits) {
   return prefix;
 }
 
+static Buf distinct_heads_of(const SortedSegments& seg) {
+  const int64_t n = seg.n;
+  Buf mask = dev_alloc(bitmap_bytes(n));
+  ProfileScope ps("distinct_heads", (uint64_t)n * (4 + (dtype_width(seg.value->dtype) ? dtype_width(seg.value->dtype) : 1)) + (uint64_t)n / 4, (uint64_t)n);
+  hipLaunchKernelGGL(distinct_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), key_col(seg.value), seg.perm->values->as<uint32_t>(), seg.heads->as<uint64_t>(), n, mask->as<uint64_t>());
+  PLX_HIP(hipGetLastError());
+  return mask;
+}
+
 ColumnPtr segment_distinct(const SortedSegments& seg) {
   const int64_t n = seg.n, n_groups = seg.n_groups;
   ColumnPtr out = make_idx(n_groups);
   if (!n_groups) return out;
-  Buf mask = dev_alloc(bitmap_bytes(n));
-  {
-    ProfileScope ps("distinct_heads", (uint64_t)n * (4 + (dtype_width(seg.value->dtype) ? dtype_width(seg.value->dtype) : 1)) + (uint64_t)n / 4, (uint64_t)n);
-    hipLaunchKernelGGL(distinct_heads_kernel, dim3(k::grid_for(n, kBlock * 4)), dim3(kBlock), 0, stream(), key_col(seg.value), seg.perm->values->as<uint32_t>(), seg.heads->as<uint64_t>(), n, mask->as<uint64_t>());
-    PLX_HIP(hipGetLastError());
-  }
+  Buf mask = distinct_heads_of(seg);
   Buf prefix = mask_rank_prefix(mask, n);
   {
     ProfileScope ps("segment_distinct", (uint64_t)n_groups * 44, (uint64_t)n_groups);
@@ -832,6 +836,21 @@ ColumnPtr segment_distinct(const SortedSegments& seg) {
     PLX_HIP(hipGetLastError());
   }
   return out;
+}
+
+ValueRuns value_runs(const SortedSegments& seg) {
+  ValueRuns r;
+  const int64_t n = seg.n;
+  PLX_REQUIRE(n > 0 && seg.heads, PLX_ERR_INVALID, "value runs: sorted segments of at least one row");
+  r.heads = distinct_heads_of(seg);
+  r.prefix = mask_rank_prefix(r.heads, n);
+  k::FilterPlan fp = k::filter_prepare(r.heads->as<uint64_t>(), n);
+  r.n_runs = fp.n_out;
+  Buf iota = dev_alloc((size_t)n * 4);
+  k::fill_iota_u32(iota->as<uint32_t>(), n);
+  r.starts = dev_alloc((size_t)std::max<int64_t>(r.n_runs, 1) * 4);
+  k::filter_apply(fp, 4, iota->ptr, nullptr, r.starts->ptr, nullptr);
+  return r;
 }
 
 uint32_t n_unique_column(const ColumnPtr& c, bool force_sort, std::string* desc) {

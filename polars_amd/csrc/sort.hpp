@@ -50,7 +50,15 @@ struct SortedSegments {
   int64_t n = 0, n_groups = 0;
   std::string sort_desc;
 };
-SortedSegments sort_segments(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, int64_t expect_groups);
+// descending: the value sorts descending inside every segment (nulls stay last, ties keep row order); the keys never do.  No key at all: the whole column is one
+// segment.  expect_groups < 0: no expectation.
+SortedSegments sort_segments(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, int64_t expect_groups, bool descending = false);
+// The runs of equal values inside the segments of a sorted order: distinct_heads_kernel's mask (a position starts a segment, or its value differs from the position
+// before; a null and a value differ, two nulls do not), its per-word prefix and its compacted positions starts[n_runs].  What rank reads beside the segments.
+struct ValueRuns { Buf heads, prefix, starts; int64_t n_runs = 0; };
+ValueRuns value_runs(const SortedSegments& seg);
+// the exclusive prefix of a mask's per-word popcounts (words + 1 entries, the last the total): what distinct::rank_before reads
+Buf mask_rank_prefix(const Buf& mask, int64_t n_bits);
 // Quantiles per group: one lane per group picking two values (segment_quantile_kernel).  One column per spec (Float64; Float32 for a Float32 value column; null for
 // a group without a valid value), G rows in the segments' order.
 struct QuantileSpec { double q; int interpolation; };
@@ -96,4 +104,20 @@ RowMap map_rows(const std::vector<ColumnPtr>& keys, const std::vector<ColumnPtr>
 // has a validity bitmap only when its group column holds a null.  PLX_ERR_INVALID when a row has no group.
 std::vector<ColumnPtr> broadcast(const RowMap& m, const std::vector<ColumnPtr>& group_cols);
 }  // namespace window
+
+// ---- cumulative and ranking functions (kernels_cumulative.hip; cumulative.hpp holds the arithmetic) ----
+namespace cumulative {
+// The order a partitioned scan walks: one stable sort_indices of the rows by the keys (rows of a partition stay in row order) and its segment-head mask.  Shared by
+// every cumulative node of one key list.  No key: perm and heads stay null, the rows themselves are the order.
+struct ScanOrder { ColumnPtr perm; Buf heads; int64_t n = 0; std::string desc; };      // desc: "cumulative[whole column]" | "cumulative[sorted rows: <sort>]"
+ScanOrder scan_order(const std::vector<ColumnPtr>& keys, int64_t n);
+// One cumulative function of `value` (any column dtype for PLX_CUM_COUNT; integer, float, Boolean otherwise) along `order`: a segmented inclusive scan in three
+// launches (tile aggregates; their scan, recursive above one tile of tiles; the tiles with their carry).  The result shares the validity of `value`.
+ColumnPtr scan_column(const ScanOrder& order, const ColumnPtr& value, int op, bool reverse);
+// The sorted order rank reads: sort_segments(keys, value; descending as asked, nulls last), the prefix of its segment heads and the runs of equal values.
+struct RankOrder { sort::SortedSegments seg; Buf seg_prefix; sort::ValueRuns runs; std::string desc; };      // desc: "rank[sorted segments: <sort>]"
+RankOrder rank_order(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, bool descending);
+// One ranking method over `order`: O(1) per sorted position.  PLX_F64 ("average") or PLX_U32, the validity of the ranked column
+ColumnPtr rank_column(const RankOrder& order, int method);
+}  // namespace cumulative
 }  // namespace plx

@@ -129,6 +129,31 @@ class Expr:
         keys = check_over(partition_by, order_by, mapping_strategy)
         return Expr("window", lhs=self, value=keys)
 
+    # -- cumulative and ranking functions ---------------------------------------------------
+    def cum_sum(self, *, reverse: bool = False) -> "Expr":
+        """The running sum (py-polars expr.cum_sum): one value per row, a null row stays null and adds nothing.  Int8 / Int16 / UInt8 / UInt16 -> Int64, Boolean ->
+        UInt32, every other integer and float dtype keeps its own; integers wrap, Float32 accumulates as the sum aggregate does.  reverse=True scans from the last
+        row to the first.  Plain: over the whole column; directly under .over(keys): within each partition, in the frame's row order."""
+        return Expr("cum", F.CUM_SUM, self, value=check_reverse(reverse, "cum_sum"))
+
+    def cum_min(self, *, reverse: bool = False) -> "Expr":
+        """The running minimum (py-polars expr.cum_min): the dtype stays, a null row stays null; a NaN is ignored unless every valid value so far is NaN, as min() does."""
+        return Expr("cum", F.CUM_MIN, self, value=check_reverse(reverse, "cum_min"))
+
+    def cum_max(self, *, reverse: bool = False) -> "Expr":
+        """The running maximum (py-polars expr.cum_max); see cum_min."""
+        return Expr("cum", F.CUM_MAX, self, value=check_reverse(reverse, "cum_max"))
+
+    def cum_count(self, *, reverse: bool = False) -> "Expr":
+        """The number of non-null values up to and including the row (py-polars expr.cum_count): UInt32, never null; any dtype."""
+        return Expr("cum", F.CUM_COUNT, self, value=check_reverse(reverse, "cum_count"))
+
+    def rank(self, method: str = "average", *, descending: bool = False) -> "Expr":
+        """The rank of every value (py-polars expr.rank): method one of "average" (Float64), "min", "max", "dense", "ordinal" (UInt32).  A null row's rank is null and
+        nulls take no part.  Values rank in the sort's order (NaN greatest, all NaNs tie, -0 == +0); "ordinal" breaks ties by row order, also when descending.
+        Plain: over the whole column; directly under .over(keys): within each partition."""
+        return Expr("rank", F.RANK_METHODS[check_rank_method(method)], self, value=(method, check_reverse(descending, "rank", "descending")))
+
     # -- misc -----------------------------------------------------------------------------
     @property
     def str(self) -> "ExprStringNameSpace":
@@ -152,6 +177,8 @@ class Expr:
             return f"{self.lhs!r}.median()" if self.value == (0.5, "linear") else f"{self.lhs!r}.quantile({self.value[0]!r}, {self.value[1]!r})"
         if self.kind == "agg" and self.op == F.AGG_N_UNIQUE: return f"{self.lhs!r}.n_unique()"
         if self.kind == "agg": return f"{self.lhs!r}.agg{self.op}()"
+        if self.kind == "cum": return f"{self.lhs!r}.{CUM_NAMES[self.op]}({'reverse=True' if self.value else ''})"
+        if self.kind == "rank": return f"{self.lhs!r}.rank({self.value[0]!r}{', descending=True' if self.value[1] else ''})"
         if self.kind == "window": return f"{self.lhs!r}.over([{', '.join(repr(k) for k in self.value)}])"
         if self.kind == "alias": return f"{self.lhs!r}.alias({self.name!r})"
         if self.kind == "cast": return f"{self.lhs!r}.cast({self.dtype})"
@@ -187,6 +214,23 @@ def check_keep(keep: Any) -> str:
     if not isinstance(keep, str) or keep not in F.UNIQUE_KEEPS:
         raise ValueError(f"keep must be one of {list(F.UNIQUE_KEEPS)}, got {keep!r}")
     return keep
+
+
+CUM_NAMES = {F.CUM_SUM: "cum_sum", F.CUM_MIN: "cum_min", F.CUM_MAX: "cum_max", F.CUM_COUNT: "cum_count"}
+
+
+def check_reverse(flag: Any, what: str, name: str = "reverse") -> bool:
+    """reverse= of a cumulative function / descending= of rank: a bool; anything else is a TypeError (a truthy string would otherwise turn the scan around)."""
+    if not isinstance(flag, (bool, np.bool_)):
+        raise TypeError(f"{what}({name}=...) takes a bool, got {flag!r}")
+    return bool(flag)
+
+
+def check_rank_method(method: Any) -> str:
+    """The ranking method: one of "average", "min", "max", "dense", "ordinal" ("random" is not built)."""
+    if not isinstance(method, str) or method not in F.RANK_METHODS:
+        raise ValueError(f"rank method must be one of {list(F.RANK_METHODS)}, got {method!r}")
+    return method
 
 
 def check_over(partition_by: Any, order_by: Any = None, mapping_strategy: Any = "group_to_rows") -> tuple:
@@ -408,6 +452,26 @@ def quantile(name: str, quantile: float, interpolation: str = "nearest") -> Expr
 
 def n_unique(name: str) -> Expr:
     return col(name).n_unique()
+
+
+def cum_sum(name: str, *, reverse: bool = False) -> Expr:
+    return col(name).cum_sum(reverse=reverse)
+
+
+def cum_min(name: str, *, reverse: bool = False) -> Expr:
+    return col(name).cum_min(reverse=reverse)
+
+
+def cum_max(name: str, *, reverse: bool = False) -> Expr:
+    return col(name).cum_max(reverse=reverse)
+
+
+def cum_count(name: str, *, reverse: bool = False) -> Expr:
+    return col(name).cum_count(reverse=reverse)
+
+
+def rank(name: str, method: str = "average", *, descending: bool = False) -> Expr:
+    return col(name).rank(method, descending=descending)
 
 
 _EPOCH = _dt.date(1970, 1, 1)

@@ -451,6 +451,44 @@ class Series:
         F.set_plan_note(plan)
         return out
 
+    # -- cumulative and ranking functions (plx_cumulative / plx_rank over the whole column) --------
+    def _cumulative(self, op: int, reverse: Any, what: str) -> "Series":
+        from .expr import check_reverse
+        reverse = check_reverse(reverse, what)
+        out_dt = P.cum_result_dtype(op, self.dtype)          # TypeError: a dtype the function does not take
+        F.ensure_init()
+        F.set_plan_note(None)
+        h = C.c_uint64()
+        F.check(F.lib().plx_cumulative(None, 0, self._h, op, int(reverse), C.byref(h)))
+        return Series._from_handle(self.name, h.value, out_dt)
+
+    def cum_sum(self, *, reverse: bool = False) -> "Series":
+        """The running sum (Series.cum_sum): nulls stay null and add nothing; narrow integers -> Int64, Boolean -> UInt32; integers wrap."""
+        return self._cumulative(F.CUM_SUM, reverse, "cum_sum")
+
+    def cum_min(self, *, reverse: bool = False) -> "Series":
+        """The running minimum (Series.cum_min): the dtype stays; a NaN is ignored unless every valid value so far is NaN."""
+        return self._cumulative(F.CUM_MIN, reverse, "cum_min")
+
+    def cum_max(self, *, reverse: bool = False) -> "Series":
+        """The running maximum (Series.cum_max)."""
+        return self._cumulative(F.CUM_MAX, reverse, "cum_max")
+
+    def cum_count(self, *, reverse: bool = False) -> "Series":
+        """The number of non-null values up to and including each row (Series.cum_count): UInt32, never null."""
+        return self._cumulative(F.CUM_COUNT, reverse, "cum_count")
+
+    def rank(self, method: str = "average", *, descending: bool = False) -> "Series":
+        """The rank of every value (Series.rank): "average" (Float64), "min", "max", "dense", "ordinal" (UInt32); a null row's rank is null."""
+        from .expr import check_rank_method, check_reverse
+        method, descending = check_rank_method(method), check_reverse(descending, "rank", "descending")
+        out_dt = P.rank_result_dtype(method, self.dtype)
+        F.ensure_init()
+        F.set_plan_note(None)
+        h = C.c_uint64()
+        F.check(F.lib().plx_rank(None, 0, self._h, F.RANK_METHODS[method], int(descending), C.byref(h)))
+        return Series._from_handle(self.name, h.value, out_dt)
+
     @property
     def str(self) -> "SeriesStringNameSpace":
         """String predicates (starts_with / ends_with / contains of a literal) on a dictionary column or on a column of raw views."""
@@ -1069,6 +1107,7 @@ class LazyFrame:
         lines += P.describe_join_orders(self._node)
         lines += P.describe_distincts(self._node)
         lines += P.describe_windows(self._node)
+        lines += P.describe_cumulatives(self._node)
         if _io.has_file_scan(self._node):
             self._lower()
             lines += _io.describe_scans(self._node)

@@ -799,19 +799,20 @@ def simple_predicates(e: Expr) -> List[Pred]:
 
 
 def _row_preserving(exprs) -> bool:
-    """no aggregate anywhere: the node maps row i to row i"""
+    """no aggregate anywhere, and no cumulative / ranking expression (row i of its output depends on the rows around it, so no slice passes it): the node maps
+    row i to row i"""
     def walk(e) -> bool:
         if e is None:
             return True
-        if e.kind in ("agg", "len"):
+        if e.kind in ("agg", "len", "cum", "rank"):
             return False
         return all(walk(c) for c in e.children())
     return all(walk(e) for e in exprs) and any(expr_columns(e) for e in exprs)
 
 
 def _has_window(e: Optional[Expr]) -> bool:
-    """a window expression (f.over(keys)) anywhere in `e`"""
-    return e is not None and (e.kind == "window" or any(_has_window(c) for c in e.children()))
+    """a window expression (f.over(keys)) or a cumulative / ranking expression anywhere in `e`: both read every row of their input"""
+    return e is not None and (e.kind in ("window", "cum", "rank") or any(_has_window(c) for c in e.children()))
 
 
 def scan_under(node: P.Node):
@@ -837,7 +838,7 @@ def push_down(node: P.Node, needed: Optional[Set[str]] = None, preds: Optional[L
         cols = expr_columns(node.predicate)
         below = preds if preds is not None else []
         if _has_window(node.predicate):
-            # a window reads EVERY row of this filter's input: neither its own conjuncts nor the filters above it may drop a row group below it (a filter
+            # a window (and a cumulative / ranking expression) reads EVERY row of this filter's input: neither its own conjuncts nor the filters above it may drop a row group below it (a filter
             # under it still prunes: those rows never reach the window)
             push_down(node.input, None if needed is None else needed | cols, [])
             return

@@ -15,7 +15,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 from . import _ffi as F
 from . import datatypes as T
-from .expr import STR_MATCH_NAMES, Expr, dt_part_dtype, dt_unit, literal_physical, str_match_host, str_pattern_bytes
+from .expr import CUM_NAMES, STR_MATCH_NAMES, Expr, dt_part_dtype, dt_unit, literal_physical, str_match_host, str_pattern_bytes
 
 Schema = Dict[str, T.DataType]
 
@@ -84,13 +84,73 @@ def describe_windows(node: Node) -> List[str]:
     def walk(e):
         if e is None:
             return
-        if e.kind == "window":
+        f = e.lhs if e.kind == "window" else None
+        while f is not None and f.kind == "alias":
+            f = f.lhs
+        if e.kind == "window" and f.kind not in ("cum", "rank"):      # (a cumulative / ranking function under .over has its own line: describe_cumulatives)
             out.append(f"Window[{e.lhs!r} over [{', '.join(repr(k) for k in e.value)}], mapping=group_to_rows] in {node.kind}")
         for c in e.children():
             walk(c)
     for e in list(getattr(node, "exprs", None) or []) + [getattr(node, "predicate", None)]:
         walk(e)
     return out
+
+
+def describe_cumulatives(node: Node) -> List[str]:
+    """One line per cumulative / ranking expression under `node` (LazyFrame.explain): the function as written and its partition.  The route each one took is in the
+    physical plan of the last collect (`Cumulative{... route=cumulative[whole column] | cumulative[sorted rows: ...]}`, `Rank{... route=rank[sorted segments: ...]}`)."""
+    out: List[str] = []
+    for attr in ("input", "left", "right"):
+        child = getattr(node, attr, None)
+        if isinstance(child, Node):
+            out += describe_cumulatives(child)
+
+    def walk(e, keys):
+        if e is None:
+            return
+        if e.kind in ("cum", "rank"):
+            over = "the whole column" if keys is None else "[" + ", ".join(repr(k) for k in keys) + "]"
+            out.append(f"{'Rank' if e.kind == 'rank' else 'Cumulative'}[{e!r} over {over}] in {node.kind}")
+        if e.kind == "window":
+            f = e.lhs
+            while f is not None and f.kind == "alias":
+                f = f.lhs
+            if f is not None and f.kind in ("cum", "rank"):
+                walk(f, e.value)
+                return
+        for c in e.children():
+            walk(c, None)
+    for e in list(getattr(node, "exprs", None) or []) + [getattr(node, "predicate", None)]:
+        walk(e, None)
+    return out
+
+
+def has_row_function(e: Optional[Expr]) -> bool:
+    """a cumulative or ranking expression anywhere in `e`: like a window, it reads every row of its input"""
+    return e is not None and (e.kind in ("cum", "rank") or any(has_row_function(c) for c in e.children()))
+
+
+def cum_result_dtype(op: int, dt) -> T.DataType:
+    """Logical result dtype of a cumulative function over a `dt` operand; TypeError for an operand it does not take.  cum_sum follows the sum aggregate and takes no
+    temporal or Categorical operand; cum_min / cum_max keep the dtype (Date / Datetime included) and take no Categorical (codes are not lexical order); cum_count
+    takes anything."""
+    name = CUM_NAMES[op]
+    if op == F.CUM_COUNT:
+        return T.UInt32
+    if not isinstance(dt, T.DataType) or isinstance(dt, T.Categorical):
+        raise TypeError(f"{name}() needs an integer, float or Boolean expression{' (or a Date / Datetime one)' if op != F.CUM_SUM else ''}, got {dt}")
+    if op == F.CUM_SUM:
+        if not (dt.is_numeric() or dt == T.Boolean):        # Date / Datetime
+            raise TypeError(f"cum_sum() needs an integer, float or Boolean expression, got {dt}")
+        return sum_dtype(dt)
+    return dt
+
+
+def rank_result_dtype(method: str, dt) -> T.DataType:
+    """Float64 for "average", UInt32 for the other methods; TypeError for a Categorical operand (codes are not lexical order)."""
+    if not isinstance(dt, T.DataType) or isinstance(dt, T.Categorical):
+        raise TypeError(f"rank() needs an integer, float, Boolean, Date or Datetime expression, got {dt}")
+    return T.Float64 if method == "average" else T.UInt32
 
 
 def describe_join_orders(node: Node) -> List[str]:
@@ -242,7 +302,24 @@ class Lowering:
             else:
                 out = dt
             return self._push(kind=F.AE_AGG, op=e.op, lhs=idx), out
+        if k == "cum":
+            # x.cum_sum(reverse=...): AE_CUMULATIVE with the operand in lhs, the plx_cum_op in `op` and reverse in the literal slot (plx_aexpr.lit.u), as a date
+            # part's unit rides there.  The operand is a row-level expression: the refusals are by name, here, before anything runs
+            self._check_row_operand(e)
+            idx, dt = self.lower_expr(e.lhs, schema)
+            return self._push(kind=F.AE_CUMULATIVE, op=e.op, lhs=idx, lit=int(bool(e.value))), cum_result_dtype(e.op, dt)
+        if k == "rank":
+            self._check_row_operand(e)
+            idx, dt = self.lower_expr(e.lhs, schema)
+            method, descending = e.value
+            return self._push(kind=F.AE_RANK, op=F.RANK_METHODS[method], lhs=idx, lit=int(bool(descending))), rank_result_dtype(method, dt)
         if k == "window":
+            f = e.lhs
+            while f.kind == "alias":
+                f = f.lhs
+            if f.kind not in ("cum", "rank") and has_row_function(e.lhs):
+                raise TypeError(f"{e!r}: under .over() a function that mixes a cumulative / ranking expression with anything else is not built; put .over(keys) directly on "
+                                "the cumulative / ranking expression (and on each aggregate) and the arithmetic outside")
             # f.over(k1, k2, ...): AE_WINDOW with the function in lhs and the first link of the key chain in rhs; one AE_WINDOW_KEY link per key (lhs = the key,
             # rhs = the next link or -1).  The arena is topological, so the links are pushed last key first.  The engine checks that f aggregates and the keys do not
             fi, fdt = self.lower_expr(e.lhs, schema)
@@ -449,6 +526,21 @@ class Lowering:
         ai, adt, bi, bdt = self._coerce_pair(ai, adt, bi, bdt)
         return self._push(kind=F.AE_TERNARY, lhs=ai, rhs=bi, cond=pi), adt
 
+    def _check_row_operand(self, e: Expr) -> None:
+        """The operand of a cumulative / ranking expression is row-level: no aggregate, no window and no other cumulative / ranking expression inside."""
+        what = CUM_NAMES[e.op] if e.kind == "cum" else "rank"
+
+        def walk(x):
+            if x.kind in ("agg", "len"):
+                raise TypeError(f"{what}(): an aggregate ({x!r}) inside the operand of a cumulative / ranking expression is not built; the operand is a row-level expression")
+            if x.kind == "window":
+                raise TypeError(f"{what}(): a window expression ({x!r}) inside the operand of a cumulative / ranking expression is not built; compute it in with_columns first")
+            if x.kind in ("cum", "rank"):
+                raise TypeError(f"{what}(): a cumulative / ranking expression ({x!r}) inside the operand of another one is not built; compute the inner one in with_columns first")
+            for c in x.children():
+                walk(c)
+        walk(e.lhs)
+
     def _null_node(self, dt: T.DataType) -> int:
         return self._push(kind=F.AE_LITERAL, dtype=dt.physical, lit=0, is_null=1)
 
@@ -481,6 +573,10 @@ class Lowering:
         if k == "group_by":
             inp, schema = self.lower_node(n.input)
             keys, aggs, out_schema = [], [], {}
+            for e in list(n.keys) + list(n.aggs):
+                if has_row_function(e):
+                    raise TypeError(f"group_by: a cumulative / ranking expression ({e!r}) cannot stand in the keys or aggregates of a group_by: it keeps one value per "
+                                    "row; use it in select / with_columns, with .over(keys) for partitions")
             for e in n.keys:
                 idx, dt = self.lower_expr(e, schema)
                 keys.append(idx)
@@ -553,7 +649,7 @@ class Lowering:
                     a.lit.u = int(d["lit"]) & 0xFFFFFFFFFFFFFFFF
                 else:
                     a.lit.i = int(d["lit"])
-            if d["kind"] == F.AE_TEMPORAL or (d["kind"] == F.AE_AGG and d["op"] in (F.AGG_VAR, F.AGG_STD)):
+            if d["kind"] in (F.AE_TEMPORAL, F.AE_CUMULATIVE, F.AE_RANK) or (d["kind"] == F.AE_AGG and d["op"] in (F.AGG_VAR, F.AGG_STD)):
                 a.lit.u = int(d["lit"])            # the operand's time unit / the ddof of var and std rides in the literal slot, like a lookup bitmap's handle
             if d["kind"] == F.AE_AGG and d["op"] == F.AGG_QUANTILE:
                 a.lit.f64 = float(d["lit"])        # q (the interpolation went into the dtype slot with every other field)

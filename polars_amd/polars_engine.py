@@ -190,6 +190,26 @@ class Translator:
             if not keys:
                 raise NotSupported("window expression without partition_by")
             return E.Expr("window", lhs=self.expr(x.function), value=tuple(keys))
+        if kind == "Function":
+            # visitor/expr_nodes.rs Function: input (expression node ids), function_data = (name, *arguments), options.  The five that keep one value per row:
+            # ("cum_sum" | "cum_min" | "cum_max" | "cum_count", reverse) and ("rank", method, descending, seed).  Everything else is refused by name
+            data = tuple(getattr(x, "function_data", None) or ())
+            name = str(data[0]) if data else ""
+            inputs = list(getattr(x, "input", None) or [])
+            if name in F.CUM_OPS and len(inputs) == 1:
+                reverse = data[1] if len(data) > 1 else False
+                if not isinstance(reverse, bool):
+                    raise NotSupported(f"{name} with reverse={reverse!r}")
+                return E.Expr("cum", F.CUM_OPS[name], self.expr(inputs[0]), value=reverse)
+            if name == "rank" and len(inputs) == 1:
+                method = str(data[1]).lower() if len(data) > 1 else "average"
+                descending = data[2] if len(data) > 2 else False
+                if method not in F.RANK_METHODS:
+                    raise NotSupported(f"rank with method {method}: only {list(F.RANK_METHODS)} are built")
+                if not isinstance(descending, bool):
+                    raise NotSupported(f"rank with descending={descending!r}")
+                return E.Expr("rank", F.RANK_METHODS[method], self.expr(inputs[0]), value=(method, descending))
+            raise NotSupported(f"function {name or '?'}")
         raise NotSupported(f"expression node {kind}")
 
     def named(self, e: Any) -> E.Expr:

@@ -64,6 +64,22 @@ def share_of_flag_total(lineitem):
             .filter(c("l_quantity") > c("l_quantity").median().over("l_returnflag")))
 
 
+def running_revenue_by_flag(lineitem):
+    """with_columns((l_extendedprice * (1 - l_discount)).cum_sum().over(l_returnflag, l_linestatus).alias("running_revenue")) -- every line's revenue added to the
+    revenue of the lines of its (flag, status) before it, in the frame's row order.  One stable sort of the rows by the two keys, one head mask and one segmented scan
+    in three launches; height and row order stay the frame's"""
+    c = E.col
+    return lineitem.with_columns((c("l_extendedprice") * (1.0 - c("l_discount"))).cum_sum().over("l_returnflag", "l_linestatus").alias("running_revenue"))
+
+
+def top3_price_per_flag(lineitem):
+    """filter(l_extendedprice.rank("ordinal", descending=True).over(l_returnflag, l_linestatus) <= 3) -- the three most expensive lines of every (flag, status), in
+    the frame's row order; ordinal ranks break ties by row order, so exactly three rows of every partition stay.  One sort by (flag, status, price descending) and one
+    O(1)-per-row rank kernel"""
+    c = E.col
+    return lineitem.filter(c("l_extendedprice").rank("ordinal", descending=True).over("l_returnflag", "l_linestatus") <= 3)
+
+
 def q1(lineitem, cutoff=Q1_CUTOFF):
     """TPC-H Q1; the final sort by (flag, status) happens on the host."""
     c = E.col
