@@ -642,6 +642,18 @@ const char* plx_last_plan_encodings(void);
 /* Rows per wave tile of the process's last fused aggregate scan (whole-frame aggregates or the LDS group table): 512 when it ran over wide tiles, 128 when it did
  * not, 0 before the first.  For tests; the plan description does not say. */
 int32_t plx_last_scan_tile_rows(void);
+/* LDS cells per group that the process's last LDS-table scan held: the program's aggregate count, or fewer when aggregates share cells (count, integer sum and the
+ * f64 sum behind a mean of one small non-negative integer input: 5 for TPC-H Q1's 7 aggregates); 0 before the first.  plx_set_shared_cells(0) keeps one cell per
+ * aggregate, like PLX_SHARED_CELLS=0 in the environment (read once, at the first scan). */
+int32_t plx_last_lds_cells(void);
+void plx_set_shared_cells(int32_t on);
+/* The cell plan as a pure function (no GPU needed).  The program is AOT shape `static_shape_id`, or (-1) the arrays: ops = n_ops x {code, dst, a, b, c}, aggs =
+ * n_aggs x {kind, src}.  known / lo / hi: per aggregate, the bound lo <= v <= hi on its source; wg_rows: rows one workgroup can add to its table.  out gets
+ * {cells per group, shift, cell[k] for every aggregate, the aggregate whose cell k is read from or -1 for every aggregate}; returns the aggregate count, -1 on bad
+ * arguments.  plx_lds_wg_rows: the row bound for a grid of `grid` workgroups over 512-row wide tiles (wide != 0) or 128-row tiles. */
+int32_t plx_cell_plan(int32_t static_shape_id, int32_t n_inputs, const int32_t* dtypes, const int32_t* nullable, int32_t n_ops, const uint8_t* ops, int32_t n_aggs, const uint8_t* aggs,
+                      const uint8_t* known, const int64_t* lo, const int64_t* hi, uint64_t wg_rows, uint64_t n_rows, int32_t* out);
+uint64_t plx_lds_wg_rows(int64_t n_rows, int32_t grid, int32_t wide);
 /* The launchers' choice between the two tile sizes, as a pure function (no GPU needed): 1 = 512-row wide tiles.  They are chosen exactly when the program is compiled
  * (ahead of time or at run time), a row is at most 16 bytes of integer or f64 columns (no Boolean, no f32), one of them narrower than eight bytes, no input is nullable or carries a bitmap, n_rows holds one whole tile,
  * every values pointer is aligned to eight rows of its column, and the knob (PLX_WIDE_TILES, default on) is on.  dtypes / nullable / values / validity: n_inputs

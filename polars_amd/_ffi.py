@@ -251,6 +251,11 @@ SIGNATURES = {
     "plx_last_plan_description": (C.c_char_p, []),
     "plx_last_plan_encodings": (C.c_char_p, []),
     "plx_last_scan_tile_rows": (C.c_int32, []),
+    "plx_last_lds_cells": (C.c_int32, []),
+    "plx_set_shared_cells": (None, [C.c_int32]),
+    "plx_cell_plan": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_uint8),
+                                  C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_uint64, C.c_uint64, C.POINTER(C.c_int32)]),
+    "plx_lds_wg_rows": (C.c_uint64, [C.c_int64, C.c_int32, C.c_int32]),
     "plx_wide_tiles_choice": (C.c_int32, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "plx_profile_enable": (C.c_int, [C.c_int]),
     "plx_profile_fetch": (C.c_int, [C.POINTER(ProfileRecord), C.c_int32, _i32p]),
@@ -324,6 +329,32 @@ def last_plan_encodings() -> str:
 def last_scan_tile_rows() -> int:
     """Rows per wave tile of the last fused aggregate scan: 512 (wide tiles), 128, or 0 before the first."""
     return int(lib().plx_last_scan_tile_rows())
+
+
+def last_lds_cells() -> int:
+    """LDS cells per group the last LDS-table scan held: the aggregate count, or fewer with shared cells; 0 before the first."""
+    return int(lib().plx_last_lds_cells())
+
+
+def set_shared_cells(on: bool) -> None:
+    """The switch behind PLX_SHARED_CELLS: False keeps one LDS cell per aggregate."""
+    lib().plx_set_shared_cells(int(bool(on)))
+
+
+def cell_plan(facts, wg_rows, n_rows, static_shape_id=-1, dtypes=(), nullable=(), ops=(), aggs=()):
+    """plx_cell_plan: facts = [(known, lo, hi)] per aggregate -> (cells, shift, [cell of k], [aggregate k is read from, or -1]); no GPU needed."""
+    n_aggs = len(facts)
+    ni, no = len(dtypes), len(ops)
+    out = (C.c_int32 * (2 + 2 * 16))()
+    flat_ops = [int(x) for op in ops for x in op]
+    flat_aggs = [int(x) for a in aggs for x in a]
+    r = lib().plx_cell_plan(int(static_shape_id), ni, (C.c_int32 * max(ni, 1))(*[int(d) for d in dtypes]), (C.c_int32 * max(ni, 1))(*[int(x) for x in nullable]),
+                            no, (C.c_uint8 * max(len(flat_ops), 1))(*flat_ops), len(aggs), (C.c_uint8 * max(len(flat_aggs), 1))(*flat_aggs),
+                            (C.c_uint8 * 16)(*[int(f[0]) for f in facts]), (C.c_int64 * 16)(*[int(f[1]) for f in facts]), (C.c_int64 * 16)(*[int(f[2]) for f in facts]),
+                            int(wg_rows), int(n_rows), out)
+    if r < 0:
+        raise ValueError("plx_cell_plan: bad arguments")
+    return int(out[0]), int(out[1]), [int(out[2 + k]) for k in range(r)], [int(out[2 + r + k]) for k in range(r)]
 
 
 def wide_tiles_choice(compiled, knob_on, n_rows, dtypes, nullable, values, validity) -> int:

@@ -1265,6 +1265,32 @@ int plx_execute_plan(const plx_ir* ir, int32_t n_ir, const plx_aexpr* exprs, int
 const char* plx_last_plan_description(void) { return t_plan_desc.c_str(); }
 const char* plx_last_plan_encodings(void) { return t_plan_encoded.c_str(); }
 int32_t plx_last_scan_tile_rows(void) { return k::last_scan_tile_rows(); }
+int32_t plx_last_lds_cells(void) { return k::last_lds_cells(); }
+void plx_set_shared_cells(int32_t on) { k::set_shared_cells(on != 0); }
+uint64_t plx_lds_wg_rows(int64_t n_rows, int32_t grid, int32_t wide) { return (n_rows < 0 || grid < 1) ? 0 : k::lds_agg_wg_rows_of(n_rows, grid, wide != 0); }
+int32_t plx_cell_plan(int32_t static_shape_id, int32_t n_inputs, const int32_t* dtypes, const int32_t* nullable, int32_t n_ops, const uint8_t* ops, int32_t n_aggs, const uint8_t* aggs,
+                      const uint8_t* known, const int64_t* lo, const int64_t* hi, uint64_t wg_rows, uint64_t n_rows, int32_t* out) {
+  if (!known || !lo || !hi || !out) return -1;
+  fused::Shape sh{};
+  if (static_shape_id >= 0) {
+    if (static_shape_id >= fused::kNumStaticShapes) return -1;
+    sh = fused::static_shape(static_shape_id);
+  } else {
+    if (n_inputs < 0 || n_inputs > fused::kMaxInputs || n_ops < 0 || n_ops > fused::kMaxOps || n_aggs < 0 || n_aggs > fused::kMaxAggs) return -1;
+    if ((n_inputs && (!dtypes || !nullable)) || (n_ops && !ops) || (n_aggs && !aggs)) return -1;
+    sh.n_inputs = (uint8_t)n_inputs; sh.n_ops = (uint8_t)n_ops; sh.n_aggs = (uint8_t)n_aggs; sh.pred = fused::kNone; sh.key = fused::kNone;
+    for (int i = 0; i < n_inputs; i++) { sh.in_dtype[i] = (uint8_t)dtypes[i]; sh.in_nullable[i] = (uint8_t)(nullable[i] != 0); }
+    for (int i = 0; i < n_ops; i++) sh.ops[i] = fused::Op{ops[5 * i], ops[5 * i + 1], ops[5 * i + 2], ops[5 * i + 3], ops[5 * i + 4], {0, 0, 0}};
+    for (int i = 0; i < n_aggs; i++) sh.aggs[i] = fused::Agg{aggs[2 * i], aggs[2 * i + 1]};
+  }
+  fused::AggFacts f{};
+  f.wg_rows = wg_rows; f.n_rows = n_rows;
+  for (int k = 0; k < sh.n_aggs; k++) { f.known[k] = known[k]; f.lo[k] = lo[k]; f.hi[k] = hi[k]; }
+  const fused::CellPlan p = fused::plan_cells(sh, f);
+  out[0] = p.n_cells; out[1] = p.shift;
+  for (int k = 0; k < sh.n_aggs; k++) { out[2 + k] = p.cell[k]; out[2 + sh.n_aggs + k] = p.from[k] == fused::kNone ? -1 : (int)p.from[k]; }
+  return sh.n_aggs;
+}
 int32_t plx_wide_tiles_choice(int32_t compiled, int32_t knob_on, int64_t n_rows, int32_t n_inputs, const int32_t* dtypes, const int32_t* nullable, const uint64_t* values,
                               const uint64_t* validity) {
   if (n_inputs < 0 || n_inputs > fused::kMaxInputs || (n_inputs && (!dtypes || !nullable || !values || !validity))) return -1;
@@ -1397,6 +1423,12 @@ int plx_jit_selftest(const plx_ir* ir, int32_t n_ir, const plx_aexpr* exprs, int
   for (auto& j : jobs) {
     const std::string log = jit::selftest(j.first, j.second);
     if (!log.empty()) fail(PLX_ERR_INVALID, "jit selftest failed: " + log.substr(0, 4000));
+    // the LDS table with shared cells, where the shape admits a plan at all: the plan it has when every bound holds
+    if (j.second != jit::LDSAGG && j.second != jit::LDSAGG_WIDE) continue;
+    const uint32_t code = fused::full_cell_plan_code(j.first);
+    if (fused::cell_plan_is_identity(fused::cell_plan_from_code(j.first, code), j.first)) continue;
+    const std::string log2 = jit::selftest(j.first, j.second == jit::LDSAGG ? jit::LDSCELL : jit::LDSCELL_WIDE, code);
+    if (!log2.empty()) fail(PLX_ERR_INVALID, "jit selftest failed: " + log2.substr(0, 4000));
   }
   PLX_CATCH
 }

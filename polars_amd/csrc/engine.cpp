@@ -1455,11 +1455,51 @@ void finish_table(GroupByRun& q, const Buf& cells, int64_t G, const Buf& oob) {
   check_oob_flag(oob);
   q.res.key_valid = nullptr;  // packed keys carry their own null codes
 }
+// What the library KNOWS about the values of input i of the running program (q.sh / q.args: plain, or rewritten over shadows): the codes of an affine shadow span their
+// width, a narrow integer column its type, a 64-bit column its measured range -- exact statistics only, never bounds a caller declared or the planner assumed.
+bool input_value_bounds(const GroupByRun& q, int i, int64_t* lo, int64_t* hi) {
+  if (i < 0 || i >= (int)q.c.input_cols.size() || q.args.in[i].validity) return false;
+  const ColumnPtr& col = q.c.cols[q.c.input_cols[i]];
+  const std::shared_ptr<EncodedShadow> s = std::atomic_load(&col->shadow);
+  const bool codes = s && s->kind == EncodedShadow::kAffine && s->codes && q.args.in[i].values == s->codes->ptr;
+  if (!codes && q.args.in[i].values != col->data()) {
+    // rows [off, off + n) of the column: its statistics cover them
+    const char* p = (const char*)q.args.in[i].values; const char* b = (const char*)col->data();
+    if (!b || p < b || p >= b + (size_t)col->len * dtype_width(col->dtype) || q.sh.in_dtype[i] != col->dtype) return false;
+  }
+  switch (q.sh.in_dtype[i]) {
+    case PLX_U8: *lo = 0; *hi = 255; return true;
+    case PLX_U16: *lo = 0; *hi = 65535; return true;
+    case PLX_U32: *lo = 0; *hi = 0xffffffffll; return true;
+    case PLX_I8: *lo = -128; *hi = 127; return true;
+    case PLX_I16: *lo = -32768; *hi = 32767; return true;
+    case PLX_I32: *lo = INT32_MIN; *hi = INT32_MAX; return true;
+    case PLX_I64: case PLX_U64:
+      if (codes || col->range_state != 1 || !col->range_trusted || col->range_assumed) return false;
+      if (q.sh.in_dtype[i] == PLX_U64 && col->range_min < 0) return false;
+      *lo = col->range_min; *hi = col->range_max; return true;
+    default: return false;
+  }
+}
+// the cell plan of this scan (fused_cells.hpp): facts about the sources of its integer sums, from the columns behind the inputs
+CellPlan shared_cells_plan(const GroupByRun& q) {
+  AggFacts f{};
+  f.n_rows = (uint64_t)q.args.n_rows; f.wg_rows = k::lds_agg_wg_rows(q.args.n_rows);
+  for (int k = 0; k < q.sh.n_aggs; k++) {
+    if (q.sh.aggs[k].kind != AGG_SUM_I) continue;
+    const int in = affine_source_input(q.sh, q.sh.aggs[k].src);
+    int64_t lo = 0, hi = 0;
+    if (in < 0 || !input_value_bounds(q, in, &lo, &hi) || !affine_source_interval(q.sh, q.args, q.sh.aggs[k].src, &lo, &hi)) continue;
+    f.known[k] = 1; f.lo[k] = lo; f.hi[k] = hi;
+  }
+  return plan_cells(q.sh, f);
+}
 void lds_table(GroupByRun& q) {
   const int G = 1 << q.kp.total_bits;
   Buf cells = dev_alloc(sizeof(uint64_t) * (size_t)G * q.sh.n_aggs);
   Buf oob = untrusted_key_bounds(q.c) ? dev_alloc_zero(8) : nullptr;      // key bounds nobody measured: the sink reports a group id outside the table
-  k::fused_lds_agg(q.sh, q.args, G, q.static_id, cells->as<uint64_t>(), oob ? oob->as<unsigned int>() : nullptr);
+  const CellPlan cell_plan = shared_cells_plan(q);
+  k::fused_lds_agg(q.sh, q.args, G, q.static_id, cells->as<uint64_t>(), oob ? oob->as<unsigned int>() : nullptr, &cell_plan);
   q.desc += scan_tag(q.static_id, q.args.n_rows) + "lds_table(G=" + std::to_string(G) + ",copies=" + std::to_string(k::lds_agg_copies(G, q.sh.n_aggs)) + ")";
   finish_table(q, cells, G, oob);
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include <type_traits>
 
+#include "fused_cells.hpp"
 #include "fused_device.hpp"
 
 namespace plx {
@@ -109,6 +110,84 @@ struct LdsAggSink {
     }
   }
 };
+
+// ---- sink: the same LDS table with shared cells (fused_cells.hpp: the plan is a compile-time constant of the kernel) -----------------
+// Layout lds[(g * NC + cell) * C + copy] with NC = plan.n_cells <= n_aggs.  The packed cell takes ONE ds_add_u64 of (1 << shift) + v per row for the row count and
+// the integer sum; a derived aggregate issues nothing (its OP_I2F is then dead code in the compiled program).  finish folds the copies of every cell into copy 0, then
+// writes the very table LdsAggSink writes -- [G][n_aggs] partials, or the same additions to global_acc -- with count and sum unpacked and the derived f64 sum
+// converted once from the exact integer sum.
+template <class P, uint32_t CODE>
+struct LdsCellSink {
+  static constexpr CellPlan kPlan = cell_plan_from_code(P::shape(), CODE);
+  static constexpr int NC = kPlan.n_cells;
+  struct Params {
+    unsigned long long* partials;    // as LdsAggSink::Params
+    unsigned long long* global_acc;
+    int n_groups;
+    int copies;                      // power of two, sized from NC cells a group (lds_agg_copies)
+    unsigned int* oob;
+    unsigned int shift;              // packed cell: count << shift | sum (fused_cells.hpp packed_shift)
+  };
+  template <class S> __device__ __forceinline__ void init(const S& sh, const Params& p) {
+    extern __shared__ unsigned long long lds_tbl[];
+    const int cells = p.n_groups * NC;
+    for (int i = threadIdx.x; i < cells * p.copies; i += blockDim.x) lds_tbl[i] = agg_identity_dev(sh.aggs[kPlan.owner[(i / p.copies) % NC]].kind);      // (packed: AGG_SUM_I, 0)
+    __syncthreads();
+  }
+  template <class S, class RF> __device__ __forceinline__ void consume(const S& sh, const RF& rf, const bool pass[kRows], int64_t row0, const Params& p) {
+    extern __shared__ unsigned long long lds_tbl[];
+    constexpr CellPlan pl = kPlan;
+    const int copy = lane_id() & (p.copies - 1);
+#pragma unroll
+    for (int r = 0; r < kRows; r++) {
+      if (!pass[r]) continue;
+      const uint64_t gid64 = rf.get(r, sh.key);
+      if (gid64 >= (uint64_t)p.n_groups) { if (p.oob) *p.oob = 1u; continue; }   // see LdsAggSink
+      const uint32_t gid = (uint32_t)gid64;
+      unsigned long long* cells = lds_tbl + (size_t)gid * NC * p.copies + copy;
+#pragma unroll
+      for (int k = 0; k < kMaxAggs; k++) {
+        if (k < sh.n_aggs) {
+          if (pl.from[k] != kNone) continue;      // read from another aggregate's cell at finish
+          const Agg ag = sh.aggs[k];
+          uint64_t v = rf.get(r, ag.src);
+          if (k == pl.packed) { atomicAdd(cells + pl.cell[k] * p.copies, (unsigned long long)packed_row(p.shift, v)); continue; }      // a non-nullable source: every row counts
+          bool valid = (rf.getv(ag.src) >> r) & 1;
+          if ((ag.kind == AGG_SUM_F || ag.kind == AGG_SUM_I || ag.kind == AGG_COUNT) && !valid) continue;
+          uint64_t x = agg_row_value(ag.kind, v, true, valid, (uint64_t)(row0 + r));
+          lds_atomic_agg(ag.kind, cells + pl.cell[k] * p.copies, x);
+        }
+      }
+    }
+  }
+  template <class S> __device__ __forceinline__ void finish(const S& sh, const Params& p) {
+    extern __shared__ unsigned long long lds_tbl[];
+    constexpr CellPlan pl = kPlan;
+    __syncthreads();
+    const int held = p.n_groups * NC;
+    for (int i = threadIdx.x; i < held; i += blockDim.x) {      // fold: every cell's copies into its copy 0 (one thread per cell: no other thread touches these words)
+      const uint8_t kind = sh.aggs[pl.owner[i % NC]].kind;
+      uint64_t x = lds_tbl[(size_t)i * p.copies];
+      for (int c = 1; c < p.copies; c++) x = agg_combine(kind, x, lds_tbl[(size_t)i * p.copies + c]);
+      lds_tbl[(size_t)i * p.copies] = x;
+    }
+    __syncthreads();
+    const int cells = p.n_groups * sh.n_aggs;
+    for (int i = threadIdx.x; i < cells; i += blockDim.x) {
+      const int g = i / sh.n_aggs, k = i % sh.n_aggs;
+      const uint8_t kind = sh.aggs[k].kind;
+      uint64_t x = lds_tbl[((size_t)g * NC + pl.cell[k]) * p.copies];
+      if (pl.packed != kNone && pl.cell[k] == pl.cell[pl.packed]) {
+        x = k == pl.packed_len ? packed_count(x, p.shift) : packed_sum(x, p.shift);
+        if (k != pl.packed && k != pl.packed_len) x = as_u((double)(long long)x);      // derived from the packed sum
+      } else if (pl.from[k] != kNone) x = as_u((double)(long long)x);                 // derived from a plain integer cell
+      if (p.global_acc) { if (x != agg_identity_dev(kind) || kind == AGG_SUM_F) atomic_agg(kind, p.global_acc + i, x); }
+      else p.partials[(size_t)blockIdx.x * cells + i] = x;
+    }
+  }
+};
+template <class Sink> struct is_lds_table_sink : std::is_same<Sink, LdsAggSink> {};
+template <class P, uint32_t CODE> struct is_lds_table_sink<LdsCellSink<P, CODE>> : std::true_type {};
 
 // ---- sink: direct-address table (dense integer keys) ---------------------------------
 struct DenseAggSink {
@@ -567,7 +646,7 @@ __host__ __device__ constexpr bool late_probe() {
 // the two aggregate sinks over a compile-time program with narrow rows: the loads of inputs the shape declares non-nullable do not look for a bitmap (load_input)
 template <class P, class Sink>
 __host__ __device__ constexpr bool trust_nullable() {
-  if constexpr (P::kStatic && (std::is_same<Sink, LdsAggSink>::value || std::is_same<Sink, RegAggSink>::value)) return narrow_rows(P::shape());
+  if constexpr (P::kStatic && (is_lds_table_sink<Sink>::value || std::is_same<Sink, RegAggSink>::value)) return narrow_rows(P::shape());
   else return false;
 }
 // ... and those whose inputs are ALL non-nullable fixed-width columns have a wide-tile form (fused_device.hpp wide_load); the launcher picks it when the pointers allow

@@ -32,12 +32,14 @@ std::map<std::string, Entry> g_cache;
 int g_compiled = 0;
 double g_ms = 0;
 
-bool wide_tiles(Sink s) { return s == REGAGG_WIDE || s == LDSAGG_WIDE; }
+bool wide_tiles(Sink s) { return s == REGAGG_WIDE || s == LDSAGG_WIDE || s == LDSCELL_WIDE; }
+bool shared_cells(Sink s) { return s == LDSCELL || s == LDSCELL_WIDE; }
 const char* sink_type(Sink s) {
   static const char* n[] = {"RegAggSink", "LdsAggSink", "DenseAggSink", "HashAggSink", "WideAggSink", "JoinBuildSink", "ProbeAggSink", "DirectBuildSink", "DirectProbeAggSink", "BitmapBuildSink",
                             "part_count", "part_scatter", "part_agg", "part2_scatter_hash", "part2_scatter_direct", "part2_agg_hash", "part2_agg_direct", "part2_scatter_hash_t2", "part2_scatter_direct_t2"};
   if (s == REGAGG_WIDE) return "RegAggSink";
   if (s == LDSAGG_WIDE) return "LdsAggSink";
+  if (shared_cells(s)) return "LdsCellSink";
   if (s == PART3_AGG_PAIRV) return "part3_agg";
   if (s >= PART3_SCATTER_PAIRV && s < PART3_AGG_PAIRV) return "part3_scatter";
   if (s == PART3_AGG_PAIR || s == PART3_AGG_PAIR_DIRECT) return "part3_agg";
@@ -84,19 +86,20 @@ uint64_t fnv1a(const std::string& s, uint64_t h = 0xcbf29ce484222325ull) { for (
 
 // Every run-time-compiled kernel gets a symbol of its own: plx_jit_<kind>_<sink number>_<8 hex digits of the program shape>.  Tracers (rocprofv3 --kernel-trace /
 // --pmc) key their rows by symbol: under one shared name the scatter and the aggregation pass of a partitioned group-by were one row of the statistics.
-std::string kernel_symbol(const Shape& sh, Sink sink) {
+std::string kernel_symbol(const Shape& sh, Sink sink, uint32_t cell_code) {
   std::string key((const char*)&sh, sizeof(Shape));
   key.push_back((char)sink);
+  if (shared_cells(sink)) key.append((const char*)&cell_code, sizeof cell_code);
   char out[96];
   snprintf(out, sizeof out, "plx_jit_%s_%d_%08x", sink_type(sink), (int)sink, (unsigned)(fnv1a(key) & 0xffffffffu));
   return out;
 }
 
-std::string source_for(const Shape& sh, Sink sink) {
+std::string source_for(const Shape& sh, Sink sink, uint32_t cell_code) {
   std::ostringstream o;
-  const std::string sym = kernel_symbol(sh, sink);
+  const std::string sym = kernel_symbol(sh, sink, cell_code);
   o << "#define plx_jit_kernel " << sym << "\n";
-  o << ((sink == BALLOT || sink == DIRECT_HITS || wide_tiles(sink)) ? "#include \"fused_sinks.hpp\"\n" : sink >= PART3_SCATTER ? "#include \"partition3_device.hpp\"\n" : sink >= PART2_SCATTER_HASH ? "#include \"partition2_device.hpp\"\n" : sink >= PART_COUNT ? "#include \"partition_device.hpp\"\n" : "#include \"fused_sinks.hpp\"\n") << "namespace plx { namespace k {\n"
+  o << ((sink == BALLOT || sink == DIRECT_HITS || wide_tiles(sink) || shared_cells(sink)) ? "#include \"fused_sinks.hpp\"\n" : sink >= PART3_SCATTER ? "#include \"partition3_device.hpp\"\n" : sink >= PART2_SCATTER_HASH ? "#include \"partition2_device.hpp\"\n" : sink >= PART_COUNT ? "#include \"partition_device.hpp\"\n" : "#include \"fused_sinks.hpp\"\n") << "namespace plx { namespace k {\n"
        "struct JitProg {\n  static constexpr bool kStatic = true; static constexpr int kId = -2;\n  static constexpr Shape shape() {\n    Shape s{};\n";
   o << "    s.n_inputs = " << (int)sh.n_inputs << "; s.n_ops = " << (int)sh.n_ops << "; s.n_aggs = " << (int)sh.n_aggs << "; s.pred = " << (int)sh.pred
     << "; s.key = " << (int)sh.key << "; s.n_keys = " << (int)sh.n_keys << ";\n";
@@ -130,6 +133,11 @@ std::string source_for(const Shape& sh, Sink sink) {
            "  part2_agg_body<Shape, " << (sink == PART2_AGG_DIRECT ? 1 : 0) << ", p2_agg_chunks_in_flight(cl.rec_words)>(csh, cl, pp, ap);\n}\n}}\n";
       break;
     default:
+      if (shared_cells(sink)) {
+        o << "extern \"C\" __global__ __launch_bounds__(kBlock) void plx_jit_kernel(Shape dsh, Args args, LdsCellSink<JitProg, " << cell_code << "u>::Params sp) {\n"
+             "  fused_scan_body<JitProg, LdsCellSink<JitProg, " << cell_code << "u>" << (wide_tiles(sink) ? ", true" : "") << ">(dsh, args, sp);\n}\n}}\n";
+        break;
+      }
       if (wide_tiles(sink)) {
         o << "extern \"C\" __global__ __launch_bounds__(kBlock) void plx_jit_kernel(Shape dsh, Args args, " << sink_type(sink)
           << "::Params sp) {\n  fused_scan_body<JitProg, " << sink_type(sink) << ", true>(dsh, args, sp);\n}\n}}\n";
@@ -206,7 +214,7 @@ std::string cache_dir() {
 std::string headers_fingerprint() {   // the device headers the generated source includes: a stale cache entry must never survive an upgrade
   static const std::string fp = [] {
     uint64_t h = 0xcbf29ce484222325ull;
-    for (const char* f : {"fused.hpp", "fused_device.hpp", "fused_sinks.hpp", "fused_shapes.hpp", "partition_device.hpp", "partition2_device.hpp", "partition3_device.hpp", "dev.hpp", "kconfig.hpp", "temporal.hpp", "decimal.hpp"}) {
+    for (const char* f : {"fused.hpp", "fused_cells.hpp", "fused_device.hpp", "fused_sinks.hpp", "fused_shapes.hpp", "partition_device.hpp", "partition2_device.hpp", "partition3_device.hpp", "dev.hpp", "kconfig.hpp", "temporal.hpp", "decimal.hpp"}) {
       if (FILE* fp2 = fopen((include_dir() + "/" + f).c_str(), "rb")) {
         char buf[65536]; size_t n;
         while ((n = fread(buf, 1, sizeof buf, fp2)) > 0) h = fnv1a(std::string(buf, n), h);
@@ -250,14 +258,14 @@ void store_cached(const std::string& path, const std::vector<char>& code) {
 }
 int g_cache_hits = 0;
 
-Entry compile(const Shape& sh, Sink sink) {
+Entry compile(const Shape& sh, Sink sink, uint32_t cell_code) {
   Entry e;
   const auto t0 = std::chrono::steady_clock::now();
-  const std::string src = source_for(sh, sink);
+  const std::string src = source_for(sh, sink, cell_code);
   const std::string cpath = cache_path(src);
   {
     std::vector<char> cached;
-    if (load_cached(cpath, &cached) && hipModuleLoadData(&e.mod, cached.data()) == hipSuccess && hipModuleGetFunction(&e.fn, e.mod, kernel_symbol(sh, sink).c_str()) == hipSuccess) {
+    if (load_cached(cpath, &cached) && hipModuleLoadData(&e.mod, cached.data()) == hipSuccess && hipModuleGetFunction(&e.fn, e.mod, kernel_symbol(sh, sink, cell_code).c_str()) == hipSuccess) {
       g_cache_hits++; g_compiled++;      // stats(): specialised kernels made available, compiled or loaded
       if (getenv("PLX_JIT_VERBOSE")) fprintf(stderr, "[plx jit] %s: loaded from %s\n", sink_type(sink), cpath.c_str());
       return e;
@@ -284,7 +292,7 @@ Entry compile(const Shape& sh, Sink sink) {
   std::vector<char> code(cs);
   hiprtcGetCode(prog, code.data());
   hiprtcDestroyProgram(&prog);
-  if (hipModuleLoadData(&e.mod, code.data()) != hipSuccess || hipModuleGetFunction(&e.fn, e.mod, kernel_symbol(sh, sink).c_str()) != hipSuccess) { e.failed = true; return e; }
+  if (hipModuleLoadData(&e.mod, code.data()) != hipSuccess || hipModuleGetFunction(&e.fn, e.mod, kernel_symbol(sh, sink, cell_code).c_str()) != hipSuccess) { e.failed = true; return e; }
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   g_compiled++; g_ms += ms;
   if (getenv("PLX_JIT_VERBOSE")) fprintf(stderr, "[plx jit] %s: %.0f ms, %zu bytes\n", sink_type(sink), ms, cs);
@@ -293,8 +301,8 @@ Entry compile(const Shape& sh, Sink sink) {
 }  // namespace
 
 // compile-only check (no GPU needed: hiprtc cross-compiles): returns "" on success, else the compiler log
-std::string selftest(const Shape& sh, Sink sink) {
-  const std::string src = source_for(sh, sink);
+std::string selftest(const Shape& sh, Sink sink, uint32_t cell_code) {
+  const std::string src = source_for(sh, sink, cell_code);
   hiprtcProgram prog = nullptr;
   if (hiprtcCreateProgram(&prog, src.c_str(), "plx_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return "hiprtcCreateProgram failed";
   const std::vector<std::string> optv = compile_options();
@@ -309,7 +317,9 @@ std::string selftest(const Shape& sh, Sink sink) {
     size_t cs = 0; hiprtcGetCodeSize(prog, &cs);
     std::vector<char> code(cs);
     hiprtcGetCode(prog, code.data());
-    const std::string base = std::string(dir) + "/" + sink_type(sink) + (wide_tiles(sink) ? "_wide" : "") + "_" + std::to_string((int)sink);
+    // (the kernels with shared cells go to a folder of their own: readers of the dump directory count the files of the plain sinks)
+    if (shared_cells(sink)) (void)mkdir((std::string(dir) + "/shared_cells").c_str(), 0755);
+    const std::string base = std::string(dir) + (shared_cells(sink) ? "/shared_cells/" : "/") + sink_type(sink) + (wide_tiles(sink) ? "_wide" : "") + "_" + std::to_string((int)sink);
     if (FILE* f = fopen((base + ".hsaco").c_str(), "wb")) { fwrite(code.data(), 1, code.size(), f); fclose(f); }
     if (FILE* f = fopen((base + ".hip").c_str(), "wb")) { fwrite(src.data(), 1, src.size(), f); fclose(f); }
   }
@@ -327,12 +337,13 @@ void stats(int* compiled, double* compile_ms) {
   if (compile_ms) *compile_ms = g_ms;
 }
 
-static hipFunction_t get_fn(const Shape& sh, Sink sink) {
+static hipFunction_t get_fn(const Shape& sh, Sink sink, uint32_t cell_code = 0) {
   std::string key((const char*)&sh, sizeof(Shape));
   key.push_back((char)sink);
+  if (shared_cells(sink)) key.append((const char*)&cell_code, sizeof cell_code);
   std::lock_guard<std::mutex> lk(g_mu);
   auto it = g_cache.find(key);
-  if (it == g_cache.end()) it = g_cache.emplace(key, compile(sh, sink)).first;
+  if (it == g_cache.end()) it = g_cache.emplace(key, compile(sh, sink, cell_code)).first;
   return it->second.failed ? nullptr : it->second.fn;
 }
 
@@ -346,11 +357,16 @@ bool launch_raw(const Shape& sh, Sink kind, void** kargs, int grid, int block, s
   return true;
 }
 
-bool launch(const Shape& sh, const Args& args, Sink sink, const void* params, int grid, size_t lds_bytes) {
+bool launch(const Shape& sh, const Args& args, Sink sink, const void* params, int grid, size_t lds_bytes, uint32_t cell_code) {
   if (!enabled(args.n_rows)) return false;
   Shape shc = sh; Args ac = args;
   void* kargs[] = {(void*)&shc, (void*)&ac, const_cast<void*>(params)};
-  return launch_raw(sh, sink, kargs, grid, k::kBlock, lds_bytes);
+  if (!shared_cells(sink)) return launch_raw(sh, sink, kargs, grid, k::kBlock, lds_bytes);
+  hipFunction_t fn = get_fn(sh, sink, cell_code);
+  if (!fn) return false;
+  const hipError_t rc = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, (unsigned)k::kBlock, 1, 1, (unsigned)lds_bytes, stream(), kargs, nullptr);
+  if (rc != hipSuccess) { set_last_error(std::string("jit: launch failed: ") + hipGetErrorString(rc)); return false; }
+  return true;
 }
 
 }  // namespace jit

@@ -37,6 +37,9 @@ enum Sink { REGAGG = 0, LDSAGG, DENSE, HASH, WIDE, JOIN_BUILD, PROBE_AGG, DIRECT
             // the two aggregate scans over 512-row wide tiles (fused_sinks.hpp fused_scan_body<P, Sink, true>; plain scan sinks, launched with launch()).  A kind of
             // its own each: kernel symbol and disk-cache key differ from the 128-row form's
             REGAGG_WIDE, LDSAGG_WIDE,
+            // the LDS table with shared cells (fused_sinks.hpp LdsCellSink<JitProg, code>; params = its Params), 128-row and wide tiles.  The plan's code
+            // (fused_cells.hpp cell_plan_code) is a second key beside the shape: part of the generated source, the kernel symbol and the cache keys
+            LDSCELL, LDSCELL_WIDE,
             kNumSinks };
 inline Sink part3_scatter_sink(uint32_t mode, uint32_t tiles, uint32_t pack, bool hot) {
   if (pack == fused::kPackPairV) return (Sink)(PART3_SCATTER_PAIRV + (tiles - 1) + (hot ? 4 : 0));
@@ -45,14 +48,14 @@ inline Sink part3_scatter_sink(uint32_t mode, uint32_t tiles, uint32_t pack, boo
 }
 inline Sink part3_agg_sink(uint32_t mode, uint32_t pack) { return pack == fused::kPackPairV ? PART3_AGG_PAIRV : pack == fused::kPackPair ? (Sink)(PART3_AGG_PAIR + mode) : (Sink)(PART3_AGG + mode + 2 * pack); }
 
-bool launch(const fused::Shape& sh, const fused::Args& args, Sink sink, const void* params, int grid, size_t lds_bytes);
+bool launch(const fused::Shape& sh, const fused::Args& args, Sink sink, const void* params, int grid, size_t lds_bytes, uint32_t cell_code = 0 /* LDSCELL* only */);
 // Compile (or fetch) the specialised kernel of (shape, kind) without launching: lets a multi-kernel pipeline decide up
 // front whether every stage is available.  n_rows gates on PLX_JIT / PLX_JIT_MIN_ROWS like launch().
 bool ensure(const fused::Shape& sh, Sink kind, int64_t n_rows);
 // Launch with an explicit argument list (pointers to each kernel argument, in the wrapper's order).
 bool launch_raw(const fused::Shape& sh, Sink kind, void** kargs, int grid, int block, size_t lds_bytes);
 // compile-only check of the JIT toolchain for one (shape, sink): "" on success, else the compiler log (no GPU needed)
-std::string selftest(const fused::Shape& sh, Sink sink);
+std::string selftest(const fused::Shape& sh, Sink sink, uint32_t cell_code = 0);
 // "aot" (pre-instantiated), "jit" (run-time specialised) or "generic" (interpreter): how a program of this size runs
 const char* program_mode(int static_id, int64_t n_rows);
 // inputs of at least min_rows rows use the JIT; < 0 disables it (overrides PLX_JIT / PLX_JIT_MIN_ROWS)

@@ -33,6 +33,7 @@
 //     rows 8l .. 8l+7: one 8- or 16-byte load per column and lane; fused_device.hpp
 //     wide_load, wide_tiles_choice below) and finish the last < 512 rows per 128-row tile.
 #include "fused_sinks.hpp"
+#include "fused_cells.hpp"
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
 #include "variance.hpp"
@@ -246,12 +247,58 @@ int lds_agg_copies(int n_groups, int n_aggs) {
   return c;
 }
 
-void fused_lds_agg(const Shape& sh, const Args& args, int n_groups, int static_id, uint64_t* out_dev /* [G][n_aggs] */, unsigned int* oob) {
-  const int copies = lds_agg_copies(n_groups, sh.n_aggs);
+// ---- shared cells: the host's side (fused_cells.hpp, fused_sinks.hpp LdsCellSink) ---------------------------------------------------------------------------------
+// PLX_SHARED_CELLS=0 (read once) keeps one cell per aggregate: measurement runs and the tests, which also have a setter.
+static std::atomic<int> g_shared_cells{-1};
+static bool shared_cells_knob() {
+  int v = g_shared_cells.load(std::memory_order_relaxed);
+  if (v < 0) { const char* e = getenv("PLX_SHARED_CELLS"); v = (e && e[0] == '0') ? 0 : 1; g_shared_cells.store(v, std::memory_order_relaxed); }
+  return v != 0;
+}
+void set_shared_cells(bool on) { g_shared_cells.store(on ? 1 : 0, std::memory_order_relaxed); }
+static std::atomic<int> g_last_lds_cells{0};
+int last_lds_cells() { return g_last_lds_cells.load(std::memory_order_relaxed); }
+// rows the waves of one workgroup can feed its table when `grid` workgroups share the scan: every wave takes every (grid * waves)-th tile -- whole wide tiles first
+// (wide), then the 128-row tiles of what is left
+uint64_t lds_agg_wg_rows_of(int64_t n_rows, int grid, bool wide) {
+  const int64_t wpw = kBlock / 64, nwaves = (int64_t)grid * wpw;
+  const int64_t nwide = wide ? n_rows / kWideTileRows : 0;
+  const int64_t rest = (n_rows - nwide * kWideTileRows + kTileRows - 1) / kTileRows;
+  const int64_t per_wave = (nwide + nwaves - 1) / nwaves * kWideTileRows + (rest + nwaves - 1) / nwaves * kTileRows;
+  const int64_t r = wpw * per_wave;
+  return (uint64_t)(r < n_rows ? r : n_rows);
+}
+// R of rule A: holds whichever tile size fused_lds_agg then chooses for these rows (the two grids differ), tail included
+uint64_t lds_agg_wg_rows(int64_t n_rows) {
+  const uint64_t a = lds_agg_wg_rows_of(n_rows, scan_grid(n_rows, 5, "PLX_BPC_LDSAGG", kWideTileRows), true);
+  const uint64_t b = lds_agg_wg_rows_of(n_rows, scan_grid(n_rows, 5, "PLX_BPC_LDSAGG", kTileRows), false);
+  return a > b ? a : b;
+}
+// the ahead-of-time kernels with shared cells: compiled for the plan their shape has when every bound holds
+template <int ID> using SharedCellSink = LdsCellSink<StatProg<ID>, full_cell_plan_code(static_shape(ID))>;
+static_assert(SharedCellSink<SHAPE_Q1_ENCODED>::NC == 5 && SharedCellSink<SHAPE_Q1_ENCODED_PRICE>::NC == 5, "encoded Q1: count, sum and mean of the quantity share one cell");
+static_assert(wide_tiles_form<StatProg<SHAPE_Q1_ENCODED_PRICE>, SharedCellSink<SHAPE_Q1_ENCODED_PRICE>>() && wide_tiles_form<StatProg<SHAPE_Q1_ENCODED>, SharedCellSink<SHAPE_Q1_ENCODED>>(),
+              "the shared-cell kernels have the wide-tile form of the kernels they stand in for");
+static uint32_t static_shared_code(int static_id) {
+  switch (static_id) {
+    case SHAPE_Q1_ENCODED: return full_cell_plan_code(static_shape(SHAPE_Q1_ENCODED));
+    case SHAPE_Q1_ENCODED_PRICE: return full_cell_plan_code(static_shape(SHAPE_Q1_ENCODED_PRICE));
+    default: return kIdentityCells;
+  }
+}
+
+void fused_lds_agg(const Shape& sh, const Args& args, int n_groups, int static_id, uint64_t* out_dev /* [G][n_aggs] */, unsigned int* oob, const CellPlan* cell_plan) {
+  const bool compiled = static_id >= 0 || jit::program_mode(static_id, args.n_rows)[0] == 'j';
+  // the plan in force: the engine's, for a compiled kernel that exists with it (an ahead-of-time shape has ONE shared plan; run-time compilation takes any)
+  CellPlan plan = cell_plan_from_code(sh, kIdentityCells);
+  if (cell_plan && compiled && shared_cells_knob() && !cell_plan_is_identity(*cell_plan, sh) && (static_id < 0 || cell_plan_code(*cell_plan, sh) == static_shared_code(static_id))) plan = *cell_plan;
+  bool shared = !cell_plan_is_identity(plan, sh);
+  const uint32_t code = cell_plan_code(plan, sh);
+  int copies = lds_agg_copies(n_groups, plan.n_cells);
   PLX_REQUIRE(copies > 0, PLX_ERR_INVALID, "fused_lds_agg: group table does not fit LDS");
   const int cells = n_groups * sh.n_aggs;
-  const size_t lds = (size_t)cells * copies * 8;
-  const bool wide = wide_tiles_choice(sh, args, static_id >= 0 || jit::program_mode(static_id, args.n_rows)[0] == 'j', wide_tiles_knob());
+  size_t lds = (size_t)n_groups * plan.n_cells * copies * 8;
+  const bool wide = wide_tiles_choice(sh, args, compiled, wide_tiles_knob());
   g_last_tile_rows.store(wide ? kWideTileRows : kTileRows, std::memory_order_relaxed);
   const int grid = scan_grid(args.n_rows, 5, "PLX_BPC_LDSAGG", wide ? kWideTileRows : kTileRows);
   const bool use_partials = n_groups <= 64;
@@ -260,21 +307,38 @@ void fused_lds_agg(const Shape& sh, const Args& args, int n_groups, int static_i
   sp.n_groups = n_groups; sp.copies = copies; sp.oob = oob;
   if (use_partials) { partials = dev_alloc(sizeof(uint64_t) * (size_t)grid * cells); sp.partials = partials->as<unsigned long long>(); }
   else { init_agg_cells(out_dev, n_groups, sh); sp.global_acc = (unsigned long long*)out_dev; }
+  // (the parameters of every LdsCellSink instantiation have one layout: those of the plain sink and the shift)
+  SharedCellSink<SHAPE_Q1_ENCODED_PRICE>::Params cp{sp.partials, sp.global_acc, sp.n_groups, sp.copies, sp.oob, plan.shift};
   {
     ProfileScope ps(scope_name("fused_scan_ldsagg_static", "fused_scan_ldsagg_generic", static_id).c_str(), algo_bytes(sh, args), (uint64_t)args.n_rows);
-    switch (static_id) {
-      case SHAPE_Q1: launch_static<SHAPE_Q1, LdsAggSink>(wide, grid, lds, sh, args, sp); break;
-      case SHAPE_Q1_ENCODED: launch_static<SHAPE_Q1_ENCODED, LdsAggSink>(wide, grid, lds, sh, args, sp); break;
-      case SHAPE_Q1_ENCODED_PRICE: launch_static<SHAPE_Q1_ENCODED_PRICE, LdsAggSink>(wide, grid, lds, sh, args, sp); break;
-      default:
-        if (!jit::launch(sh, args, wide ? jit::LDSAGG_WIDE : jit::LDSAGG, &sp, grid, lds)) {
-          g_last_tile_rows.store(kTileRows, std::memory_order_relaxed);
-          const DynLaunch d = dyn_launch(sh, args, lds); PLX_LAUNCH_SCAN(DynProg, LdsAggSink, grid, d.lds, sh, d.args, sp);
-        }
-        break;
+    if (shared && static_id == SHAPE_Q1_ENCODED) {
+      SharedCellSink<SHAPE_Q1_ENCODED>::Params c15{cp.partials, cp.global_acc, cp.n_groups, cp.copies, cp.oob, cp.shift};
+      launch_static<SHAPE_Q1_ENCODED, SharedCellSink<SHAPE_Q1_ENCODED>>(wide, grid, lds, sh, args, c15);
+    } else if (shared && static_id == SHAPE_Q1_ENCODED_PRICE) {
+      launch_static<SHAPE_Q1_ENCODED_PRICE, SharedCellSink<SHAPE_Q1_ENCODED_PRICE>>(wide, grid, lds, sh, args, cp);
+    } else if (shared && jit::launch(sh, args, wide ? jit::LDSCELL_WIDE : jit::LDSCELL, &cp, grid, lds, code)) {
+    } else {
+      if (shared) {      // no compiled kernel after all: the interpreter keeps one cell per aggregate
+        shared = false; plan = cell_plan_from_code(sh, kIdentityCells);
+        copies = lds_agg_copies(n_groups, sh.n_aggs);
+        PLX_REQUIRE(copies > 0, PLX_ERR_INVALID, "fused_lds_agg: group table does not fit LDS");
+        sp.copies = copies; lds = (size_t)cells * copies * 8;
+      }
+      switch (static_id) {
+        case SHAPE_Q1: launch_static<SHAPE_Q1, LdsAggSink>(wide, grid, lds, sh, args, sp); break;
+        case SHAPE_Q1_ENCODED: launch_static<SHAPE_Q1_ENCODED, LdsAggSink>(wide, grid, lds, sh, args, sp); break;
+        case SHAPE_Q1_ENCODED_PRICE: launch_static<SHAPE_Q1_ENCODED_PRICE, LdsAggSink>(wide, grid, lds, sh, args, sp); break;
+        default:
+          if (!jit::launch(sh, args, wide ? jit::LDSAGG_WIDE : jit::LDSAGG, &sp, grid, lds)) {
+            g_last_tile_rows.store(kTileRows, std::memory_order_relaxed);
+            const DynLaunch d = dyn_launch(sh, args, lds); PLX_LAUNCH_SCAN(DynProg, LdsAggSink, grid, d.lds, sh, d.args, sp);
+          }
+          break;
+      }
     }
     PLX_HIP(hipGetLastError());
   }
+  g_last_lds_cells.store(plan.n_cells, std::memory_order_relaxed);
   if (use_partials) {
     hipLaunchKernelGGL(partials_finish_kernel, dim3(cells), dim3(kBlock), 0, stream(), sh, sp.partials, grid, cells, cells, (unsigned long long*)out_dev);
     PLX_HIP(hipGetLastError());

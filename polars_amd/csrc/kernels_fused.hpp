@@ -6,6 +6,7 @@
 
 #include "core.hpp"
 #include "fused.hpp"
+#include "fused_cells.hpp"
 
 namespace plx {
 namespace k {
@@ -17,7 +18,14 @@ void fused_regagg(const fused::Shape& sh, const fused::Args& args, int static_id
 // filter -> exprs -> LDS-resident table for dense group ids in [0, n_groups); out_dev
 // [n_groups][n_aggs] 64-bit patterns in HBM.  lds_agg_copies() == 0 => does not fit.
 int lds_agg_copies(int n_groups, int n_aggs);
-void fused_lds_agg(const fused::Shape& sh, const fused::Args& args, int n_groups, int static_id, uint64_t* out_dev, unsigned int* oob = nullptr /* device flag: a group id outside the table */);
+void fused_lds_agg(const fused::Shape& sh, const fused::Args& args, int n_groups, int static_id, uint64_t* out_dev, unsigned int* oob = nullptr /* device flag: a group id outside the table */,
+                   const fused::CellPlan* cell_plan = nullptr /* shared cells (fused_cells.hpp): taken by the compiled kernels; null = one cell per aggregate */);
+// R of the cell plan's rule A: an upper bound on the rows one workgroup of fused_lds_agg adds to its table, at either tile size
+uint64_t lds_agg_wg_rows(int64_t n_rows);
+uint64_t lds_agg_wg_rows_of(int64_t n_rows, int grid, bool wide);      // the same bound for one grid and tile size (a pure function)
+// LDS cells per group the last fused_lds_agg held (n_aggs, or fewer with shared cells; 0 before the first); the switch behind PLX_SHARED_CELLS
+int last_lds_cells();
+void set_shared_cells(bool on);
 
 // The two scans above run over 512-row wave tiles (kernels_fused.hip "wide tiles") when this says so: a compiled program (ahead of time or at run time) over narrow
 // rows, no nullable input, at least one whole tile, every column pointer aligned to eight rows, and the knob (PLX_WIDE_TILES, read once by the launchers) on.
