@@ -177,6 +177,17 @@ typedef enum plx_rank_method {
   PLX_RANK_ORDINAL = 4
 } plx_rank_method;
 
+/* The fixed-window rolling functions (PLX_AE_ROLLING, plx_rolling).  The window of row i is the rows [i + h - w + 1, i + h] of its partition, h = 0 or, centered,
+ * (w - 1) / 2, clipped to the partition; the result is null where the window holds fewer than min_samples non-null values, else the function of its non-null values.
+ * SUM: the dtype of PLX_CUM_SUM (narrow integers -> PLX_I64, PLX_BOOL -> PLX_U32, integers wrap, PLX_F32 accumulates in f64); MEAN: PLX_F64 (PLX_F32 for a PLX_F32
+ * operand), accumulated in f64; MIN / MAX keep the dtype and ignore a NaN unless every valid value of the window is NaN. */
+typedef enum plx_rolling_op {
+  PLX_ROLLING_SUM = 0,
+  PLX_ROLLING_MEAN = 1,
+  PLX_ROLLING_MIN = 2,
+  PLX_ROLLING_MAX = 3
+} plx_rolling_op;
+
 /* With pos = (n - 1) * q over the n valid values in order and a, b the values at ranks floor(pos), ceil(pos): NEAREST = the value at rank floor(pos + 0.5),
  * LOWER = a, HIGHER = b, MIDPOINT = a == b ? a : (a + b) / 2, LINEAR = a == b ? a : (pos - floor(pos)) * (b - a) + a. */
 typedef enum plx_quantile_interpolation {
@@ -417,6 +428,17 @@ int plx_window_agg(const plx_column* keys, int32_t n_keys, const plx_column* val
  * At most 2^32 - 2 rows. */
 int plx_cumulative(const plx_column* keys, int32_t n_keys, plx_column value, int32_t op, int32_t reverse, plx_column* out);
 int plx_rank(const plx_column* keys, int32_t n_keys, plx_column value, int32_t method, int32_t descending, plx_column* out);
+/* shift / diff and the rolling functions over plain columns (PLX_AE_SHIFT / PLX_AE_ROLLING as column calls).  keys / n_keys as for plx_cumulative.
+ * plx_shift: row i takes row i - n of its partition (any n; |n| >= the partition length vacates every row); vacated rows are null, or hold *fill (a value of the
+ * column's dtype) and are valid when fill is not NULL.  diff != 0: the result is value[i] - value[i - n] in the widened dtype (PLX_U8 -> PLX_I16, PLX_U16 -> PLX_I32,
+ * PLX_U32 / PLX_U64 -> PLX_I64, else unchanged; integers wrap), null where either row is null or row i - n lies outside the partition; fill must be NULL and a
+ * PLX_BOOL column is PLX_ERR_UNSUPPORTED.  plx_rolling: op is a plx_rolling_op, window_size >= 1, min_samples in 1..window_size, center 0 or 1.  Anything else is
+ * PLX_ERR_INVALID naming the parameter, checked before anything runs, an empty input included.  plx_last_plan_description() names the route:
+ * "Shift{... route=shift[whole column] | shift[sorted rows: ...]}", "Rolling{... route=rolling[tile halo: w=.., lds=..] | rolling[two scans: ...]}".  The environment
+ * variable PLX_ROLLING_ROUTE=scans (read per call) forces the two-scan route at every window size; "tile" or unset: the tile route up to a window of 1024 rows.
+ * At most 2^32 - 2 rows. */
+int plx_shift(const plx_column* keys, int32_t n_keys, plx_column value, int64_t n, const plx_scalar* fill, int32_t diff, plx_column* out);
+int plx_rolling(const plx_column* keys, int32_t n_keys, plx_column value, int32_t op, int64_t window_size, int64_t min_samples, int32_t center, plx_column* out);
 /* Row-order Boolean mask (no nulls) of the rows that unique() keeps: the n_keys (1..8: more is PLX_ERR_UNSUPPORTED) key columns of integer, float or Boolean dtype
  * are sorted stably once, so the head of every run of equal rows is its first occurrence and the tail its last; keep is a plx_unique_keep (outside 0..3:
  * PLX_ERR_INVALID).  Two rows are equal when every key is equal by the sort's equality, null == null.  Filtering any column of the same height by the mask
@@ -501,9 +523,16 @@ typedef enum plx_aexpr_kind {
                            * as the lhs of a PLX_AE_WINDOW, each partition of its keys in the frame's row order.  Legal where a window is; in the keys or aggregates of a
                            * PLX_IR_GROUPBY it is PLX_ERR_INVALID.  Nodes of one select / with_columns / filter that share their key list share one stable sort of the
                            * rows and one head mask; fused pipelines decline the kind by name.  Output name: that of lhs */
-  PLX_AE_RANK = 17        /* lhs = a row-level operand (as for PLX_AE_CUMULATIVE), op = the plx_rank_method (outside 0..4: PLX_ERR_INVALID at import), lit.u = descending
+  PLX_AE_RANK = 17,       /* lhs = a row-level operand (as for PLX_AE_CUMULATIVE), op = the plx_rank_method (outside 0..4: PLX_ERR_INVALID at import), lit.u = descending
                            * (0 / 1).  Result: PLX_F64 (AVERAGE) or PLX_U32 with the operand's validity; whole column, or per partition as the lhs of a PLX_AE_WINDOW.
                            * Nodes that share (keys, operand, descending) share one sort.  Output name: that of lhs */
+  PLX_AE_SHIFT = 18,      /* lhs = a row-level operand (as for PLX_AE_CUMULATIVE), op = 0 (shift) or 1 (diff), lit.i = n (any int64), rhs = the arena index of the fill
+                           * literal (a non-null PLX_AE_LITERAL of the operand's dtype; shift only) or -1: vacated rows are null.  Result: shift keeps the dtype, diff
+                           * widens unsigned operands (plx_shift); one value per row.  Whole column, or per partition as the lhs of a PLX_AE_WINDOW.  Legal where
+                           * PLX_AE_CUMULATIVE is; shares that kind's stable sort and head mask per key list.  Output name: that of lhs */
+  PLX_AE_ROLLING = 19     /* lhs = a row-level operand, op = the plx_rolling_op (outside 0..3: PLX_ERR_INVALID at import), lit.u = window_size in bits 0..31,
+                           * min_samples in bits 32..62, center in bit 63 (window_size < 1 or min_samples outside 1..window_size: PLX_ERR_INVALID at import).  Result:
+                           * the dtype of plx_rolling_op, a validity of its own.  Placement and sharing as for PLX_AE_SHIFT.  Output name: that of lhs */
 } plx_aexpr_kind;
 
 /* polars_plan::dsl::Operator subset */
@@ -515,14 +544,15 @@ typedef enum plx_operator {
 
 typedef struct plx_aexpr {
   int32_t kind; /* plx_aexpr_kind */
-  int32_t op;   /* plx_operator or plx_agg_op; PLX_AE_CUMULATIVE: plx_cum_op; PLX_AE_RANK: plx_rank_method */
+  int32_t op;   /* plx_operator or plx_agg_op; PLX_AE_CUMULATIVE: plx_cum_op; PLX_AE_RANK: plx_rank_method; PLX_AE_SHIFT: 0 shift / 1 diff; PLX_AE_ROLLING: plx_rolling_op */
   int32_t lhs;  /* arena index of the (left) input, -1 if none */
   int32_t rhs;  /* arena index of the right input, -1 if none */
   int32_t dtype; /* literal dtype / cast target (plx_dtype) */
   int32_t is_null; /* literal is NULL */
   plx_scalar lit;   /* PLX_AE_LITERAL: the value; PLX_AE_BITMAP_LOOKUP: lit.u = the lookup bitmap's plx_column handle; PLX_AE_TEMPORAL: lit.u = the plx_time_unit;
                      * PLX_AE_AGG of PLX_AGG_VAR / PLX_AGG_STD: lit.u = ddof; of PLX_AGG_QUANTILE: lit.f64 = q (and dtype = the plx_quantile_interpolation); PLX_AGG_N_UNIQUE carries nothing;
-                     * PLX_AE_CUMULATIVE: lit.u = reverse; PLX_AE_RANK: lit.u = descending; read for those kinds only */
+                     * PLX_AE_CUMULATIVE: lit.u = reverse; PLX_AE_RANK: lit.u = descending; PLX_AE_SHIFT: lit.i = n; PLX_AE_ROLLING: lit.u = the packed parameters;
+                     * read for those kinds only */
   const char* name; /* column name / alias */
   int32_t cond;     /* PLX_AE_TERNARY: arena index of the predicate; read for that kind only (appended last: arenas of earlier callers never carry the kind) */
 } plx_aexpr;
@@ -948,6 +978,16 @@ void _polars_plugin_field_plx_cum(const struct ArrowSchema* fields, size_t n_fie
  * UInt32 otherwise, under the first input's name */
 void _polars_plugin_plx_rank(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
 void _polars_plugin_field_plx_rank(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
+/* plx_shift / plx_diff (values, key...): plx_shift; kwargs {"n": int} (absent: 1; an integer that fits 32 bits).  Vacated rows are null.  The field is the input's
+ * (plx_shift) or the widened difference dtype (plx_diff; a Boolean or temporal series is refused) under the first input's name */
+void _polars_plugin_plx_shift(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
+void _polars_plugin_field_plx_shift(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
+void _polars_plugin_plx_diff(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
+void _polars_plugin_field_plx_diff(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
+/* plx_rolling (values, key...): plx_rolling; kwargs {"op": "sum" | "mean" | "min" | "max", "window_size": int, "min_samples": int (absent: window_size), "center":
+ * bool}; the field is the plx_rolling_op dtype under the first input's name */
+void _polars_plugin_plx_rolling(const plx_series_export* inputs, size_t n_inputs, const uint8_t* kwargs, size_t kwargs_len, plx_series_export* out, const void* ctx);
+void _polars_plugin_field_plx_rolling(const struct ArrowSchema* fields, size_t n_fields, struct ArrowSchema* out, const uint8_t* kwargs, size_t kwargs_len);
 
 #ifdef __cplusplus
 }

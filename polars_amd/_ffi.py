@@ -42,6 +42,22 @@ CUM_SUM, CUM_MIN, CUM_MAX, CUM_COUNT = range(4)                            # plx
 CUM_OPS = {"cum_sum": CUM_SUM, "cum_min": CUM_MIN, "cum_max": CUM_MAX, "cum_count": CUM_COUNT}
 RANK_AVERAGE, RANK_MIN, RANK_MAX, RANK_DENSE, RANK_ORDINAL = range(5)      # plx_rank_method
 RANK_METHODS = {"average": RANK_AVERAGE, "min": RANK_MIN, "max": RANK_MAX, "dense": RANK_DENSE, "ordinal": RANK_ORDINAL}
+AE_SHIFT, AE_ROLLING = 18, 19                                              # x.shift(n) / x.diff(n): lhs = the operand, op = 0 / 1, lit.i = n, rhs = the fill literal or -1; x.rolling_*(w): op = the plx_rolling_op, lit.u = the packed parameters
+SHIFT_SHIFT, SHIFT_DIFF = 0, 1
+ROLLING_SUM, ROLLING_MEAN, ROLLING_MIN, ROLLING_MAX = range(4)            # plx_rolling_op
+ROLLING_OPS = {"rolling_sum": ROLLING_SUM, "rolling_mean": ROLLING_MEAN, "rolling_min": ROLLING_MIN, "rolling_max": ROLLING_MAX}
+ROLLING_MAX_WINDOW = (1 << 31) - 1
+
+
+def rolling_pack(window_size: int, min_samples: int, center: bool) -> int:
+    """The literal of a PLX_AE_ROLLING node: window_size in bits 0..31, min_samples in bits 32..62, center in bit 63."""
+    return (int(window_size) & 0xFFFFFFFF) | ((int(min_samples) & 0x7FFFFFFF) << 32) | (int(bool(center)) << 63)
+
+
+def rolling_unpack(u: int):
+    return u & 0xFFFFFFFF, (u >> 32) & 0x7FFFFFFF, bool(u >> 63)
+
+
 STR_STARTS_WITH, STR_ENDS_WITH, STR_CONTAINS = range(3)                 # plx_str_match_kind
 STR_MATCH_MAX_PATTERN = 64
 UNIT_DATE, UNIT_MS, UNIT_US, UNIT_NS = range(4)                          # plx_time_unit
@@ -219,6 +235,8 @@ SIGNATURES = {
     "plx_window_agg": (C.c_int, [_u64p, C.c_int32, _u64p, _i32p, C.c_int32, _i32p, C.POINTER(C.c_double), _i32p, _u64p]),
     "plx_cumulative": (C.c_int, [_u64p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _u64p]),
     "plx_rank": (C.c_int, [_u64p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _u64p]),
+    "plx_shift": (C.c_int, [_u64p, C.c_int32, C.c_uint64, C.c_int64, C.POINTER(Scalar), C.c_int32, _u64p]),
+    "plx_rolling": (C.c_int, [_u64p, C.c_int32, C.c_uint64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _u64p]),
     "plx_join_indices": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _u64p, _u64p]),
     "plx_datagen_lineitem_q1": (C.c_int, [C.c_int64, C.c_uint64, _u64p]),
     "plx_datagen_lineitem_q1_host": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

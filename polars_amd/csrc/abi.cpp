@@ -20,6 +20,7 @@
 #include "ops.hpp"
 #include "cumulative.hpp"
 #include "quantile.hpp"
+#include "rolling.hpp"
 #include "scan.hpp"
 #include "sort.hpp"
 #include "strmatch.hpp"
@@ -473,8 +474,58 @@ ColumnPtr rank_call(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, 
   if (desc) *desc = "Rank{keys=[" + std::to_string(keys.size()) + " columns], fns=1, rows=" + std::to_string(value->len) + ", method=" + cumulative::method_name(method) + (descending ? ", descending" : "") + ", route=" + order.desc + "}; ";
   return out;
 }
+// plx_shift / plx_rolling and their plugin twins: every parameter is checked by name before anything runs, an empty input included
+ColumnPtr shift_call(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, int64_t n, const plx_scalar* fill, int diff, std::string* desc) {
+  PLX_REQUIRE(diff == 0 || diff == 1, PLX_ERR_INVALID, "shift: diff must be 0 or 1, got " + std::to_string(diff));
+  PLX_REQUIRE(!(diff && fill), PLX_ERR_INVALID, "shift: fill must be NULL when diff is set (a fill value belongs to shift)");
+  const char* what = diff ? "diff" : "shift";
+  if (diff ? rolling::diff_dtype(value->dtype) < 0 : !(value->dtype >= PLX_BOOL && value->dtype <= PLX_F64))
+    fail(PLX_ERR_UNSUPPORTED, std::string(what) + " of a " + dtype_name(value->dtype) + " column: " + (diff ? "integer and float columns only" : "integer, float and Boolean columns only"));
+  const cumulative::ScanOrder order = cumulative::scan_order(keys, value->len);
+  const rolling::Segments segs = rolling::segments_of(order);
+  ColumnPtr out = rolling::shift_column(order, segs, value, n, fill, diff != 0);
+  const std::string od = order.desc.rfind("cumulative[", 0) == 0 ? order.desc.substr(11) : order.desc;
+  if (desc) *desc = "Shift{keys=[" + std::to_string(keys.size()) + " columns], fns=1, rows=" + std::to_string(value->len) + ", " + what + ", n=" + std::to_string((long long)n) + ", route=shift[" + od + "}; ";
+  return out;
+}
+ColumnPtr rolling_call(const std::vector<ColumnPtr>& keys, const ColumnPtr& value, int op, int64_t window_size, int64_t min_samples, int center, std::string* desc) {
+  PLX_REQUIRE(rolling::op_ok(op), PLX_ERR_INVALID, "rolling: op " + std::to_string(op) + " is no plx_rolling_op (0 = sum, 1 = mean, 2 = min, 3 = max)");
+  PLX_REQUIRE(window_size >= 1 && window_size <= 0x7fffffffll, PLX_ERR_INVALID, "rolling: window_size must be at least 1 (and below 2^31), got " + std::to_string((long long)window_size));
+  PLX_REQUIRE(min_samples >= 1 && min_samples <= window_size, PLX_ERR_INVALID, "rolling: min_samples must lie in 1..window_size, got " + std::to_string((long long)min_samples));
+  PLX_REQUIRE(center == 0 || center == 1, PLX_ERR_INVALID, "rolling: center must be 0 or 1, got " + std::to_string(center));
+  if (rolling::result_dtype(op, value->dtype) < 0) fail(PLX_ERR_UNSUPPORTED, std::string(rolling::op_name(op)) + " of a " + dtype_name(value->dtype) + " column: integer, float and Boolean columns only");
+  const cumulative::ScanOrder order = cumulative::scan_order(keys, value->len);
+  const rolling::Segments segs = rolling::segments_of(order);
+  std::string route;
+  ColumnPtr out = rolling::rolling_column(order, segs, value, op, rolling::Params{(uint64_t)window_size, (uint64_t)min_samples, center != 0}, &route);
+  const std::string od = order.desc.rfind("cumulative[", 0) == 0 ? order.desc.substr(11, order.desc.size() - 12) : order.desc;
+  if (desc) *desc = "Rolling{keys=[" + std::to_string(keys.size()) + " columns], fns=1, rows=" + std::to_string(value->len) + ", w=" + std::to_string((long long)window_size) + ", route=" + route + (order.perm ? "; " + od : "") + "}; ";
+  return out;
+}
 }  // namespace
 }  // extern "C++"
+
+int plx_shift(const plx_column* keys, int32_t n_keys, plx_column value, int64_t n, const plx_scalar* fill, int32_t diff, plx_column* out) {
+  PLX_TRY
+  PLX_REQUIRE(out, PLX_ERR_INVALID, "shift: null output");
+  ColumnPtr v = get_column(value);
+  std::string d;
+  ColumnPtr r = shift_call(rowfn_inputs(diff ? "diff" : "shift", keys, n_keys, v), v, n, fill, diff, &d);
+  t_plan_desc = d;
+  *out = register_column(r);
+  PLX_CATCH
+}
+
+int plx_rolling(const plx_column* keys, int32_t n_keys, plx_column value, int32_t op, int64_t window_size, int64_t min_samples, int32_t center, plx_column* out) {
+  PLX_TRY
+  PLX_REQUIRE(out, PLX_ERR_INVALID, "rolling: null output");
+  ColumnPtr v = get_column(value);
+  std::string d;
+  ColumnPtr r = rolling_call(rowfn_inputs("rolling", keys, n_keys, v), v, op, window_size, min_samples, center, &d);
+  t_plan_desc = d;
+  *out = register_column(r);
+  PLX_CATCH
+}
 
 int plx_cumulative(const plx_column* keys, int32_t n_keys, plx_column value, int32_t op, int32_t reverse, plx_column* out) {
   PLX_TRY
@@ -823,7 +874,7 @@ ColumnPtr plugin_arith(int op, std::vector<PluginInput>& in) {
 ColumnPtr plugin_reduce(int agg, std::vector<PluginInput>& in) { return ops::scalar_column(ops::reduce(agg, in[0].col)); }
 
 // output field of a plugin function: name of the first input, dtype by the rule of the operator
-enum FieldRule { FIELD_BOOL, FIELD_SAME, FIELD_ARITH, FIELD_SUM, FIELD_MEAN, FIELD_U32, FIELD_F64 };
+enum FieldRule { FIELD_BOOL, FIELD_SAME, FIELD_ARITH, FIELD_SUM, FIELD_MEAN, FIELD_U32, FIELD_F64, FIELD_DIFF };
 void plugin_field(const ArrowSchema* fields, size_t n, ArrowSchema* out, FieldRule rule, int arith_op) {
   try {
     PLX_REQUIRE(fields && n >= 1 && out, PLX_ERR_INVALID, "plugin field: bad arguments");
@@ -838,6 +889,10 @@ void plugin_field(const ArrowSchema* fields, size_t n, ArrowSchema* out, FieldRu
       case FIELD_MEAN: odt = dt == PLX_F32 ? PLX_F32 : PLX_F64; break;
       case FIELD_U32: odt = PLX_U32; break;
       case FIELD_F64: odt = PLX_F64; break;
+      case FIELD_DIFF:
+        odt = rolling::diff_dtype(dt);
+        if (odt < 0 || (fields[0].format && fields[0].format[0] == 't')) fail(PLX_ERR_UNSUPPORTED, std::string("plugin field: diff of an Arrow format '") + (fields[0].format ? fields[0].format : "") + "' series: integer and float series only");
+        break;
     }
     memset(out, 0, sizeof(*out));
     auto* nm = new std::string(fields[0].name ? fields[0].name : "");
@@ -1046,6 +1101,84 @@ void _polars_plugin_field_plx_rank(PLX_FIELD_SIG) {
   const int method = rank_method_of(pickle_str_value(kwargs, kwargs_len, "method"));
   if (method < 0) { t_plugin_error = kRankKwargs; if (out) out->release = nullptr; return; }
   plugin_field(fields, n_fields, out, method == PLX_RANK_AVERAGE ? FIELD_F64 : FIELD_U32, 0);
+}
+// shift / diff and the rolling functions of the first series, per partition of the others when there are any (plx_shift / plx_rolling): kwargs {"n": int} (absent:
+// 1; vacated rows are null -- a fill value is a fill_null on the caller's side) and {"op": name, "window_size": int, "min_samples": int (absent: window_size),
+// "center": bool}
+extern "C++" {
+namespace {
+// a signed integer value of a pickled dict (BININT1 / BININT2 / BININT: what fits 32 bits); *ok = false when the key is there with another kind of value
+long long pickle_signed_value(const uint8_t* kw, size_t n, const char* key, long long absent, bool* ok) {
+  const size_t klen = strlen(key);
+  *ok = true;
+  for (size_t i = 0; i + 2 + klen <= n; i++) {
+    if (!((kw[i] == 0x8c || kw[i] == 'U') && kw[i + 1] == klen && !memcmp(kw + i + 2, key, klen))) continue;
+    size_t j = i + 2 + klen;
+    if (j < n && kw[j] == 0x94) j += 1; else if (j < n && kw[j] == 'q') j += 2; else if (j < n && kw[j] == 'r') j += 5;
+    if (j + 1 < n && kw[j] == 'K') return kw[j + 1];
+    if (j + 2 < n && kw[j] == 'M') return (long long)kw[j + 1] | ((long long)kw[j + 2] << 8);
+    if (j + 4 < n && kw[j] == 'J') { int32_t v; memcpy(&v, kw + j + 1, 4); return v; }
+    *ok = false;
+    return absent;
+  }
+  return absent;
+}
+int rolling_op_of(const std::string& s) {
+  static const char* names[] = {"sum", "mean", "min", "max"};
+  for (int i = 0; i < 4; i++) if (s == names[i] || s == std::string("rolling_") + names[i]) return i;
+  return -1;
+}
+const char* kRollingKwargs = "plx_rolling: kwargs must carry op in {sum, mean, min, max}";
+template <class Call>
+void plugin_rowfn(const char* what, PLX_PLUGIN_SIG, Call&& call) {
+  (void)kwargs; (void)kwargs_len;
+  plugin_call(inputs, n_inputs, out, ctx, n_inputs, [&](std::vector<PluginInput>& in) {
+    PLX_REQUIRE(in.size() >= 1, PLX_ERR_INVALID, std::string(what) + ": the value series, then 0..8 key series");
+    std::vector<ColumnPtr> cols;
+    for (PluginInput& x : in) cols.push_back(plugin_column(x));
+    PLX_REQUIRE((int)cols.size() - 1 <= sort::kSegmentMaxKeys, PLX_ERR_UNSUPPORTED, std::string(what) + " over " + std::to_string(cols.size() - 1) + " keys; a window takes 1.." + std::to_string(sort::kSegmentMaxKeys) + " keys on this path");
+    for (auto& c : cols) PLX_REQUIRE(c->len == cols[0]->len, PLX_ERR_SHAPE, std::string(what) + ": key length mismatch");
+    return call(std::vector<ColumnPtr>(cols.begin() + 1, cols.end()), cols[0]);
+  });
+}
+}  // namespace
+}  // extern "C++"
+void _polars_plugin_plx_shift(PLX_PLUGIN_SIG) {
+  bool ok = true;
+  const long long n = pickle_signed_value(kwargs, kwargs_len, "n", 1, &ok);
+  plugin_rowfn("plx_shift", inputs, n_inputs, kwargs, kwargs_len, out, ctx, [&](const std::vector<ColumnPtr>& keys, const ColumnPtr& v) {
+    PLX_REQUIRE(ok, PLX_ERR_INVALID, "plx_shift: kwargs n must be an integer (that fits 32 bits)");
+    return shift_call(keys, v, n, nullptr, 0, nullptr);
+  });
+}
+void _polars_plugin_field_plx_shift(PLX_FIELD_SIG) { (void)kwargs; (void)kwargs_len; plugin_field(fields, n_fields, out, FIELD_SAME, 0); }
+void _polars_plugin_plx_diff(PLX_PLUGIN_SIG) {
+  bool ok = true;
+  const long long n = pickle_signed_value(kwargs, kwargs_len, "n", 1, &ok);
+  plugin_rowfn("plx_diff", inputs, n_inputs, kwargs, kwargs_len, out, ctx, [&](const std::vector<ColumnPtr>& keys, const ColumnPtr& v) {
+    PLX_REQUIRE(ok, PLX_ERR_INVALID, "plx_diff: kwargs n must be an integer (that fits 32 bits)");
+    return shift_call(keys, v, n, nullptr, 1, nullptr);
+  });
+}
+void _polars_plugin_field_plx_diff(PLX_FIELD_SIG) { (void)kwargs; (void)kwargs_len; plugin_field(fields, n_fields, out, FIELD_DIFF, 0); }
+void _polars_plugin_plx_rolling(PLX_PLUGIN_SIG) {
+  const int op = rolling_op_of(pickle_str_value(kwargs, kwargs_len, "op"));
+  bool ok_w = true, ok_m = true;
+  const long long w = pickle_signed_value(kwargs, kwargs_len, "window_size", 0, &ok_w);
+  const long long m = pickle_signed_value(kwargs, kwargs_len, "min_samples", w, &ok_m);
+  const int center = pickle_bool_value(kwargs, kwargs_len, "center", 0);
+  plugin_rowfn("plx_rolling", inputs, n_inputs, kwargs, kwargs_len, out, ctx, [&](const std::vector<ColumnPtr>& keys, const ColumnPtr& v) {
+    PLX_REQUIRE(op >= 0, PLX_ERR_INVALID, kRollingKwargs);
+    PLX_REQUIRE(ok_w && w >= 1, PLX_ERR_INVALID, "plx_rolling: kwargs window_size must be an integer of at least 1");
+    PLX_REQUIRE(ok_m && m >= 1 && m <= w, PLX_ERR_INVALID, "plx_rolling: kwargs min_samples must be an integer in 1..window_size");
+    PLX_REQUIRE(center >= 0, PLX_ERR_INVALID, "plx_rolling: kwargs center must be a bool");
+    return rolling_call(keys, v, op, w, m, center, nullptr);
+  });
+}
+void _polars_plugin_field_plx_rolling(PLX_FIELD_SIG) {
+  const int op = rolling_op_of(pickle_str_value(kwargs, kwargs_len, "op"));
+  if (op < 0) { t_plugin_error = kRollingKwargs; if (out) out->release = nullptr; return; }
+  plugin_field(fields, n_fields, out, op == PLX_ROLLING_SUM ? FIELD_SUM : op == PLX_ROLLING_MEAN ? FIELD_MEAN : FIELD_SAME, 0);
 }
 void _polars_plugin_plx_filter(PLX_PLUGIN_SIG) {
   (void)kwargs; (void)kwargs_len;

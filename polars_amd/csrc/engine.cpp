@@ -22,6 +22,7 @@
 #include "kernels_fused.hpp"
 #include "ops.hpp"
 #include "quantile.hpp"
+#include "rolling.hpp"
 #include "sort.hpp"
 #include "temporal.hpp"
 #include "variance.hpp"
@@ -88,6 +89,19 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       PLX_REQUIRE(cumulative::method_ok(e.op), PLX_ERR_INVALID, "rank expression: method " + std::to_string(e.op) + " is no plx_rank_method (0 = average, 1 = min, 2 = max, 3 = dense, 4 = ordinal)");
       PLX_REQUIRE(e.lit.u <= 1, PLX_ERR_INVALID, "rank expression: descending rides in lit.u as 0 / 1, got " + std::to_string((long long)e.lit.i));
     }
+    if (e.kind == PLX_AE_SHIFT) {
+      PLX_REQUIRE(e.lhs >= 0, PLX_ERR_INVALID, "shift / diff expression needs an operand (lhs)");
+      PLX_REQUIRE(e.op == 0 || e.op == 1, PLX_ERR_INVALID, "shift / diff expression: op " + std::to_string(e.op) + " is neither 0 (shift) nor 1 (diff)");
+      PLX_REQUIRE(e.rhs < 0 || (e.op == 0 && e.rhs < i && ae[e.rhs].kind == PLX_AE_LITERAL && !ae[e.rhs].is_null), PLX_ERR_INVALID,
+                  "shift expression: fill_value (rhs) must be a non-null literal node or -1, and diff takes none");
+    }
+    if (e.kind == PLX_AE_ROLLING) {
+      PLX_REQUIRE(e.lhs >= 0, PLX_ERR_INVALID, "rolling expression needs an operand (lhs)");
+      PLX_REQUIRE(rolling::op_ok(e.op), PLX_ERR_INVALID, "rolling expression: op " + std::to_string(e.op) + " is no plx_rolling_op (0 = sum, 1 = mean, 2 = min, 3 = max)");
+      const rolling::Params rp = rolling::unpack_params(e.lit.u);
+      PLX_REQUIRE(rp.window >= 1 && rp.window <= 0x7fffffffull, PLX_ERR_INVALID, "rolling expression: window_size (lit.u bits 0..31) must be at least 1 and below 2^31, got " + std::to_string((long long)rp.window));
+      PLX_REQUIRE(rp.min_samples >= 1 && rp.min_samples <= rp.window, PLX_ERR_INVALID, "rolling expression: min_samples (lit.u bits 32..62) must lie in 1..window_size, got " + std::to_string((long long)rp.min_samples));
+    }
     p.ae.push_back(std::move(e));
   }
   // a key link stands below a window (as its rhs) or below another link (as its rhs), nowhere else
@@ -144,9 +158,9 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       std::function<bool(int)> has_window = [&](int e) { return e >= 0 && (p.ae[e].kind == PLX_AE_WINDOW || has_window(p.ae[e].lhs) || has_window(p.ae[e].rhs) || has_window(p.ae[e].cond)); };
       for (int e : n.keys) PLX_REQUIRE(!has_window(e), PLX_ERR_INVALID, "group_by: a window expression (.over) cannot stand in the keys of a group_by");
       for (int e : n.exprs) PLX_REQUIRE(!has_window(e), PLX_ERR_INVALID, "group_by: a window expression (.over) cannot stand in the aggregate list of a group_by; aggregate first, or use the window in select / with_columns");
-      std::function<bool(int)> has_rowfn = [&](int e) { return e >= 0 && (p.ae[e].kind == PLX_AE_CUMULATIVE || p.ae[e].kind == PLX_AE_RANK || has_rowfn(p.ae[e].lhs) || has_rowfn(p.ae[e].rhs) || has_rowfn(p.ae[e].cond)); };
-      for (int e : n.keys) PLX_REQUIRE(!has_rowfn(e), PLX_ERR_INVALID, "group_by: a cumulative / ranking expression (cum_sum, cum_min, cum_max, cum_count, rank) cannot stand in the keys of a group_by; compute it in with_columns first");
-      for (int e : n.exprs) PLX_REQUIRE(!has_rowfn(e), PLX_ERR_INVALID, "group_by: a cumulative / ranking expression (cum_sum, cum_min, cum_max, cum_count, rank) cannot stand in the aggregate list of a group_by; it keeps one value per row -- use it in select / with_columns, with .over(keys) for partitions");
+      std::function<bool(int)> has_rowfn = [&](int e) { return e >= 0 && (p.ae[e].kind == PLX_AE_CUMULATIVE || p.ae[e].kind == PLX_AE_RANK || p.ae[e].kind == PLX_AE_SHIFT || p.ae[e].kind == PLX_AE_ROLLING || has_rowfn(p.ae[e].lhs) || has_rowfn(p.ae[e].rhs) || has_rowfn(p.ae[e].cond)); };
+      for (int e : n.keys) PLX_REQUIRE(!has_rowfn(e), PLX_ERR_INVALID, "group_by: a cumulative / ranking expression (cum_sum, cum_min, cum_max, cum_count, rank) or a shift / diff / rolling expression cannot stand in the keys of a group_by; compute it in with_columns first");
+      for (int e : n.exprs) PLX_REQUIRE(!has_rowfn(e), PLX_ERR_INVALID, "group_by: a cumulative / ranking expression (cum_sum, cum_min, cum_max, cum_count, rank) or a shift / diff / rolling expression cannot stand in the aggregate list of a group_by; it keeps one value per row -- use it in select / with_columns, with .over(keys) for partitions");
     }
     PLX_REQUIRE(n.input < i && n.input_right < i, PLX_ERR_INVALID, "IR arena must be topologically ordered (inputs before consumers)");
     p.ir.push_back(std::move(n));
@@ -207,6 +221,19 @@ int infer_dtype(const Plan& plan, int e, const Frame& schema) {
       return out;
     }
     case PLX_AE_RANK: infer_dtype(plan, x.lhs, schema); return cumulative::rank_dtype(x.op);
+    case PLX_AE_SHIFT: {
+      const int in = infer_dtype(plan, x.lhs, schema);
+      const int out = x.op == 1 ? rolling::diff_dtype(in) : (in >= PLX_BOOL && in <= PLX_F64 ? in : -1);
+      if (out < 0) fail(PLX_ERR_UNSUPPORTED, std::string(x.op == 1 ? "diff" : "shift") + " of a " + dtype_name(in) + " expression: " + (x.op == 1 ? "integer and float operands only" : "integer, float and Boolean operands only"));
+      if (x.rhs >= 0) PLX_REQUIRE(plan.ae.at(x.rhs).dtype == in, PLX_ERR_INVALID, std::string("shift: the fill_value literal's dtype ") + dtype_name(plan.ae.at(x.rhs).dtype) + " differs from the operand's " + dtype_name(in));
+      return out;
+    }
+    case PLX_AE_ROLLING: {
+      const int in = infer_dtype(plan, x.lhs, schema);
+      const int out = rolling::result_dtype(x.op, in);
+      if (out < 0) fail(PLX_ERR_UNSUPPORTED, std::string(rolling::op_name(x.op)) + " of a " + dtype_name(in) + " expression: integer, float and Boolean operands only");
+      return out;
+    }
     case PLX_AE_AGG: {
       int in = infer_dtype(plan, x.lhs, schema);
       switch (x.op) {
@@ -247,7 +274,9 @@ std::string output_name(const Plan& plan, int e) {
 // A window (PLX_AE_WINDOW) is a row-level value to everything around it: it does not reduce its node (no aggregate), it reads columns (a column outside an
 // aggregate), and the aggregates inside it belong to its own group-by (collect_aggs stops at it).
 // A cumulative or ranking node (PLX_AE_CUMULATIVE / PLX_AE_RANK) is row-level in the same way: one value per row, its operand is its own business.
-static bool is_rowfn(const AE& x) { return x.kind == PLX_AE_CUMULATIVE || x.kind == PLX_AE_RANK; }
+// ... and so is a shift / diff or rolling node (PLX_AE_SHIFT / PLX_AE_ROLLING): a fixed number of neighbouring rows of the same order.
+static bool is_neighbour_fn(const AE& x) { return x.kind == PLX_AE_SHIFT || x.kind == PLX_AE_ROLLING; }
+static bool is_rowfn(const AE& x) { return x.kind == PLX_AE_CUMULATIVE || x.kind == PLX_AE_RANK || is_neighbour_fn(x); }
 static bool contains_agg(const Plan& plan, int e) {
   if (e < 0) return false;
   const AE& x = plan.ae[e];
@@ -264,6 +293,15 @@ static bool contains_rowfn(const Plan& plan, int e) {
   if (e < 0) return false;
   const AE& x = plan.ae[e];
   return is_rowfn(x) || contains_rowfn(plan, x.lhs) || contains_rowfn(plan, x.rhs) || contains_rowfn(plan, x.cond);
+}
+static bool contains_neighbour_fn(const Plan& plan, int e) {
+  if (e < 0) return false;
+  const AE& x = plan.ae[e];
+  return is_neighbour_fn(x) || contains_neighbour_fn(plan, x.lhs) || contains_neighbour_fn(plan, x.rhs) || contains_neighbour_fn(plan, x.cond);
+}
+// why a fused pipeline leaves an expression list that holds a per-row function to the per-node route
+static const char* rowfn_route_note(const Plan& plan, int e) {
+  return contains_neighbour_fn(plan, e) ? "shift / diff / rolling expression: per-node route" : "cumulative / ranking expression: per-node route";
 }
 static bool contains_column_outside_agg(const Plan& plan, int e) {
   if (e < 0) return false;
@@ -357,6 +395,8 @@ static Evaluated eval(const Plan& plan, int e, const Frame& df, const std::map<i
     // ... and so is a cumulative or ranking node's
     case PLX_AE_CUMULATIVE: case PLX_AE_RANK:
       fail(PLX_ERR_UNSUPPORTED, std::string(x.kind == PLX_AE_RANK ? "rank" : cumulative::op_name(x.op)) + ": a cumulative / ranking expression stands in the expressions of select / with_columns and the predicate of filter only");
+    case PLX_AE_SHIFT: case PLX_AE_ROLLING:
+      fail(PLX_ERR_UNSUPPORTED, std::string(x.kind == PLX_AE_SHIFT ? (x.op == 1 ? "diff" : "shift") : rolling::op_name(x.op)) + ": a shift / diff / rolling expression stands in the expressions of select / with_columns and the predicate of filter only");
     case PLX_AE_AGG: {
       Evaluated c = eval(plan, x.lhs, df, overrides);
       if (x.op == PLX_AGG_VAR || x.op == PLX_AGG_STD) return {ops::scalar_column(ops::reduce_var(c.col, (int)x.lit.u, x.op == PLX_AGG_STD)), true};
@@ -643,8 +683,9 @@ class Compiler {
           default: throw Unsupported("operator inside a fused program");
         }
       }
-      case PLX_AE_WINDOW: case PLX_AE_WINDOW_KEY: throw Unsupported(contains_rowfn(plan, x.lhs) ? "cumulative / ranking expression: per-node route" : "window expression: per-node route");
+      case PLX_AE_WINDOW: case PLX_AE_WINDOW_KEY: throw Unsupported(contains_rowfn(plan, x.lhs) ? rowfn_route_note(plan, x.lhs) : "window expression: per-node route");
       case PLX_AE_CUMULATIVE: case PLX_AE_RANK: throw Unsupported("cumulative / ranking expression: per-node route");
+      case PLX_AE_SHIFT: case PLX_AE_ROLLING: throw Unsupported("shift / diff / rolling expression: per-node route");
       default: throw Unsupported("aggregation nested inside a row expression");
     }
   }
@@ -1850,7 +1891,7 @@ static int and_predicates(Compiler& c, const std::vector<int>& preds) {
 // Select(aggregations) over [Filter]* over `src`
 static bool fused_select(Plan& plan, const IRN& node, const std::vector<int>& preds, const FramePtr& src, FramePtr& out, Shape* shape_out, int* sid_out,
                          std::string* why, bool compile_only) {
-  for (int e : node.exprs) if (contains_rowfn(plan, e)) { if (why) *why = "cumulative / ranking expression: per-node route"; return false; }
+  for (int e : node.exprs) if (contains_rowfn(plan, e)) { if (why) *why = rowfn_route_note(plan, e); return false; }
   for (int e : node.exprs) if (contains_window(plan, e)) { if (why) *why = "window expression: per-node route"; return false; }
   for (int e : node.exprs) if (!contains_agg(plan, e) || contains_column_outside_agg(plan, e)) { if (why) *why = "select mixes row expressions and aggregations"; return false; }
   // select(lit(2.5).sum()) aggregates a one-row literal (sum 2.5, count 1, whatever the filter keeps), as the per-node evaluator does: a fused program would
@@ -1905,7 +1946,7 @@ static bool forget_assumed_bounds(const std::vector<ColumnPtr>& cols) {
 // GroupBy(keys, aggregations) over [Filter]* over `src`
 static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& preds, const FramePtr& src, FramePtr& out, Shape* shape_out, int* sid_out,
                           std::string* why, bool compile_only) {
-  for (int e : node.exprs) if (contains_rowfn(plan, e)) { if (why) *why = "cumulative / ranking expression: per-node route"; return false; }
+  for (int e : node.exprs) if (contains_rowfn(plan, e)) { if (why) *why = rowfn_route_note(plan, e); return false; }
   for (int e : node.exprs) if (contains_window(plan, e)) { if (why) *why = "window expression: per-node route"; return false; }
   for (int e : node.exprs) if (!contains_agg(plan, e) || contains_column_outside_agg(plan, e)) { if (why) *why = "group_by aggregation list contains a non-aggregated column"; return false; }
   Compiler c(plan, *src);
@@ -2926,7 +2967,11 @@ static ColumnPtr empty_column(int dtype) {
 // One per-row function of a node: `id` is the node eval() will look up (the PLX_AE_CUMULATIVE / PLX_AE_RANK itself, or the PLX_AE_WINDOW around it), `fn` the
 // function, `keys` the window's keys (none: the whole column).
 struct RowFn { int id, fn; std::vector<int> keys; };
-static std::string rowfn_name(const AE& x) { return x.kind == PLX_AE_RANK ? "rank" : cumulative::op_name(x.op); }
+static std::string rowfn_name(const AE& x) {
+  if (x.kind == PLX_AE_SHIFT) return x.op == 1 ? "diff" : "shift";
+  if (x.kind == PLX_AE_ROLLING) return rolling::op_name(x.op);
+  return x.kind == PLX_AE_RANK ? "rank" : cumulative::op_name(x.op);
+}
 // Buckets by key list: the cumulative functions of a bucket share one stable sort of the rows by the keys and one head mask (cumulative::scan_order); its ranks
 // share one sort_segments per (operand, descending) (cumulative::rank_order).  Every finished column goes into `done` under the function's id.
 static void run_rowfns(Plan& plan, const std::vector<RowFn>& fns, const Frame& in, std::map<int, ColumnPtr>& done) {
@@ -2954,14 +2999,25 @@ static void run_rowfns(Plan& plan, const std::vector<RowFn>& fns, const Frame& i
   for (const Bucket& b : buckets) {
     std::string key_names;
     for (int kx : b.keys) key_names += (key_names.empty() ? "" : ", ") + output_name(plan, kx);
-    std::vector<RowFn> cums, ranks;
-    for (const RowFn& r : b.fns) (plan.ae[r.fn].kind == PLX_AE_RANK ? ranks : cums).push_back(r);
+    std::vector<RowFn> cums, ranks, shifts, rolls;
+    for (const RowFn& r : b.fns) {
+      const int kind = plan.ae[r.fn].kind;
+      (kind == PLX_AE_RANK ? ranks : kind == PLX_AE_SHIFT ? shifts : kind == PLX_AE_ROLLING ? rolls : cums).push_back(r);
+    }
+    // the windows of the bucket's rolling functions, as written, for the plan text
+    std::string roll_w;
+    for (const RowFn& r : rolls) {
+      const std::string w = std::to_string((long long)rolling::unpack_params(plan.ae[r.fn].lit.u).window);
+      if (("+" + roll_w + "+").find("+" + w + "+") == std::string::npos) roll_w += (roll_w.empty() ? "" : "+") + w;
+    }
     const std::string rows = ", rows=" + std::to_string(in.height);
     if (in.height == 0) {      // an empty frame: empty columns of the right dtype, the plan text in the shape of every other
       for (int kx : b.keys) infer_dtype(plan, kx, in);
       for (const RowFn& r : b.fns) done[r.id] = empty_column(infer_dtype(plan, r.fn, in));
       if (!cums.empty()) plan.desc += "Cumulative{keys=[" + key_names + "], fns=" + std::to_string(cums.size()) + rows + ", route=cumulative[empty]}; ";
       if (!ranks.empty()) plan.desc += "Rank{keys=[" + key_names + "], fns=" + std::to_string(ranks.size()) + rows + ", route=rank[empty]}; ";
+      if (!shifts.empty()) plan.desc += "Shift{keys=[" + key_names + "], fns=" + std::to_string(shifts.size()) + rows + ", route=shift[empty]}; ";
+      if (!rolls.empty()) plan.desc += "Rolling{keys=[" + key_names + "], fns=" + std::to_string(rolls.size()) + rows + ", w=" + roll_w + ", route=rolling[empty]}; ";
       continue;
     }
     std::vector<ColumnPtr> keys;
@@ -2974,8 +3030,14 @@ static void run_rowfns(Plan& plan, const std::vector<RowFn>& fns, const Frame& i
       return operands.back().second;
     };
     flush_node_notes(plan);
+    // cumulative, shift and rolling functions of the bucket share ONE stable sort of the rows by the keys and one head mask; the shift and rolling functions also
+    // share the mask's prefix and compacted starts (their O(1) segment bounds)
+    cumulative::ScanOrder order;
+    if (!cums.empty() || !shifts.empty() || !rolls.empty()) order = cumulative::scan_order(keys, in.height);
+    rolling::Segments segs;
+    if (!shifts.empty() || !rolls.empty()) segs = rolling::segments_of(order);
+    const std::string order_desc = order.desc.rfind("cumulative[", 0) == 0 ? order.desc.substr(std::string("cumulative[").size()) : order.desc;      // "whole column]" | "sorted rows: ...]"
     if (!cums.empty()) {
-      const cumulative::ScanOrder order = cumulative::scan_order(keys, in.height);
       for (size_t i = 0; i < cums.size(); i++) {
         const RowFn& r = cums[i];
         const AE& f = plan.ae[r.fn];
@@ -2985,6 +3047,34 @@ static void run_rowfns(Plan& plan, const std::vector<RowFn>& fns, const Frame& i
         done[r.id] = twin < i ? done[cums[twin].id] : cumulative::scan_column(order, operand(f.lhs), f.op, f.lit.u != 0);
       }
       plan.desc += "Cumulative{keys=[" + key_names + "], fns=" + std::to_string(cums.size()) + rows + ", route=" + order.desc + "}; ";
+    }
+    if (!shifts.empty()) {
+      for (size_t i = 0; i < shifts.size(); i++) {
+        const RowFn& r = shifts[i];
+        const AE& f = plan.ae[r.fn];
+        infer_dtype(plan, r.fn, in);      // (the operand's dtype and the fill literal's are refused by name before anything runs)
+        size_t twin = i;
+        for (size_t j = 0; j < i && twin == i; j++) if (same_expr(plan, shifts[j].fn, r.fn)) twin = j;
+        if (twin < i) { done[r.id] = done[shifts[twin].id]; continue; }
+        const plx_scalar* fill = f.rhs >= 0 ? &plan.ae[f.rhs].lit : nullptr;
+        done[r.id] = rolling::shift_column(order, segs, operand(f.lhs), f.lit.i, fill, f.op == 1);
+      }
+      plan.desc += "Shift{keys=[" + key_names + "], fns=" + std::to_string(shifts.size()) + rows + ", route=shift[" + order_desc + "}; ";
+    }
+    if (!rolls.empty()) {
+      std::string routes;
+      for (size_t i = 0; i < rolls.size(); i++) {
+        const RowFn& r = rolls[i];
+        const AE& f = plan.ae[r.fn];
+        infer_dtype(plan, r.fn, in);
+        size_t twin = i;
+        for (size_t j = 0; j < i && twin == i; j++) if (same_expr(plan, rolls[j].fn, r.fn)) twin = j;
+        if (twin < i) { done[r.id] = done[rolls[twin].id]; continue; }
+        std::string route;
+        done[r.id] = rolling::rolling_column(order, segs, operand(f.lhs), f.op, rolling::unpack_params(f.lit.u), &route);
+        if (routes.find(route) == std::string::npos) routes += (routes.empty() ? "" : " + ") + route;
+      }
+      plan.desc += "Rolling{keys=[" + key_names + "], fns=" + std::to_string(rolls.size()) + rows + ", w=" + roll_w + ", route=" + routes + (order.perm ? "; " + order_desc.substr(0, order_desc.size() - 1) : "") + "}; ";
     }
     std::vector<bool> ranked(ranks.size(), false);
     for (size_t i = 0; i < ranks.size(); i++) {

@@ -120,4 +120,20 @@ RankOrder rank_order(const std::vector<ColumnPtr>& keys, const ColumnPtr& value,
 // One ranking method over `order`: O(1) per sorted position.  PLX_F64 ("average") or PLX_U32, the validity of the ranked column
 ColumnPtr rank_column(const RankOrder& order, int method);
 }  // namespace cumulative
+
+// ---- shift / diff and the rolling functions (kernels_rolling.hip; rolling.hpp holds the arithmetic) ----
+namespace rolling {
+struct Params;
+// What finds the segment of a sorted position in O(1) beside the order's head mask: the mask's per-word prefix and its compacted starts (cumulative::run_of).
+// Built once per key list and shared by every shift / diff / rolling function over it; empty for the whole column.
+struct Segments { Buf prefix, starts; int64_t n_segments = 0; };
+Segments segments_of(const cumulative::ScanOrder& order);
+// shift(n) / diff(n) of `value` along `order`: one launch.  fill (shift only): the value of the vacated rows, which are then valid; null: they are null.
+// shift(0) returns `value` itself.
+ColumnPtr shift_column(const cumulative::ScanOrder& order, const Segments& segs, const ColumnPtr& value, int64_t n, const plx_scalar* fill, bool diff);
+// One rolling function (a plx_rolling_op) along `order`.  *route = "rolling[tile halo: w=.., lds=..]" | "rolling[two scans: w=.., launches=7]" | "rolling[empty]".
+// tile_route_for(w): the route a window of w rows takes now (PLX_ROLLING_ROUTE=scans in the environment forces the two scans, read per call).
+bool tile_route_for(int64_t w);
+ColumnPtr rolling_column(const cumulative::ScanOrder& order, const Segments& segs, const ColumnPtr& value, int op, const Params& p, std::string* route);
+}  // namespace rolling
 }  // namespace plx

@@ -154,6 +154,43 @@ class Expr:
         Plain: over the whole column; directly under .over(keys): within each partition."""
         return Expr("rank", F.RANK_METHODS[check_rank_method(method)], self, value=(method, check_reverse(descending, "rank", "descending")))
 
+    # -- shift / diff and the fixed-window rolling functions ------------------------------------
+    def shift(self, n: int = 1, *, fill_value: Any = None) -> "Expr":
+        """Row i takes the operand's row i - n (py-polars expr.shift): n any integer, negative looks ahead, 0 is the operand itself, |n| >= the partition length
+        vacates every row.  Vacated rows are null, or hold `fill_value` (a literal the column's dtype can hold exactly) and are valid.  Dtype, name and the validity
+        of the moved rows are the operand's; every column dtype is taken.  Plain: over the whole column; directly under .over(keys): within each partition, in the
+        frame's row order."""
+        return Expr("shift", F.SHIFT_SHIFT, self, value=(check_shift_n(n, "shift"), check_fill_value(fill_value)))
+
+    def diff(self, n: int = 1, null_behavior: str = "ignore") -> "Expr":
+        """x[i] - x[i - n] (py-polars expr.diff), null where either row is null or row i - n lies outside the partition.  UInt8 -> Int16, UInt16 -> Int32, UInt32 /
+        UInt64 -> Int64, signed integers and floats keep their dtype; integers wrap.  null_behavior="drop" changes the height and is not built."""
+        if null_behavior != "ignore":
+            raise ValueError(f"diff(null_behavior={null_behavior!r}) is not built: the height is kept on this path, only null_behavior=\"ignore\" is served")
+        return Expr("shift", F.SHIFT_DIFF, self, value=(check_shift_n(n, "diff"), None))
+
+    def _rolling(self, what: str, window_size: Any, weights: Any, min_samples: Any, center: Any) -> "Expr":
+        return Expr("rolling", F.ROLLING_OPS[what], self, value=check_rolling(what, window_size, weights, min_samples, center))
+
+    def rolling_sum(self, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> "Expr":
+        """The sum over a window of `window_size` rows (py-polars expr.rolling_sum): the window of row i is the rows [i - window_size + 1, i], or centered
+        [i + h - window_size + 1, i + h] with h = (window_size - 1) // 2, clipped to the partition; null where it holds fewer than `min_samples` (default:
+        window_size) non-null values.  The dtype of cum_sum.  Weights and the temporal form ("7d") are not built."""
+        return self._rolling("rolling_sum", window_size, weights, min_samples, center)
+
+    def rolling_mean(self, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> "Expr":
+        """The mean of the window's non-null values (py-polars expr.rolling_mean): Float64, a Float32 operand stays Float32; see rolling_sum."""
+        return self._rolling("rolling_mean", window_size, weights, min_samples, center)
+
+    def rolling_min(self, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> "Expr":
+        """The minimum of the window's non-null values (py-polars expr.rolling_min): the dtype stays (Date / Datetime included); a NaN is ignored unless every valid
+        value of the window is NaN; see rolling_sum."""
+        return self._rolling("rolling_min", window_size, weights, min_samples, center)
+
+    def rolling_max(self, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> "Expr":
+        """The maximum of the window's non-null values (py-polars expr.rolling_max); see rolling_min."""
+        return self._rolling("rolling_max", window_size, weights, min_samples, center)
+
     # -- misc -----------------------------------------------------------------------------
     @property
     def str(self) -> "ExprStringNameSpace":
@@ -179,6 +216,12 @@ class Expr:
         if self.kind == "agg": return f"{self.lhs!r}.agg{self.op}()"
         if self.kind == "cum": return f"{self.lhs!r}.{CUM_NAMES[self.op]}({'reverse=True' if self.value else ''})"
         if self.kind == "rank": return f"{self.lhs!r}.rank({self.value[0]!r}{', descending=True' if self.value[1] else ''})"
+        if self.kind == "shift":
+            n, fill = self.value
+            return f"{self.lhs!r}.{'diff' if self.op == F.SHIFT_DIFF else 'shift'}({n}{'' if fill is None else f', fill_value={fill!r}'})"
+        if self.kind == "rolling":
+            w, m, c = self.value
+            return f"{self.lhs!r}.{ROLLING_NAMES[self.op]}({w}{'' if m == w else f', min_samples={m}'}{', center=True' if c else ''})"
         if self.kind == "window": return f"{self.lhs!r}.over([{', '.join(repr(k) for k in self.value)}])"
         if self.kind == "alias": return f"{self.lhs!r}.alias({self.name!r})"
         if self.kind == "cast": return f"{self.lhs!r}.cast({self.dtype})"
@@ -224,6 +267,47 @@ def check_reverse(flag: Any, what: str, name: str = "reverse") -> bool:
     if not isinstance(flag, (bool, np.bool_)):
         raise TypeError(f"{what}({name}=...) takes a bool, got {flag!r}")
     return bool(flag)
+
+
+ROLLING_NAMES = {v: k for k, v in F.ROLLING_OPS.items()}
+
+
+def check_shift_n(n: Any, what: str) -> int:
+    """n of shift / diff: any Python or numpy integer; a bool, a float or None is a TypeError."""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)):
+        raise TypeError(f"{what}(n=...) takes an integer, got n={n!r}")
+    return int(n)
+
+
+def check_fill_value(fill_value: Any) -> Any:
+    """fill_value of shift: None or a literal; whether the column's dtype holds it is decided where the dtype is known (plan.shift_fill_literal)."""
+    if isinstance(fill_value, Expr):
+        if fill_value.kind == "lit" and fill_value.dtype is None:
+            return fill_value.value
+        raise TypeError(f"shift(fill_value=...): an expression as fill_value ({fill_value!r}) is not built; fill_value is a literal")
+    return fill_value
+
+
+def check_rolling(what: str, window_size: Any, weights: Any, min_samples: Any, center: Any) -> tuple:
+    """(window_size, min_samples, center) of a rolling function: window_size an integer >= 1, min_samples an integer in 1..window_size (default: window_size),
+    center a bool.  Weights and a string window_size (the temporal form) are refused by name."""
+    if weights is not None:
+        raise ValueError(f"{what}(weights=...) is not built: only unweighted windows are served")
+    if isinstance(window_size, str):
+        raise ValueError(f"{what}(window_size={window_size!r}): a temporal window (and by=) is not built; window_size is a number of rows")
+    if isinstance(window_size, (bool, np.bool_)) or not isinstance(window_size, (int, np.integer)):
+        raise TypeError(f"{what}(window_size=...) takes an integer, got window_size={window_size!r}")
+    window_size = int(window_size)
+    if not 1 <= window_size <= F.ROLLING_MAX_WINDOW:
+        raise ValueError(f"{what}: window_size must be at least 1 (and below 2^31), got window_size={window_size}")
+    if min_samples is None:
+        min_samples = window_size
+    if isinstance(min_samples, (bool, np.bool_)) or not isinstance(min_samples, (int, np.integer)):
+        raise TypeError(f"{what}(min_samples=...) takes an integer, got min_samples={min_samples!r}")
+    min_samples = int(min_samples)
+    if not 1 <= min_samples <= window_size:
+        raise ValueError(f"{what}: min_samples must lie in 1..window_size ({window_size}), got min_samples={min_samples}")
+    return window_size, min_samples, check_reverse(center, what, "center")
 
 
 def check_rank_method(method: Any) -> str:
@@ -472,6 +556,30 @@ def cum_count(name: str, *, reverse: bool = False) -> Expr:
 
 def rank(name: str, method: str = "average", *, descending: bool = False) -> Expr:
     return col(name).rank(method, descending=descending)
+
+
+def shift(name: str, n: int = 1, *, fill_value: Any = None) -> Expr:
+    return col(name).shift(n, fill_value=fill_value)
+
+
+def diff(name: str, n: int = 1, null_behavior: str = "ignore") -> Expr:
+    return col(name).diff(n, null_behavior)
+
+
+def rolling_sum(name: str, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> Expr:
+    return col(name).rolling_sum(window_size, weights, min_samples=min_samples, center=center)
+
+
+def rolling_mean(name: str, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> Expr:
+    return col(name).rolling_mean(window_size, weights, min_samples=min_samples, center=center)
+
+
+def rolling_min(name: str, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> Expr:
+    return col(name).rolling_min(window_size, weights, min_samples=min_samples, center=center)
+
+
+def rolling_max(name: str, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> Expr:
+    return col(name).rolling_max(window_size, weights, min_samples=min_samples, center=center)
 
 
 _EPOCH = _dt.date(1970, 1, 1)

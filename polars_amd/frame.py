@@ -489,6 +489,66 @@ class Series:
         F.check(F.lib().plx_rank(None, 0, self._h, F.RANK_METHODS[method], int(descending), C.byref(h)))
         return Series._from_handle(self.name, h.value, out_dt)
 
+    # -- shift / diff and the rolling functions (plx_shift / plx_rolling over the whole column) --------
+    def shift(self, n: int = 1, *, fill_value: Any = None) -> "Series":
+        """Row i takes row i - n (Series.shift): vacated rows are null, or hold `fill_value` and are valid.  Dtype, name and dictionary stay."""
+        from .expr import check_fill_value, check_shift_n
+        n, fill_value = check_shift_n(n, "shift"), check_fill_value(fill_value)
+        out_dt = P.shift_result_dtype(F.SHIFT_SHIFT, self.dtype)
+        fill = None
+        if fill_value is not None:
+            v, fill = P.shift_fill_literal(fill_value, self.dtype), F.Scalar()
+            phys = self.dtype.physical
+            if phys == F.F64: fill.f64 = float(v)
+            elif phys == F.F32: fill.f32 = float(v)
+            elif phys in (F.U8, F.U16, F.U32, F.U64, F.BOOL): fill.u = int(v) & 0xFFFFFFFFFFFFFFFF
+            else: fill.i = int(v)
+        F.ensure_init()
+        F.set_plan_note(None)
+        h = C.c_uint64()
+        F.check(F.lib().plx_shift(None, 0, self._h, max(-(2 ** 63), min(2 ** 63 - 1, n)), C.byref(fill) if fill is not None else None, 0, C.byref(h)))
+        return Series._from_handle(self.name, h.value, out_dt)
+
+    def diff(self, n: int = 1, null_behavior: str = "ignore") -> "Series":
+        """x[i] - x[i - n] (Series.diff): null where either row is null or row i - n does not exist; unsigned dtypes widen to the next signed one."""
+        from .expr import check_shift_n
+        n = check_shift_n(n, "diff")
+        if null_behavior != "ignore":
+            raise ValueError(f"diff(null_behavior={null_behavior!r}) is not built: the height is kept on this path, only null_behavior=\"ignore\" is served")
+        out_dt = P.shift_result_dtype(F.SHIFT_DIFF, self.dtype)
+        F.ensure_init()
+        F.set_plan_note(None)
+        h = C.c_uint64()
+        F.check(F.lib().plx_shift(None, 0, self._h, max(-(2 ** 63), min(2 ** 63 - 1, n)), None, 1, C.byref(h)))
+        return Series._from_handle(self.name, h.value, out_dt)
+
+    def _rolling(self, what: str, window_size: Any, weights: Any, min_samples: Any, center: Any) -> "Series":
+        from .expr import check_rolling
+        w, m, c = check_rolling(what, window_size, weights, min_samples, center)
+        op = F.ROLLING_OPS[what]
+        out_dt = P.rolling_result_dtype(op, self.dtype)      # TypeError: a dtype the function does not take
+        F.ensure_init()
+        F.set_plan_note(None)
+        h = C.c_uint64()
+        F.check(F.lib().plx_rolling(None, 0, self._h, op, w, m, int(c), C.byref(h)))
+        return Series._from_handle(self.name, h.value, out_dt)
+
+    def rolling_sum(self, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> "Series":
+        """The sum over a window of `window_size` rows (Series.rolling_sum): null below `min_samples` (default: window_size) non-null values; the dtype of cum_sum."""
+        return self._rolling("rolling_sum", window_size, weights, min_samples, center)
+
+    def rolling_mean(self, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> "Series":
+        """The mean of the window's non-null values (Series.rolling_mean): Float64, Float32 stays Float32."""
+        return self._rolling("rolling_mean", window_size, weights, min_samples, center)
+
+    def rolling_min(self, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> "Series":
+        """The minimum of the window's non-null values (Series.rolling_min): the dtype stays; a NaN is ignored unless every valid value of the window is NaN."""
+        return self._rolling("rolling_min", window_size, weights, min_samples, center)
+
+    def rolling_max(self, window_size: int, weights: Any = None, *, min_samples: Optional[int] = None, center: bool = False) -> "Series":
+        """The maximum of the window's non-null values (Series.rolling_max)."""
+        return self._rolling("rolling_max", window_size, weights, min_samples, center)
+
     @property
     def str(self) -> "SeriesStringNameSpace":
         """String predicates (starts_with / ends_with / contains of a literal) on a dictionary column or on a column of raw views."""

@@ -804,7 +804,7 @@ def _row_preserving(exprs) -> bool:
     def walk(e) -> bool:
         if e is None:
             return True
-        if e.kind in ("agg", "len", "cum", "rank"):
+        if e.kind in ("agg", "len") or e.kind in P.ROW_FUNCTION_KINDS:
             return False
         return all(walk(c) for c in e.children())
     return all(walk(e) for e in exprs) and any(expr_columns(e) for e in exprs)
@@ -812,7 +812,7 @@ def _row_preserving(exprs) -> bool:
 
 def _has_window(e: Optional[Expr]) -> bool:
     """a window expression (f.over(keys)) or a cumulative / ranking expression anywhere in `e`: both read every row of their input"""
-    return e is not None and (e.kind in ("window", "cum", "rank") or any(_has_window(c) for c in e.children()))
+    return e is not None and (e.kind == "window" or e.kind in P.ROW_FUNCTION_KINDS or any(_has_window(c) for c in e.children()))
 
 
 def scan_under(node: P.Node):

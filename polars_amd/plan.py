@@ -15,7 +15,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 from . import _ffi as F
 from . import datatypes as T
-from .expr import CUM_NAMES, STR_MATCH_NAMES, Expr, dt_part_dtype, dt_unit, literal_physical, str_match_host, str_pattern_bytes
+from .expr import CUM_NAMES, ROLLING_NAMES, STR_MATCH_NAMES, Expr, dt_part_dtype, dt_unit, literal_physical, str_match_host, str_pattern_bytes
 
 Schema = Dict[str, T.DataType]
 
@@ -87,7 +87,7 @@ def describe_windows(node: Node) -> List[str]:
         f = e.lhs if e.kind == "window" else None
         while f is not None and f.kind == "alias":
             f = f.lhs
-        if e.kind == "window" and f.kind not in ("cum", "rank"):      # (a cumulative / ranking function under .over has its own line: describe_cumulatives)
+        if e.kind == "window" and f.kind not in ROW_FUNCTION_KINDS:      # (a cumulative / ranking / shift / rolling function under .over has its own line: describe_cumulatives)
             out.append(f"Window[{e.lhs!r} over [{', '.join(repr(k) for k in e.value)}], mapping=group_to_rows] in {node.kind}")
         for c in e.children():
             walk(c)
@@ -96,9 +96,15 @@ def describe_windows(node: Node) -> List[str]:
     return out
 
 
+ROW_FUNCTION_KINDS = ("cum", "rank", "shift", "rolling")      # one value per row from the rows around it: cum_*, rank, shift / diff, rolling_*
+_ROW_FUNCTION_TITLES = {"cum": "Cumulative", "rank": "Rank", "shift": "Shift", "rolling": "Rolling"}
+
+
 def describe_cumulatives(node: Node) -> List[str]:
-    """One line per cumulative / ranking expression under `node` (LazyFrame.explain): the function as written and its partition.  The route each one took is in the
-    physical plan of the last collect (`Cumulative{... route=cumulative[whole column] | cumulative[sorted rows: ...]}`, `Rank{... route=rank[sorted segments: ...]}`)."""
+    """One line per cumulative / ranking / shift / diff / rolling expression under `node` (LazyFrame.explain): the function as written and its partition.  The route
+    each one took is in the physical plan of the last collect (`Cumulative{... route=cumulative[whole column] | cumulative[sorted rows: ...]}`, `Rank{...
+    route=rank[sorted segments: ...]}`, `Shift{... route=shift[whole column] | shift[sorted rows: ...]}`, `Rolling{... route=rolling[tile halo: ...] | rolling[two
+    scans: ...]}`)."""
     out: List[str] = []
     for attr in ("input", "left", "right"):
         child = getattr(node, attr, None)
@@ -108,14 +114,14 @@ def describe_cumulatives(node: Node) -> List[str]:
     def walk(e, keys):
         if e is None:
             return
-        if e.kind in ("cum", "rank"):
+        if e.kind in ROW_FUNCTION_KINDS:
             over = "the whole column" if keys is None else "[" + ", ".join(repr(k) for k in keys) + "]"
-            out.append(f"{'Rank' if e.kind == 'rank' else 'Cumulative'}[{e!r} over {over}] in {node.kind}")
+            out.append(f"{_ROW_FUNCTION_TITLES[e.kind]}[{e!r} over {over}] in {node.kind}")
         if e.kind == "window":
             f = e.lhs
             while f is not None and f.kind == "alias":
                 f = f.lhs
-            if f is not None and f.kind in ("cum", "rank"):
+            if f is not None and f.kind in ROW_FUNCTION_KINDS:
                 walk(f, e.value)
                 return
         for c in e.children():
@@ -126,8 +132,98 @@ def describe_cumulatives(node: Node) -> List[str]:
 
 
 def has_row_function(e: Optional[Expr]) -> bool:
-    """a cumulative or ranking expression anywhere in `e`: like a window, it reads every row of its input"""
-    return e is not None and (e.kind in ("cum", "rank") or any(has_row_function(c) for c in e.children()))
+    """a cumulative, ranking, shift / diff or rolling expression anywhere in `e`: like a window, it reads every row of its input"""
+    return e is not None and (e.kind in ROW_FUNCTION_KINDS or any(has_row_function(c) for c in e.children()))
+
+
+def row_function_name(e: Expr) -> str:
+    if e.kind == "cum":
+        return CUM_NAMES[e.op]
+    if e.kind == "shift":
+        return "diff" if e.op == F.SHIFT_DIFF else "shift"
+    return ROLLING_NAMES[e.op] if e.kind == "rolling" else "rank"
+
+
+def shift_result_dtype(op: int, dt) -> T.DataType:
+    """shift keeps the dtype, whatever it is; diff widens unsigned operands (UInt8 -> Int16, UInt16 -> Int32, UInt32 / UInt64 -> Int64) and takes integers and floats
+    only: there is no Duration dtype here for a temporal difference, and Boolean / Categorical have none."""
+    if op == F.SHIFT_SHIFT:
+        if not isinstance(dt, T.DataType):
+            raise TypeError(f"shift() needs a column expression, got {dt}")
+        return dt
+    if not isinstance(dt, T.DataType) or not dt.is_numeric():
+        raise TypeError(f"diff() needs an integer or float expression, got {dt}" + (" (a temporal difference would be a Duration, which is not built)" if dt in (T.Date, T.Datetime) else ""))
+    return {T.UInt8: T.Int16, T.UInt16: T.Int32, T.UInt32: T.Int64, T.UInt64: T.Int64}.get(dt, dt)
+
+
+def rolling_result_dtype(op: int, dt) -> T.DataType:
+    """rolling_sum follows cum_sum, rolling_mean is Float64 (Float32 stays), rolling_min / rolling_max keep the dtype and are the only ones to take Date / Datetime;
+    Categorical operands are refused everywhere (codes are not lexical order, and sum nothing)."""
+    name = ROLLING_NAMES[op]
+    temporal_ok = op in (F.ROLLING_MIN, F.ROLLING_MAX)
+    if not isinstance(dt, T.DataType) or isinstance(dt, T.Categorical) or not (dt.is_numeric() or dt == T.Boolean or (temporal_ok and dt in (T.Date, T.Datetime))):
+        raise TypeError(f"{name}() needs an integer, float or Boolean expression{' (or a Date / Datetime one)' if temporal_ok else ''}, got {dt}")
+    if op == F.ROLLING_SUM:
+        return sum_dtype(dt)
+    if op == F.ROLLING_MEAN:
+        return T.Float32 if dt == T.Float32 else T.Float64
+    return dt
+
+
+def shift_fill_literal(fill: Any, dt: T.DataType):
+    """The physical value of shift's fill_value for a column of dtype `dt`; TypeError naming fill_value when the dtype cannot hold it exactly."""
+    import datetime as _dt
+
+    import numpy as np
+
+    def bad(why: str = ""):
+        return TypeError(f"shift(fill_value={fill!r}): a {dt} column cannot hold this fill_value exactly{why}")
+    if isinstance(fill, np.generic):
+        fill = fill.item()
+    if isinstance(dt, T.Categorical):
+        cats = list(dt.categories)
+        if not isinstance(fill, str) or fill not in cats:
+            raise bad(" (a Categorical column takes a string of its dictionary)")
+        return cats.index(fill)
+    if dt == T.Boolean:
+        if not isinstance(fill, bool):
+            raise bad()
+        return fill
+    if isinstance(fill, bool):
+        raise bad()
+    if dt == T.Date:
+        if isinstance(fill, _dt.date) and not isinstance(fill, _dt.datetime):
+            fill = literal_physical(fill)[0]
+        if not isinstance(fill, int) or not -(2 ** 31) <= fill < 2 ** 31:
+            raise bad()
+        return fill
+    if dt == T.Datetime:
+        if isinstance(fill, _dt.datetime):
+            us = literal_physical(fill)[0]
+            per = dt.ticks_per_second()
+            if (us * per) % 1_000_000:
+                raise bad()
+            fill = us * per // 1_000_000
+        if not isinstance(fill, int) or not -(2 ** 63) <= fill < 2 ** 63:
+            raise bad()
+        return fill
+    if dt.is_integer():
+        if isinstance(fill, float) and fill.is_integer():
+            fill = int(fill)
+        ii = np.iinfo(dt.np_dtype)
+        if not isinstance(fill, int) or not ii.min <= fill <= ii.max:
+            raise bad()
+        return fill
+    if dt.is_float():
+        if not isinstance(fill, (int, float)):
+            raise bad()
+        f = float(fill)
+        if isinstance(fill, int) and int(f) != fill:
+            raise bad()
+        if dt == T.Float32 and f == f and float(np.float32(f)) != f:
+            raise bad()
+        return f
+    raise bad()
 
 
 def cum_result_dtype(op: int, dt) -> T.DataType:
@@ -313,13 +409,27 @@ class Lowering:
             idx, dt = self.lower_expr(e.lhs, schema)
             method, descending = e.value
             return self._push(kind=F.AE_RANK, op=F.RANK_METHODS[method], lhs=idx, lit=int(bool(descending))), rank_result_dtype(method, dt)
+        if k == "shift":
+            # x.shift(n, fill_value=v) / x.diff(n): AE_SHIFT with the operand in lhs, 0 / 1 in `op`, n in the literal slot (plx_aexpr.lit.i) and the fill literal,
+            # typed as the operand, in rhs
+            self._check_row_operand(e)
+            idx, dt = self.lower_expr(e.lhs, schema)
+            out = shift_result_dtype(e.op, dt)
+            n, fill = e.value
+            fi = -1 if fill is None else self._lit_node(shift_fill_literal(fill, dt), dt)
+            return self._push(kind=F.AE_SHIFT, op=e.op, lhs=idx, rhs=fi, lit=max(-(2 ** 63), min(2 ** 63 - 1, int(n)))), out
+        if k == "rolling":
+            self._check_row_operand(e)
+            idx, dt = self.lower_expr(e.lhs, schema)
+            w, m, c = e.value
+            return self._push(kind=F.AE_ROLLING, op=e.op, lhs=idx, lit=F.rolling_pack(w, m, c)), rolling_result_dtype(e.op, dt)
         if k == "window":
             f = e.lhs
             while f.kind == "alias":
                 f = f.lhs
-            if f.kind not in ("cum", "rank") and has_row_function(e.lhs):
-                raise TypeError(f"{e!r}: under .over() a function that mixes a cumulative / ranking expression with anything else is not built; put .over(keys) directly on "
-                                "the cumulative / ranking expression (and on each aggregate) and the arithmetic outside")
+            if f.kind not in ROW_FUNCTION_KINDS and has_row_function(e.lhs):
+                raise TypeError(f"{e!r}: under .over() a function that mixes a cumulative / ranking expression (or a shift / diff / rolling expression) with anything else is not built; put "
+                                ".over(keys) directly on that expression (and on each aggregate) and the arithmetic outside")
             # f.over(k1, k2, ...): AE_WINDOW with the function in lhs and the first link of the key chain in rhs; one AE_WINDOW_KEY link per key (lhs = the key,
             # rhs = the next link or -1).  The arena is topological, so the links are pushed last key first.  The engine checks that f aggregates and the keys do not
             fi, fdt = self.lower_expr(e.lhs, schema)
@@ -528,15 +638,15 @@ class Lowering:
 
     def _check_row_operand(self, e: Expr) -> None:
         """The operand of a cumulative / ranking expression is row-level: no aggregate, no window and no other cumulative / ranking expression inside."""
-        what = CUM_NAMES[e.op] if e.kind == "cum" else "rank"
+        what = row_function_name(e)
 
         def walk(x):
             if x.kind in ("agg", "len"):
                 raise TypeError(f"{what}(): an aggregate ({x!r}) inside the operand of a cumulative / ranking expression is not built; the operand is a row-level expression")
             if x.kind == "window":
                 raise TypeError(f"{what}(): a window expression ({x!r}) inside the operand of a cumulative / ranking expression is not built; compute it in with_columns first")
-            if x.kind in ("cum", "rank"):
-                raise TypeError(f"{what}(): a cumulative / ranking expression ({x!r}) inside the operand of another one is not built; compute the inner one in with_columns first")
+            if x.kind in ROW_FUNCTION_KINDS:
+                raise TypeError(f"{what}(): a cumulative / ranking / shift / rolling expression ({x!r}) inside the operand of another one is not built; compute the inner one in with_columns first")
             for c in x.children():
                 walk(c)
         walk(e.lhs)
@@ -575,7 +685,7 @@ class Lowering:
             keys, aggs, out_schema = [], [], {}
             for e in list(n.keys) + list(n.aggs):
                 if has_row_function(e):
-                    raise TypeError(f"group_by: a cumulative / ranking expression ({e!r}) cannot stand in the keys or aggregates of a group_by: it keeps one value per "
+                    raise TypeError(f"group_by: a cumulative / ranking expression or a shift / diff / rolling expression ({e!r}) cannot stand in the keys or aggregates of a group_by: it keeps one value per "
                                     "row; use it in select / with_columns, with .over(keys) for partitions")
             for e in n.keys:
                 idx, dt = self.lower_expr(e, schema)
@@ -649,7 +759,9 @@ class Lowering:
                     a.lit.u = int(d["lit"]) & 0xFFFFFFFFFFFFFFFF
                 else:
                     a.lit.i = int(d["lit"])
-            if d["kind"] in (F.AE_TEMPORAL, F.AE_CUMULATIVE, F.AE_RANK) or (d["kind"] == F.AE_AGG and d["op"] in (F.AGG_VAR, F.AGG_STD)):
+            if d["kind"] == F.AE_SHIFT:
+                a.lit.i = int(d["lit"])            # n, signed
+            if d["kind"] in (F.AE_TEMPORAL, F.AE_CUMULATIVE, F.AE_RANK, F.AE_ROLLING) or (d["kind"] == F.AE_AGG and d["op"] in (F.AGG_VAR, F.AGG_STD)):
                 a.lit.u = int(d["lit"])            # the operand's time unit / the ddof of var and std rides in the literal slot, like a lookup bitmap's handle
             if d["kind"] == F.AE_AGG and d["op"] == F.AGG_QUANTILE:
                 a.lit.f64 = float(d["lit"])        # q (the interpolation went into the dtype slot with every other field)

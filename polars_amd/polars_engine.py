@@ -209,8 +209,44 @@ class Translator:
                 if not isinstance(descending, bool):
                     raise NotSupported(f"rank with descending={descending!r}")
                 return E.Expr("rank", F.RANK_METHODS[method], self.expr(inputs[0]), value=(method, descending))
+            # shift / diff: the visitor hands n (and shift_and_fill's fill value) over as input expressions; only literals are served.  ("shift",) [x, n],
+            # ("shift_and_fill",) [x, n, fill], ("diff", null_behavior) [x, n].  The fixed-window rolling functions carry RollingOptionsFixedWindow in order:
+            # (name, window_size, min_periods, weights, center).  Restated from the reference's sources, like the five above; other shapes are refused by name
+            if name in ("shift", "shift_and_fill", "diff"):
+                want = 3 if name == "shift_and_fill" else 2
+                if len(inputs) != want:
+                    raise NotSupported(f"function {name} with {len(inputs)} inputs")
+                n = self._literal_value(inputs[1], f"{name} by an expression: n must be an integer literal")
+                if isinstance(n, bool) or not isinstance(n, int):
+                    raise NotSupported(f"{name} with n={n!r}")
+                if name == "diff":
+                    behavior = str(data[1]).lower().split(".")[-1] if len(data) > 1 else "ignore"
+                    if behavior != "ignore":
+                        raise NotSupported(f"diff with null_behavior={behavior}: the height is kept on this path")
+                    return E.Expr("shift", F.SHIFT_DIFF, self.expr(inputs[0]), value=(n, None))
+                fill = self._literal_value(inputs[2], "shift with an expression as fill_value: fill_value must be a literal") if want == 3 else None
+                return E.Expr("shift", F.SHIFT_SHIFT, self.expr(inputs[0]), value=(n, fill))
+            if name in F.ROLLING_OPS and len(inputs) == 1:
+                window_size, min_samples, weights, center = (list(data[1:5]) + [None] * 4)[:4]
+                center = False if center is None else center
+                if weights is not None:
+                    raise NotSupported(f"{name} with weights")
+                if isinstance(window_size, str):
+                    raise NotSupported(f"{name} with a temporal window {window_size!r}")
+                try:
+                    params = E.check_rolling(name, window_size, None, min_samples, center)
+                except (TypeError, ValueError) as err:
+                    raise NotSupported(str(err)) from None
+                return E.Expr("rolling", F.ROLLING_OPS[name], self.expr(inputs[0]), value=params)
             raise NotSupported(f"function {name or '?'}")
         raise NotSupported(f"expression node {kind}")
+
+    def _literal_value(self, node_id: int, why: str) -> Any:
+        """the python value of a Literal expression node; anything else is refused with `why`"""
+        x = self.nt.view_expression(node_id)
+        if type(x).__name__ != "Literal":
+            raise NotSupported(why)
+        return x.value
 
     def named(self, e: Any) -> E.Expr:
         """PyExprIR (visit.rs:19-24): expression node + output name."""

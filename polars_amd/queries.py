@@ -80,6 +80,21 @@ def top3_price_per_flag(lineitem):
     return lineitem.filter(c("l_extendedprice").rank("ordinal", descending=True).over("l_returnflag", "l_linestatus") <= 3)
 
 
+def moving_average_revenue_by_flag(lineitem):
+    """with_columns((l_extendedprice * (1 - l_discount)).rolling_mean(7, min_samples=1).over(l_returnflag).alias("revenue_ma7")) -- the mean revenue of every line
+    and the up to six lines of its flag before it, in the frame's row order.  The stable sort and head mask of the cumulative functions, then one tile-halo launch:
+    two segmented scans in registers and one combine per row, never a difference of prefixes"""
+    c = E.col
+    return lineitem.with_columns((c("l_extendedprice") * (1.0 - c("l_discount"))).rolling_mean(7, min_samples=1).over("l_returnflag").alias("revenue_ma7"))
+
+
+def quantity_change_by_flag(lineitem):
+    """with_columns(l_quantity.diff().over(l_returnflag).alias("quantity_change"), l_quantity.shift(1).over(l_returnflag).alias("previous_quantity")) -- every
+    line's quantity against the line of its flag before it (null on the first line of a flag).  Both share one sorted order; one launch each"""
+    c = E.col
+    return lineitem.with_columns(c("l_quantity").diff().over("l_returnflag").alias("quantity_change"), c("l_quantity").shift(1).over("l_returnflag").alias("previous_quantity"))
+
+
 def q1(lineitem, cutoff=Q1_CUTOFF):
     """TPC-H Q1; the final sort by (flag, status) happens on the host."""
     c = E.col
