@@ -677,6 +677,14 @@ int32_t plx_last_scan_tile_rows(void);
  * aggregate, like PLX_SHARED_CELLS=0 in the environment (read once, at the first scan). */
 int32_t plx_last_lds_cells(void);
 void plx_set_shared_cells(int32_t on);
+/* The tail of a group-by on the LDS-table route: one kernel compacts the table, finalises every output column and writes one result block, which the host fetches
+ * in one copy behind one synchronisation and keeps as host mirrors of the result columns.  plx_set_groupby_tail(0) keeps the separate compaction, finalisation and
+ * download steps, like PLX_GROUPBY_TAIL=0 in the environment (read once, at the first such group-by).  plx_last_groupby_tail: 1 when the calling thread's last fused
+ * group-by finished through the tail kernel, else 0.  plx_last_download_mirrored: 1 when the calling thread's last plx_column_to_host / plx_frame_to_host was served
+ * from host mirrors without a device call (every requested column had one), else 0. */
+void plx_set_groupby_tail(int32_t on);
+int32_t plx_last_groupby_tail(void);
+int32_t plx_last_download_mirrored(void);
 /* The cell plan as a pure function (no GPU needed).  The program is AOT shape `static_shape_id`, or (-1) the arrays: ops = n_ops x {code, dst, a, b, c}, aggs =
  * n_aggs x {kind, src}.  known / lo / hi: per aggregate, the bound lo <= v <= hi on its source; wg_rows: rows one workgroup can add to its table.  out gets
  * {cells per group, shift, cell[k] for every aggregate, the aggregate whose cell k is read from or -1 for every aggregate}; returns the aggregate count, -1 on bad

@@ -271,6 +271,9 @@ SIGNATURES = {
     "plx_last_scan_tile_rows": (C.c_int32, []),
     "plx_last_lds_cells": (C.c_int32, []),
     "plx_set_shared_cells": (None, [C.c_int32]),
+    "plx_set_groupby_tail": (None, [C.c_int32]),
+    "plx_last_groupby_tail": (C.c_int32, []),
+    "plx_last_download_mirrored": (C.c_int32, []),
     "plx_cell_plan": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_uint8),
                                   C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_uint64, C.c_uint64, C.POINTER(C.c_int32)]),
     "plx_lds_wg_rows": (C.c_uint64, [C.c_int64, C.c_int32, C.c_int32]),
@@ -357,6 +360,21 @@ def last_lds_cells() -> int:
 def set_shared_cells(on: bool) -> None:
     """The switch behind PLX_SHARED_CELLS: False keeps one LDS cell per aggregate."""
     lib().plx_set_shared_cells(int(bool(on)))
+
+
+def set_groupby_tail(on: bool) -> None:
+    """The switch behind PLX_GROUPBY_TAIL: False keeps the separate compaction, finalisation and download steps of the LDS-table group-by."""
+    lib().plx_set_groupby_tail(int(bool(on)))
+
+
+def last_groupby_tail() -> int:
+    """1 when this thread's last fused group-by finished through the tail kernel, else 0."""
+    return int(lib().plx_last_groupby_tail())
+
+
+def last_download_mirrored() -> int:
+    """1 when this thread's last column / frame download was served from host mirrors without a device call, else 0."""
+    return int(lib().plx_last_download_mirrored())
 
 
 def cell_plan(facts, wg_rows, n_rows, static_shape_id=-1, dtypes=(), nullable=(), ops=(), aggs=()):

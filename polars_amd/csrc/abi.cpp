@@ -659,6 +659,25 @@ int plx_frame_dtypes(plx_frame f, int32_t* dtypes_out) {
 int plx_frame_to_host(plx_frame f, void* const* values_out, uint8_t* const* validity_out, int32_t* has_validity_out) {
   PLX_TRY
   FramePtr fr = get_frame(f);
+  // a result whose every requested column carries a host mirror (the group-by tail): memcpy, no device call, no staging buffer, no lock
+  {
+    bool any = false, all = true;
+    for (size_t i = 0; i < fr->cols.size(); i++) {
+      if (!((values_out && values_out[i]) || (validity_out && validity_out[i]))) continue;
+      any = true;
+      if (!fr->cols[i]->host) { all = false; break; }
+    }
+    set_last_download_mirrored(any && all ? 1 : 0);
+    if (any && all) {
+      for (size_t i = 0; i < fr->cols.size(); i++) {
+        const Column& c = *fr->cols[i];
+        if ((values_out && values_out[i]) || (validity_out && validity_out[i]))
+          column_to_host_mirrored(c, values_out ? values_out[i] : nullptr, validity_out ? validity_out[i] : nullptr, nullptr);
+        if (has_validity_out) has_validity_out[i] = c.validity ? 1 : 0;
+      }
+      return PLX_OK;
+    }
+  }
   // small results (a group-by / top-k output): one pack launch + ONE page-locked D2H copy instead of a staged pageable copy per buffer
   {
     struct Piece { const void* src; void* dst; size_t bytes; };
@@ -1400,6 +1419,9 @@ const char* plx_last_plan_encodings(void) { return t_plan_encoded.c_str(); }
 int32_t plx_last_scan_tile_rows(void) { return k::last_scan_tile_rows(); }
 int32_t plx_last_lds_cells(void) { return k::last_lds_cells(); }
 void plx_set_shared_cells(int32_t on) { k::set_shared_cells(on != 0); }
+void plx_set_groupby_tail(int32_t on) { k::set_groupby_tail(on != 0); }
+int32_t plx_last_groupby_tail(void) { return engine::last_groupby_tail(); }
+int32_t plx_last_download_mirrored(void) { return last_download_mirrored(); }
 uint64_t plx_lds_wg_rows(int64_t n_rows, int32_t grid, int32_t wide) { return (n_rows < 0 || grid < 1) ? 0 : k::lds_agg_wg_rows_of(n_rows, grid, wide != 0); }
 int32_t plx_cell_plan(int32_t static_shape_id, int32_t n_inputs, const int32_t* dtypes, const int32_t* nullable, int32_t n_ops, const uint8_t* ops, int32_t n_aggs, const uint8_t* aggs,
                       const uint8_t* known, const int64_t* lo, const int64_t* hi, uint64_t wg_rows, uint64_t n_rows, int32_t* out) {
@@ -1689,6 +1711,7 @@ int plx_strview_stamp_nulls(plx_column views_u64_pairs, plx_column valid_bool) {
     PLX_HIP(hipMemcpyAsync(copy->ptr, v->values->ptr, v->values->bytes, hipMemcpyDeviceToDevice, stream()));
     v->values = copy;
   }
+  drop_host_mirror(*v);
   k::strview_stamp_nulls(v->values->as<uint64_t>(), eff->values->as<uint64_t>(), m->len);
   PLX_HIP(hipStreamSynchronize(stream()));      // (`eff` may be a temporary)
   PLX_CATCH

@@ -121,7 +121,7 @@ void column_wires(const ColumnPtr& col, bool with_validity, std::vector<Wire>& o
   if (col->dtype == PLX_BOOL) out.push_back({bitmap_as_bytes(col->values, col->len), 1});
   else {
     auto v = std::make_shared<Column>(*col);
-    v->validity = nullptr;
+    v->validity = nullptr; v->host.reset();
     out.push_back({v, (size_t)dtype_width(col->dtype)});
   }
   if (with_validity) {

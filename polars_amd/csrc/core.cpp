@@ -283,7 +283,24 @@ ColumnPtr column_from_host(int dtype, const void* values, const uint8_t* validit
   return c;
 }
 
+static thread_local int t_last_download_mirrored = 0;
+int last_download_mirrored() { return t_last_download_mirrored; }
+void set_last_download_mirrored(int v) { t_last_download_mirrored = v; }
+void column_to_host_mirrored(const Column& c, void* values_out, uint8_t* validity_out, int32_t* has_validity) {
+  const HostMirror& m = *c.host;
+  const size_t vb = c.dtype == PLX_BOOL ? (size_t)((c.len + 7) / 8) : (size_t)c.len * dtype_width(c.dtype);
+  const size_t nb = (size_t)((c.len + 7) / 8);
+  PLX_REQUIRE(vb <= m.values_bytes && (!c.validity || nb <= m.valid_bytes), PLX_ERR_INVALID, "host mirror shorter than its column");
+  if (values_out && vb) memcpy(values_out, m.values(), vb);
+  if (validity_out && nb) {
+    if (c.validity) memcpy(validity_out, m.valid(), nb);
+    else memset(validity_out, 0xff, nb);
+  }
+  if (has_validity) *has_validity = c.validity ? 1 : 0;
+}
 void column_to_host(const ColumnPtr& c, void* values_out, uint8_t* validity_out, int32_t* has_validity) {
+  if (c->host) { column_to_host_mirrored(*c, values_out, validity_out, has_validity); t_last_download_mirrored = 1; return; }
+  t_last_download_mirrored = 0;
   size_t vb = c->dtype == PLX_BOOL ? (size_t)((c->len + 7) / 8) : (size_t)c->len * dtype_width(c->dtype);
   if (values_out && vb) PLX_HIP(hipMemcpyAsync(values_out, c->values->ptr, vb, hipMemcpyDeviceToHost, stream()));
   size_t nb = (size_t)((c->len + 7) / 8);

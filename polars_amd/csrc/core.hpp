@@ -111,6 +111,15 @@ struct EncodedShadow {
   int scans = 0;            // qualifying scans seen since the statistics were last dropped
   bool never_encode = false;   // the column was tried and does not encode (or its codes could not be allocated)
 };
+// The bytes of a result column on the host, exactly as column_to_host would deliver them: filled from the block the group-by tail kernel wrote (engine.cpp
+// groupby_tail_finish), which the host copies in its one transfer anyway.  Immutable; a column whose buffers are written after that drops it (drop_host_mirror).
+struct HostMirror {
+  std::shared_ptr<const std::vector<uint8_t>> bytes;   // the block, shared by the columns of one result
+  size_t values_off = 0, values_bytes = 0;             // >= the bytes a download of `len` rows reads
+  size_t valid_off = 0, valid_bytes = 0;               // valid_bytes == 0: the column has no validity
+  const uint8_t* values() const { return bytes->data() + values_off; }
+  const uint8_t* valid() const { return valid_bytes ? bytes->data() + valid_off : nullptr; }
+};
 struct Column {
   int dtype = PLX_I64;
   int64_t len = 0;
@@ -131,6 +140,7 @@ struct Column {
   int order_state = 0;         // 0 unknown, 1 (roughly) ascending, 2 unordered: sampled once when the column is the probe key of a large join (k::sample_sortedness)
   std::shared_ptr<EncodedShadow> shadow;   // null until the first qualifying scan; dropped with the statistics, freed with the column
   bool repeats_as_build_key = false;   // learned by a join that built on this column: some key occurs more than once (the next join skips the unique-key attempt; a fact about the column, whatever the predicate was)
+  std::shared_ptr<const HostMirror> host;   // null unless the group-by tail attached one after its last write to the column
   const void* data() const { return values ? values->ptr : nullptr; }
   const uint64_t* valid_words() const { return validity ? validity->as<uint64_t>() : nullptr; }
 };
@@ -151,6 +161,13 @@ ColumnPtr make_column(int dtype, int64_t len, bool with_validity);
 ColumnPtr column_from_host(int dtype, const void* values, const uint8_t* validity, int64_t bit_offset, int64_t len);
 int64_t column_null_count(const ColumnPtr& c);
 void column_to_host(const ColumnPtr& c, void* values_out, uint8_t* validity_out, int32_t* has_validity);
+// the download of a column from its host mirror: the same bytes, no device call (the column must have one)
+void column_to_host_mirrored(const Column& c, void* values_out, uint8_t* validity_out, int32_t* has_validity);
+// 1 when the last column_to_host / plx_frame_to_host of this thread was served from host mirrors, else 0
+int last_download_mirrored();
+void set_last_download_mirrored(int v);
+// for every function that writes into the buffers of a column it did not create: the mirror no longer describes them
+inline void drop_host_mirror(Column& c) { c.host.reset(); }
 
 // handle tables
 plx_column register_column(ColumnPtr c);

@@ -16,6 +16,7 @@
 #include "distinct.hpp"
 #include "encoded_inputs.hpp"
 #include "fused_shapes.hpp"
+#include "groupby_tail.hpp"
 #include "jit.hpp"
 #include "join.hpp"
 #include "kernels.hpp"
@@ -1480,13 +1481,22 @@ static ScanProgram scan_program_with_encodings(const Compiler& c, bool may_build
 
 // ---- the fused group-by driver: run_fused_groupby chooses the route, each route is one function that says whether it produced the result ----
 namespace {
+// What a route needs to finish the RESULT itself -- the output columns, not only the cells: the finalisation of every aggregate (the key parts are in the KeyPlan) --
+// and the columns it hands back when it did (`taken`).  Only lds_table looks at it (groupby_tail_finish below).
+struct TailRequest {
+  const std::vector<FinalSpec>& specs;
+  std::vector<ColumnPtr> key_cols, agg_cols;      // one per key part / per spec, `res.n_groups` rows each, host mirrors attached
+  bool taken = false;
+};
 // what the routes of one run share
 struct GroupByRun {
   Compiler& c; const KeyPlan& kp; const Shape& sh; const Args& args;      // (sh, args: c.shape, c.args)
   const int len_idx, static_id;
   const bool may_partition;      // the plan allows the partitioned routes and the input is large enough for them to pay
   FusedAggResult& res; std::string& desc;
+  TailRequest* tail = nullptr;   // null: the route leaves cells and packed keys in `res` and the caller finalises them
 };
+bool groupby_tail_finish(GroupByRun& q, const Buf& cells, int G, const Buf& oob);
 // "fused_scan[<mode>]+": how the scan program in front of a sink was obtained
 std::string scan_tag(int static_id, int64_t n_rows) { return std::string("fused_scan[") + jit::program_mode(static_id, n_rows) + "]+"; }
 
@@ -1542,6 +1552,7 @@ void lds_table(GroupByRun& q) {
   const CellPlan cell_plan = shared_cells_plan(q);
   k::fused_lds_agg(q.sh, q.args, G, q.static_id, cells->as<uint64_t>(), oob ? oob->as<unsigned int>() : nullptr, &cell_plan);
   q.desc += scan_tag(q.static_id, q.args.n_rows) + "lds_table(G=" + std::to_string(G) + ",copies=" + std::to_string(k::lds_agg_copies(G, q.sh.n_aggs)) + ")";
+  if (q.tail && groupby_tail_finish(q, cells, G, oob)) return;
   finish_table(q, cells, G, oob);
 }
 void dense_hbm_table(GroupByRun& q) {
@@ -1725,17 +1736,17 @@ void hash_hbm_table(GroupByRun& q, int log2_cap) {
 }  // namespace
 
 static bool lds_table_route(const KeyPlan& kp, const Shape& sh) { return kp.packed && kp.total_bits <= 12 && k::lds_agg_copies(1 << kp.total_bits, sh.n_aggs) > 0; }
-static void run_fused_groupby(Compiler& c, const KeyPlan& kp, int len_idx, FusedAggResult& res, std::string& desc, std::string& encoded) {
+static void run_fused_groupby(Compiler& c, const KeyPlan& kp, int len_idx, FusedAggResult& res, std::string& desc, std::string& encoded, TailRequest* tail = nullptr) {
   const Shape& sh = c.shape;
   const int64_t n = c.args.n_rows;
   res.n_aggs = sh.n_aggs;
   if (n == 0) { res.n_groups = 0; res.acc = dev_alloc(8); res.packed_keys = dev_alloc(8); return; }
-  GroupByRun q{c, kp, sh, c.args, len_idx, find_static_shape(sh), !(c.plan.flags & PLX_PLAN_NO_PARTITION) && n >= ((int64_t)1 << 24), res, desc};
+  GroupByRun q{c, kp, sh, c.args, len_idx, find_static_shape(sh), !(c.plan.flags & PLX_PLAN_NO_PARTITION) && n >= ((int64_t)1 << 24), res, desc, tail};
   if (lds_table_route(kp, sh)) {
     // the route is chosen on the plain program; this one may read encoded inputs (every other route keeps the plain program and its record packing)
     const ScanProgram sp = scan_program_with_encodings(c, true);
     if (sp.note.empty()) return lds_table(q);
-    GroupByRun qe{c, kp, sp.shape, sp.args, len_idx, sp.static_id, q.may_partition, res, desc};
+    GroupByRun qe{c, kp, sp.shape, sp.args, len_idx, sp.static_id, q.may_partition, res, desc, tail};
     lds_table(qe);
     encoded += sp.note + "; ";      // (beside the plan text, not in it: Plan::encoded)
     return;
@@ -1749,15 +1760,21 @@ static void run_fused_groupby(Compiler& c, const KeyPlan& kp, int len_idx, Fused
 
 // Output columns are allocated here and filled by ONE finalize_batch launch per query
 // (was one launch per key and per aggregate: ~10 launches + 2 popcount syncs for TPC-H Q1).
+// which finalisations can produce a null (a group none of whose rows counted), and the spec as the kernels take it
+static bool final_nullable(const FinalSpec& fs) { return fs.kind == FIN_MEAN || fs.kind == FIN_MINMAX_I || fs.kind == FIN_MINMAX_F || fs.kind == FIN_VAR || fs.kind == FIN_STD; }
+static FinalSpec final_job_spec(const FinalSpec& fs) {
+  FinalSpec f = fs;
+  if (fs.kind == FIN_COPY64 && dtype_width(fs.out_dtype) < 4) f.kind = FIN_NARROW;
+  return f;
+}
 static ColumnPtr finalize_column(const FusedAggResult& r, const FinalSpec& fs, FinBatch& batch) {
   const int64_t G = r.n_groups;
   auto out = std::make_shared<Column>();
   out->dtype = fs.out_dtype; out->len = G;
   out->values = dev_alloc(values_bytes(fs.out_dtype, G));
-  const bool nullable = fs.kind == FIN_MEAN || fs.kind == FIN_MINMAX_I || fs.kind == FIN_MINMAX_F || fs.kind == FIN_VAR || fs.kind == FIN_STD;
+  const bool nullable = final_nullable(fs);
   if (nullable) out->validity = dev_alloc_zero(bitmap_bytes(G)); else out->null_count = 0;
-  FinalSpec f = fs;
-  if (fs.kind == FIN_COPY64 && dtype_width(fs.out_dtype) < 4) f.kind = FIN_NARROW;
+  const FinalSpec f = final_job_spec(fs);
   PLX_REQUIRE(batch.n < kMaxFinJobs, PLX_ERR_UNSUPPORTED, "too many output columns in one fused aggregation");
   FinJob& j = batch.jobs[batch.n++];
   j = FinJob{};
@@ -1766,16 +1783,20 @@ static ColumnPtr finalize_column(const FusedAggResult& r, const FinalSpec& fs, F
 }
 // The end of every fused aggregation: a column per aggregate of `r`, the ONE finalize_batch launch of the result set (the caller has put its key columns into `batch`
 // already; no groups: no launch), then the output expressions over those columns, appended to `frame`.
+// the output expressions over the finalised aggregate columns (`overrides`: aggregate node -> its column of n_groups rows), appended to `frame`
+static void append_output_expressions(const Plan& plan, const std::map<int, ColumnPtr>& overrides, const std::vector<int>& out_exprs, int64_t n_groups, Frame& frame) {
+  Frame groups; groups.height = n_groups;
+  for (int e : out_exprs) {
+    Evaluated ev = eval(plan, e, groups, &overrides);
+    frame.names.push_back(output_name(plan, e));
+    frame.cols.push_back(broadcast(ev, n_groups));      // (a column of n_groups rows already, unless the expression is a scalar)
+  }
+}
 static void append_aggregate_columns(const Plan& plan, const FusedAggResult& r, const std::vector<int>& agg_nodes, const std::vector<FinalSpec>& specs, const std::vector<int>& out_exprs, FinBatch& batch, Frame& frame) {
   std::map<int, ColumnPtr> overrides;
   for (size_t i = 0; i < agg_nodes.size(); i++) overrides[agg_nodes[i]] = finalize_column(r, specs[i], batch);
   k::finalize_batch(r.acc->as<uint64_t>(), r.n_aggs, r.n_groups, batch);
-  Frame groups; groups.height = r.n_groups;
-  for (int e : out_exprs) {
-    Evaluated ev = eval(plan, e, groups, &overrides);
-    frame.names.push_back(output_name(plan, e));
-    frame.cols.push_back(broadcast(ev, r.n_groups));      // (a column of r.n_groups rows already, unless the expression is a scalar)
-  }
+  append_output_expressions(plan, overrides, out_exprs, r.n_groups, frame);
 }
 
 static ColumnPtr decode_key_column(const FusedAggResult& r, const KeyPart& part, int key_index, FinBatch& batch) {
@@ -1799,6 +1820,85 @@ static ColumnPtr decode_key_column(const FusedAggResult& r, const KeyPart& part,
   }
   return out;
 }
+
+// ---- the tail of the LDS-table route in one kernel, one copy and one sync (k::groupby_tail, groupby_tail.hpp; DESIGN.md 4.11 "One tail kernel") ----
+static thread_local int t_last_groupby_tail = 0;
+int last_groupby_tail() { return t_last_groupby_tail; }
+namespace {
+// an output column of the tail: `rows` rows of capacity, nothing zeroed (the kernel writes every validity word it owns), and its job
+ColumnPtr tail_column(int dtype, bool nullable, int64_t rows, FinJob& j) {
+  auto out = std::make_shared<Column>();
+  out->dtype = dtype; out->len = rows;
+  out->values = dev_alloc(values_bytes(dtype, rows));
+  if (nullable) out->validity = dev_alloc(bitmap_bytes(rows)); else out->null_count = 0;
+  j = FinJob{};
+  j.out = out->values->ptr; j.out_valid = nullable ? out->validity->as<uint64_t>() : nullptr;
+  return out;
+}
+// The cells [G][n_aggs] of an LDS-table scan are enqueued: compact, decode the keys, finalise the aggregates and fetch the result.  false: not taken (nothing was
+// launched) and the caller finishes the old way.  Raises what check_oob_flag raises, from the same place.
+bool groupby_tail_finish(GroupByRun& q, const Buf& cells, int G, const Buf& oob) {
+  TailRequest& t = *q.tail;
+  const size_t n_cols = q.kp.parts.size() + t.specs.size();
+  if (!k::groupby_tail_knob() || n_cols == 0 || n_cols > (size_t)kMaxFinJobs || G > gbt::kTailMaxSlots || !pinned_bounce()) return false;
+  int32_t dtypes[kMaxFinJobs]; uint8_t nullable[kMaxFinJobs];
+  int n = 0;
+  for (const KeyPart& part : q.kp.parts) { dtypes[n] = part.dtype; nullable[n++] = part.nullable ? 1 : 0; }
+  for (const FinalSpec& fs : t.specs) { dtypes[n] = fs.out_dtype; nullable[n++] = final_nullable(fs) ? 1 : 0; }
+  gbt::TailLayout L;
+  gbt::tail_layout(&L, G, dtypes, nullable, n);
+  if (!gbt::tail_block_fits(L, kBounceBytes)) return false;
+  // 1. the output columns at capacity G (pool allocations, no GPU work)
+  FinBatch batch{};
+  std::vector<ColumnPtr> cols;
+  for (const KeyPart& part : q.kp.parts) {
+    FinJob& j = batch.jobs[batch.n++];
+    cols.push_back(tail_column(part.dtype, part.nullable, G, j));
+    j.is_key = 1; j.kd = part.dec;
+    if (part.dtype == PLX_F32) j.kd.dtype = PLX_F32;
+  }
+  for (const FinalSpec& fs : t.specs) {
+    FinJob& j = batch.jobs[batch.n++];
+    cols.push_back(tail_column(fs.out_dtype, final_nullable(fs), G, j));
+    j.is_key = 0; j.fs = final_job_spec(fs);
+  }
+  // 2. behind the scan (and partials_finish_kernel): the tail kernel
+  Buf block = dev_alloc(L.total);
+  k::groupby_tail(cells->as<uint64_t>(), q.sh.n_aggs, G, q.len_idx, oob ? oob->as<unsigned int>() : nullptr, batch, block->ptr);
+  // 3. one copy into the page-locked bounce buffer, one sync; the bytes are the mirror
+  auto bytes = std::make_shared<std::vector<uint8_t>>(L.total);
+  {
+    std::lock_guard<std::mutex> lk(bounce_mutex());
+    PLX_HIP(hipMemcpyAsync(pinned_bounce(), block->ptr, L.total, hipMemcpyDeviceToHost, stream()));
+    PLX_HIP(hipStreamSynchronize(stream()));
+    memcpy(bytes->data(), pinned_bounce(), L.total);
+  }
+  gbt::TailHeader h;
+  memcpy(&h, bytes->data(), sizeof h);
+  PLX_REQUIRE(h.version == gbt::kTailLayoutVersion && h.n_groups <= (uint32_t)G, PLX_ERR_INVALID, "group-by tail: the result block has no valid header");
+  if (h.oob) fail(PLX_ERR_INVALID, "group key outside the bounds declared or assumed for its column");
+  const int64_t g = h.n_groups;
+  for (int j = 0; j < n; j++) {
+    Column& c = *cols[j];
+    c.len = g;
+    auto m = std::make_shared<HostMirror>();
+    m->bytes = bytes; m->values_off = L.values_off[j]; m->values_bytes = L.values_bytes[j];
+    if (c.validity) {
+      m->valid_off = L.valid_off[j]; m->valid_bytes = (size_t)L.words * 8;
+      int64_t valid = 0;
+      for (uint32_t w = 0; w < L.words; w++) { uint64_t x; memcpy(&x, bytes->data() + m->valid_off + (size_t)w * 8, 8); valid += (int64_t)gbt::tail_popc64(x); }
+      c.null_count = g - valid;
+    }
+    c.host = std::move(m);
+  }
+  q.res.n_groups = g; q.res.n_aggs = q.sh.n_aggs; q.res.acc = cells;      // (the cells stay uncompacted: nobody reads them after the tail)
+  t.key_cols.assign(cols.begin(), cols.begin() + (ptrdiff_t)q.kp.parts.size());
+  t.agg_cols.assign(cols.begin() + (ptrdiff_t)q.kp.parts.size(), cols.end());
+  t.taken = true;
+  t_last_groupby_tail = 1;
+  return true;
+}
+}  // namespace
 
 // order groups by first occurrence (maintain_order): host argsort of the FIRST_ROW cells
 static ColumnPtr first_row_permutation(const FusedAggResult& r, int first_idx) {
@@ -1977,8 +2077,11 @@ static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& p
   if (sid_out) *sid_out = find_static_shape(c.shape);
   FusedAggResult r;
   std::string d;
+  // the LDS-table route may finish the result itself (groupby_tail_finish) -- not under maintain_order, whose permutation reads compacted cells
+  TailRequest tail{specs};
+  t_last_groupby_tail = 0;
   try {
-    run_fused_groupby(c, kp, len_idx, r, d, plan.encoded);
+    run_fused_groupby(c, kp, len_idx, r, d, plan.encoded, node.maintain_order ? nullptr : &tail);
   } catch (const Error& e) {
     // a row outside bounds the planner had only ASSUMED (assume_range): forget the guesses, never guess about these columns again, and run the query once more --
     // its statistics now come from exact passes.  (Bounds the caller declared are the caller's promise: that error stands.)
@@ -1989,6 +2092,13 @@ static bool fused_groupby(Plan& plan, const IRN& node, const std::vector<int>& p
   plan.desc += kp.note + c.var_note + "FusedFilterGroupBy{" + d + ", inputs=" + std::to_string(c.shape.n_inputs) + ", ops=" + std::to_string(c.shape.n_ops) + ", aggs=" + std::to_string(c.shape.n_aggs) + ", groups=" + std::to_string(r.n_groups) + "}; ";
   out = std::make_shared<Frame>();
   out->height = r.n_groups;
+  if (tail.taken) {
+    for (size_t pi = 0; pi < kp.parts.size(); pi++) { out->names.push_back(output_name(plan, kp.parts[pi].expr)); out->cols.push_back(tail.key_cols[pi]); }
+    std::map<int, ColumnPtr> overrides;
+    for (size_t i = 0; i < agg_nodes.size(); i++) overrides[agg_nodes[i]] = tail.agg_cols[i];
+    append_output_expressions(plan, overrides, node.exprs, r.n_groups, *out);
+    return true;
+  }
   FinBatch batch{};
   for (size_t pi = 0; pi < kp.parts.size(); pi++) { out->names.push_back(output_name(plan, kp.parts[pi].expr)); out->cols.push_back(decode_key_column(r, kp.parts[pi], (int)pi, batch)); }
   append_aggregate_columns(plan, r, agg_nodes, specs, node.exprs, batch, *out);

@@ -87,6 +87,8 @@ bool describe_filter_fusion(Plan& plan, int root, fused::Shape* shape, std::stri
 // f64 columns of at least min_rows rows may get a decimal shadow (encoded_inputs.hpp; default 2^22, PLX_ENCODED_DECIMAL_MIN_ROWS); negative counts as 0
 void encoded_set_decimal_min_rows(int64_t min_rows);
 int64_t encoded_decimal_min_rows();
+// 1 when the calling thread's last fused group-by finished through the tail kernel (k::groupby_tail), else 0
+int last_groupby_tail();
 
 }  // namespace engine
 }  // namespace plx

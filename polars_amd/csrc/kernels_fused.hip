@@ -34,6 +34,7 @@
 //     wide_load, wide_tiles_choice below) and finish the last < 512 rows per 128-row tile.
 #include "fused_sinks.hpp"
 #include "fused_cells.hpp"
+#include "groupby_tail.hpp"
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
 #include "variance.hpp"
@@ -960,6 +961,100 @@ void finalize_batch(const uint64_t* acc, int n_aggs, int64_t G, const FinBatch& 
   hipLaunchKernelGGL(finalize_batch_kernel, dim3(grid_for(G, kBlock)), dim3(kBlock), 0, stream(), (const unsigned long long*)acc, n_aggs, G, b);
   PLX_HIP(hipGetLastError());
 }
+// ---- the tail of an LDS-table group-by: compaction + finalisation + the result block, one workgroup (groupby_tail.hpp; DESIGN.md 4.11 "One tail kernel") ------------------------
+// acc[G][n_aggs] complete cells; slot s is a group iff its len_idx cell is non-zero, and its output row is its rank among the occupied slots in ascending slot
+// order: a ballot per 64 slots, a prefix over the <= 64 ballot words in LDS -- no counter, no atomics.  slot_of[rank] then stands where the compacted packed keys
+// stood for finalize_batch_kernel, and the loop over RANK words below is that kernel's: the same decode_one / finalize_one, the same ballots written as whole words.
+// Every element is written twice, to the column (b.jobs[j].out) and to the block; the block's header carries n_groups and the sink's out-of-bounds flag.
+// Bounds: s < G <= kTailMaxSlots, rank < n_groups <= G, w < words = ceil(G / 64); the columns hold G rows, their bitmaps bitmap_bytes(G) = 8 * words + 8 bytes.
+static_assert(gbt::kTailMaxCols == kMaxFinJobs, "the layout holds a piece per finalize job");
+__global__ __launch_bounds__(kBlock) void groupby_tail_kernel(const unsigned long long* __restrict__ acc, int n_aggs, int G, int len_idx,
+                                                              const unsigned int* __restrict__ oob, FinBatch b, unsigned char* __restrict__ block) {
+  __shared__ unsigned long long slot_of[gbt::kTailMaxSlots];
+  __shared__ uint64_t occ[gbt::kTailMaxWords];
+  __shared__ uint32_t base[gbt::kTailMaxWords];
+  __shared__ gbt::TailLayout L;
+  __shared__ int32_t dts[kMaxFinJobs];
+  __shared__ uint8_t nul[kMaxFinJobs];
+  __shared__ uint32_t n_sh;
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  const uint32_t words = ((uint32_t)G + 63u) >> 6;
+  for (uint32_t w = wave; w < words; w += kBlock / 64) {
+    const uint32_t s = w * 64 + lane;
+    const uint64_t m = ballot(s < (uint32_t)G && acc[(size_t)s * n_aggs + len_idx] != 0);
+    if (lane == 0) occ[w] = m;
+  }
+  if ((int)threadIdx.x < b.n) {
+    const FinJob& job = b.jobs[threadIdx.x];
+    dts[threadIdx.x] = job.is_key ? (int32_t)job.kd.dtype : (int32_t)job.fs.out_dtype;
+    nul[threadIdx.x] = job.out_valid ? 1 : 0;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) n_sh = gbt::tail_rank_bases(occ, words, base);
+  if (threadIdx.x == 64) gbt::tail_layout(&L, G, dts, nul, b.n);
+  __syncthreads();
+  const uint32_t n = n_sh;
+  for (uint32_t w = wave; w < words; w += kBlock / 64) {
+    const uint32_t s = w * 64 + lane;
+    if ((occ[w] >> lane) & 1) slot_of[gbt::tail_rank_of(occ, base, s)] = s;
+  }
+  __syncthreads();
+  // a wave takes (rank word, job) pairs, not whole words: a small result (Q1: one word, ten jobs) is a chain of dependent cell loads per job, and the four waves
+  // walk a quarter of it each
+  const uint32_t n_jobs = (uint32_t)b.n;
+  for (uint32_t t = wave; t < words * n_jobs; t += kBlock / 64) {
+    const uint32_t w = t / n_jobs, g = w * 64 + lane;
+    {
+      const int j = (int)(t - w * n_jobs);   // wave-uniform (kernel arguments)
+      const FinJob& job = b.jobs[j];
+      void* copy = block + L.values_off[j];
+      bool valid = false, bit = false;
+      if (g < n) {
+        if (job.is_key) {
+          valid = decode_one(slot_of, nullptr, job.kd, job.out, g, bit);
+          decode_one(slot_of, nullptr, job.kd, copy, g, bit);
+        } else {
+          const unsigned long long* cell = acc + (size_t)slot_of[g] * n_aggs;
+          valid = finalize_one(cell, job.fs, job.out, g);
+          finalize_one(cell, job.fs, copy, g);
+        }
+      }
+      if (job.is_key && job.kd.dtype == PLX_BOOL) {
+        const uint64_t bb = gbt::tail_rank_word(ballot(bit), w, n);
+        if (lane == 0) { reinterpret_cast<uint64_t*>(job.out)[w] = bb; reinterpret_cast<uint64_t*>(copy)[w] = bb; }
+      }
+      if (job.out_valid) {
+        const uint64_t m = gbt::tail_rank_word(ballot(valid), w, n);
+        if (lane == 0) { job.out_valid[w] = m; reinterpret_cast<uint64_t*>(block + L.valid_off[j])[w] = m; }
+      }
+    }
+  }
+  // the padding word behind every bitmap of a column (bitmap_bytes), so that whole-word readers past the last row see zeros as they do after a zeroed allocation
+  if ((int)threadIdx.x < b.n) {
+    const FinJob& job = b.jobs[threadIdx.x];
+    if (job.is_key && job.kd.dtype == PLX_BOOL) reinterpret_cast<uint64_t*>(job.out)[words] = 0;
+    if (job.out_valid) job.out_valid[words] = 0;
+  }
+  if (threadIdx.x == 0) {
+    gbt::TailHeader* h = reinterpret_cast<gbt::TailHeader*>(block);
+    h->n_groups = n; h->oob = oob ? *oob : 0u; h->version = gbt::kTailLayoutVersion; h->zero = 0;
+  }
+}
+void groupby_tail(const uint64_t* acc, int n_aggs, int G, int len_idx, const unsigned int* oob, const FinBatch& b, void* block) {
+  PLX_REQUIRE(G >= 1 && G <= gbt::kTailMaxSlots && b.n >= 1 && b.n <= kMaxFinJobs && len_idx >= 0 && len_idx < n_aggs, PLX_ERR_INVALID, "groupby_tail: arguments out of range");
+  ProfileScope ps("groupby_tail", (uint64_t)G * 8 * (uint64_t)n_aggs, (uint64_t)G);
+  hipLaunchKernelGGL(groupby_tail_kernel, dim3(1), dim3(kBlock), 0, stream(), (const unsigned long long*)acc, n_aggs, G, len_idx, oob, b, (unsigned char*)block);
+  PLX_HIP(hipGetLastError());
+}
+// PLX_GROUPBY_TAIL=0 (read once) keeps the compaction, finalisation and download of the LDS-table route as separate steps: measurement runs and the tests
+static std::atomic<int> g_groupby_tail{-1};
+bool groupby_tail_knob() {
+  int v = g_groupby_tail.load(std::memory_order_relaxed);
+  if (v < 0) { const char* e = getenv("PLX_GROUPBY_TAIL"); v = (e && e[0] == '0') ? 0 : 1; g_groupby_tail.store(v, std::memory_order_relaxed); }
+  return v != 0;
+}
+void set_groupby_tail(bool on) { g_groupby_tail.store(on ? 1 : 0, std::memory_order_relaxed); }
+
 void finalize_aggs(const uint64_t* acc, int n_aggs, int64_t G, const FinalSpec& sp, void* out, uint64_t* out_valid) {
   if (G == 0) return;
   hipLaunchKernelGGL(finalize_kernel, dim3(grid_for(G, kBlock)), dim3(kBlock), 0, stream(), (const unsigned long long*)acc, n_aggs, G, sp, out, out_valid);

@@ -130,6 +130,13 @@ double sample_sortedness(const ColumnPtr& c);
 bool sample_minmax(const ColumnPtr& c, int64_t* mn, int64_t* mx, int blocks = 64);
 // all jobs of a batch (key decodes + aggregate finalisations) in one launch
 void finalize_batch(const uint64_t* acc, int n_aggs, int64_t G, const fused::FinBatch& b);
+// the tail of an LDS-table group-by in ONE launch of one workgroup (groupby_tail.hpp): acc[G][n_aggs] complete cells, 1 <= G <= gbt::kTailMaxSlots; slots whose
+// len_idx cell is non-zero are the groups, in ascending slot order; every job of `b` (packed / kvalid unused: the packed key of a group is its slot) is decoded or
+// finalised into its column, which holds G rows, and into `block` (gbt::tail_layout), whose header receives the group count and *oob (oob may be null).  No sync.
+void groupby_tail(const uint64_t* acc, int n_aggs, int G, int len_idx, const unsigned int* oob, const fused::FinBatch& b, void* block);
+// the switch behind PLX_GROUPBY_TAIL (default on)
+bool groupby_tail_knob();
+void set_groupby_tail(bool on);
 // packed group keys -> one key column
 void decode_key(const uint64_t* packed, const uint8_t* kvalid, int64_t G, const fused::KeyDecode& kd, void* out, uint64_t* out_valid);
 

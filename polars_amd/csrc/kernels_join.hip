@@ -151,6 +151,7 @@ void null_out_no_row(ColumnPtr& idx) {
   if (!idx->len) return;
   plx_scalar s; s.u = kNoRow;
   ColumnPtr ok = ops::cmp_scalar(PLX_NE, idx, s);
+  drop_host_mirror(*idx);
   idx->validity = ok->values; idx->null_count = -1;
   if (column_null_count(idx) == 0) { idx->validity = nullptr; idx->null_count = 0; }
 }

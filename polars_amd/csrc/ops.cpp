@@ -386,7 +386,7 @@ ColumnPtr fill_null(const ColumnPtr& c, plx_scalar v) {
   if (!c->validity || column_null_count(c) == 0) {
     if (!c->validity) return c;
     auto same = std::make_shared<Column>(*c);
-    same->validity = nullptr; same->null_count = 0;
+    same->validity = nullptr; same->null_count = 0; same->host.reset();
     return same;
   }
   auto out = std::make_shared<Column>();

@@ -40,5 +40,6 @@ for name, lf in (("q1", queries.q1(df.lazy())), ("q1_sorted", queries.q1_sorted(
     st = bench.kernel_stats(pl)
     F.lib().plx_profile_enable(0)
     print(f"{name}: lowered_c {acc[0]/K*1e6:.1f} us | plx_execute_plan {acc[1]/K*1e6:.1f} us | wrap frame {acc[2]/K*1e6:.1f} us | to_dict {acc[3]/K*1e6:.1f} us | total {sum(acc)/K*1e6:.1f} us")
+    print(f"   last_groupby_tail {F.last_groupby_tail()}  last_download_mirrored {F.last_download_mirrored()}")
     for k, v in sorted(st.items(), key=lambda kv: -kv[1][1]):
         print(f"   {k:32s} x{v[0]/K:.1f}  {v[1]/v[0]:.1f} us")
