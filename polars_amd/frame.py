@@ -356,6 +356,7 @@ class Series:
     def arg_sort(self, *, descending: bool = False, nulls_last: bool = False, limit: int = -1) -> "Series":
         """Stable arg-sort (Series.arg_sort); limit >= 0 keeps the first `limit` indices (top-k selection)."""
         F.ensure_init()
+        F.set_plan_note(None)
         h = C.c_uint64()
         by = (C.c_uint64 * 1)(self._h)
         d, nl = (C.c_uint8 * 1)(int(descending)), (C.c_uint8 * 1)(int(nulls_last))
@@ -653,6 +654,7 @@ def logical_arrow(arr, dtype: T.DataType):
 def arg_sort_by(by: Sequence["Series"], descending=False, nulls_last=False, limit: int = -1) -> "Series":
     """pl.arg_sort_by over device columns: stable multi-key arg-sort through plx_sort_indices (limit >= 0: top-k)."""
     F.ensure_init()
+    F.set_plan_note(None)
     n = len(by)
     d, nl = _per_key(descending, n, "descending", "exprs"), _per_key(nulls_last, n, "nulls_last", "exprs")
     h = C.c_uint64()
