@@ -45,6 +45,8 @@
  *   plx_join_indices
  *       crates/polars-ops/src/frame/join/hash_join/single_keys_dispatch.rs:234-357
  *       (hash_join_inner / hash_join_left -> (left_idx, right_idx))
+ *   plx_join_asof_indices / PLX_IR_JOIN_ASOF
+ *       crates/polars-ops/src/frame/join/asof/{mod.rs, default.rs, groups.rs} (join_asof, join_asof_by; AsofStrategy, the backward / forward / nearest scans)
  *   plx_hash_partition
  *       crates/polars-utils/src/hashing.rs:72-121 (HashPartitioner) and
  *       crates/polars-expr/src/hash_keys.rs:263-314 (gen_idxs_per_partition)
@@ -203,6 +205,11 @@ typedef enum plx_quantile_interpolation {
  * right row appears, the left index is nullable.  (The reference tree was not at hand when FULL and RIGHT were added: their contract here and at plx_ir.coalesce /
  * plx_join_order is the maintainers' reading of polars >= 1.0 and is what the tests pin.) */
 typedef enum plx_join_how { PLX_JOIN_INNER = 0, PLX_JOIN_LEFT = 1, PLX_JOIN_SEMI = 2, PLX_JOIN_ANTI = 3, PLX_JOIN_FULL = 4, PLX_JOIN_RIGHT = 5 } plx_join_how;
+
+/* As-of joins (plx_join_asof_indices, PLX_IR_JOIN_ASOF): which candidate a left row takes.  OR PLX_ASOF_STRICT into the strategy for allow_exact_matches = false:
+ * every comparison becomes strict, for NEAREST as well.  The contract is stated at plx_join_asof_indices. */
+typedef enum plx_asof_strategy { PLX_ASOF_BACKWARD = 0, PLX_ASOF_FORWARD = 1, PLX_ASOF_NEAREST = 2 } plx_asof_strategy;
+#define PLX_ASOF_STRICT 4
 
 /* A 64-bit scalar passed by bit pattern; interpreted according to a plx_dtype. */
 typedef union plx_scalar {
@@ -453,6 +460,29 @@ int plx_distinct_mask(const plx_column* keys, int32_t n_keys, int32_t keep, plx_
 int plx_join_indices(plx_join_how how, plx_column left_key, plx_column right_key,
                      plx_column* out_left_idx, plx_column* out_right_idx);
 
+/* As-of join -> one right row index (or null) per left row, in left row order (*out_right_idx: PLX_U32, len(left_on) rows, a validity bitmap only when some row
+ * is unmatched).  The reference tree was not at hand: this contract is the maintainers' reading of py-polars join_asof and polars-ops/src/frame/join/asof/, and
+ * is what the tests pin.
+ *   strategy_and_flags   a plx_asof_strategy, OR'd with PLX_ASOF_STRICT for allow_exact_matches = false; anything else is PLX_ERR_INVALID.
+ *   groups     the candidates of a left row are the right rows whose n_by (0..7: more is PLX_ERR_UNSUPPORTED) `by` parts all equal the left row's, by the sort's
+ *              equality (NaN == NaN, -0 == +0).  A null in any by part, or a null `on`, on either side makes that row match nothing; a left row whose group has
+ *              no right row gets null.  by parts: integer, float or Boolean columns, part j of one dtype on both sides.
+ *   order      the candidates of a group are taken in (on, right row) order.  Neither side needs to be sorted: the usable right rows are checked for order in
+ *              one pass and sorted (stable, by parts then on) only when that fails; left rows are searched independently.
+ *   backward   the last candidate with on_r <= on_l;  forward: the first candidate with on_r >= on_l;  nearest: the candidate at the smallest distance, among
+ *              several at that distance the LAST in candidate order -- an equidistant pair goes to the forward value, a duplicated forward value to its last
+ *              row, an exact match to the last of its duplicates.  PLX_ASOF_STRICT makes every comparison strict (nearest then skips exact matches).
+ *   tolerance  NULL, or the largest distance a match may have: read as .u for an integer `on` (Date / Datetime: in the column's own unit), as .f64 (>= 0, not
+ *              NaN: PLX_ERR_INVALID) for a float `on`.  The match found without the tolerance is kept only if its distance is at most the tolerance; there is
+ *              no fallback to another candidate.  Integer distances are exact in 64 unsigned bits (Int64 min against max is 2^64 - 1, not an overflow);
+ *              float distances are |a - b| in f64, equal values (NaN against NaN, inf against inf) are distance 0, a NaN distance is within no tolerance
+ *              and loses against any number under nearest.
+ *   on         any integer dtype, PLX_F32 or PLX_F64, the same dtype on both sides (PLX_BOOL: PLX_ERR_UNSUPPORTED).
+ * plx_last_plan_description(): "asof[backward, by=2, right=in order, rows=N x M, samples=S]", "asof[..., right=sorted: <sort>, dropped null keys=K, ...]" or
+ * "asof[empty]".  PLX_ASOF_ROUTE=global in the environment (read per call) searches without the LDS sample stage: samples=0. */
+int plx_join_asof_indices(int32_t strategy_and_flags, const plx_column* left_by, const plx_column* right_by, int32_t n_by,
+                          plx_column left_on, plx_column right_on, const plx_scalar* tolerance, plx_column* out_right_idx);
+
 /* Stable multi-key arg-sort (arg_sort_multiple; polars-core/src/chunked_array/ops/sort/arg_sort_multiple.rs,
  * SortExec polars-mem-engine/src/executors/sort.rs).  descending / nulls_last: n_by flags each, NULL = all 0.
  * nulls_last is an absolute position (not flipped by descending); floats in total order (NaN greatest,
@@ -571,9 +601,15 @@ typedef enum plx_ir_kind {
                        * otherwise (a table of row ids whose key words are compared column by column: any dtype mix, any value range). */
   PLX_IR_SORT = 6,    /* input, keys (by), sort_descending[n_keys], sort_nulls_last[n_keys] (IR::Sort; always stable) */
   PLX_IR_SLICE = 7,   /* input, slice_offset (negative: from the end), slice_len (IR::Slice); directly above a Sort it becomes top-k */
-  PLX_IR_DISTINCT = 8 /* input, keys (the subset as column expressions, 1..8: more is PLX_ERR_UNSUPPORTED), how = the plx_unique_keep (outside 0..3: PLX_ERR_INVALID at
+  PLX_IR_DISTINCT = 8, /* input, keys (the subset as column expressions, 1..8: more is PLX_ERR_UNSUPPORTED), how = the plx_unique_keep (outside 0..3: PLX_ERR_INVALID at
                        * plan import), maintain_order 0 / 1 (IR::Distinct).  The rows that are distinct over the keys, ALWAYS in the input's row order: one stable sort of
                        * the keys, a Boolean row mask, one filter of every column -- so maintain_order = 1 is honoured and 0 loses nothing. */
+  PLX_IR_JOIN_ASOF = 9 /* input, input_right, keys / keys_right (the by parts, then `on` LAST; n_keys == n_keys_right, 1..8: more is PLX_ERR_UNSUPPORTED), how = a
+                       * plx_asof_strategy OR'd with PLX_ASOF_STRICT, predicate = the arena index of a non-null, non-negative PLX_AE_LITERAL holding the tolerance in
+                       * the `on` dtype's family (an integer literal for integer / Date / Datetime, a float literal for floats) or -1, suffix and coalesce as in
+                       * PLX_IR_JOIN (the rules of a left join), maintain_order must be 0.  A bad strategy, mismatched key counts, a tolerance that is no literal or
+                       * is negative and maintain_order != 0 are PLX_ERR_INVALID at plan import.  Output: one row per left row in left order; the left columns are
+                       * the input's own (not gathered), each right column is gathered at the matched row (plx_join_asof_indices states the match). */
 } plx_ir_kind;
 
 /* Row order of a PLX_IR_JOIN's output (plx_ir.maintain_order of a join node; JoinArgs::maintain_order / MaintainOrderJoin of the reference).
@@ -612,7 +648,7 @@ typedef struct plx_ir {
   int32_t n_keys;
   const int32_t* keys_right;
   int32_t n_keys_right;
-  int32_t how; /* PLX_IR_JOIN: plx_join_how; PLX_IR_DISTINCT: plx_unique_keep */
+  int32_t how; /* PLX_IR_JOIN: plx_join_how; PLX_IR_DISTINCT: plx_unique_keep; PLX_IR_JOIN_ASOF: plx_asof_strategy | PLX_ASOF_STRICT */
   int32_t maintain_order; /* PLX_IR_GROUPBY / PLX_IR_SORT / PLX_IR_DISTINCT: 0 / 1; PLX_IR_JOIN: plx_join_order */
   const char* suffix; /* join suffix, NULL = "_right" */
   const uint8_t* sort_descending; /* PLX_IR_SORT: n_keys flags, NULL = ascending */

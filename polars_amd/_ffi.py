@@ -66,6 +66,19 @@ UNIT_DATE, UNIT_MS, UNIT_US, UNIT_NS = range(4)                          # plx_t
 (OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_PLUS, OP_MINUS, OP_MULTIPLY, OP_TRUE_DIVIDE,
  OP_FLOOR_DIVIDE, OP_MODULUS, OP_AND, OP_OR, OP_XOR) = range(15)
 IR_SCAN, IR_FILTER, IR_SELECT, IR_HSTACK, IR_GROUPBY, IR_JOIN, IR_SORT, IR_SLICE, IR_DISTINCT = range(9)
+IR_JOIN_ASOF = 9                                                          # keys / keys_right: the by parts, then `on` last; how: the strategy | ASOF_STRICT; predicate: the tolerance literal or -1
+ASOF_BACKWARD, ASOF_FORWARD, ASOF_NEAREST = range(3)                     # plx_asof_strategy
+ASOF_STRICT = 4                                                           # OR'd into the strategy: allow_exact_matches = False
+ASOF_STRATEGIES = {"backward": ASOF_BACKWARD, "forward": ASOF_FORWARD, "nearest": ASOF_NEAREST}
+ASOF_MAX_BY = 7
+ASOF_THREADS = 256                                                        # the left rows one workgroup serves per step (asof::kThreads)
+
+
+def asof_samples_for(n_words: int) -> int:
+    """asof::samples_for: the tuples of n_words 64-bit words that the 64 KiB LDS sample stage of the search holds."""
+    return (64 * 1024 // 8) // n_words if 1 <= n_words <= ASOF_MAX_BY + 1 else 0
+
+
 PLAN_NO_FUSION = 1
 PLAN_NO_DIRECT_JOIN = 2
 PLAN_NO_PARTITION = 4
@@ -238,6 +251,7 @@ SIGNATURES = {
     "plx_shift": (C.c_int, [_u64p, C.c_int32, C.c_uint64, C.c_int64, C.POINTER(Scalar), C.c_int32, _u64p]),
     "plx_rolling": (C.c_int, [_u64p, C.c_int32, C.c_uint64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _u64p]),
     "plx_join_indices": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _u64p, _u64p]),
+    "plx_join_asof_indices": (C.c_int, [C.c_int32, _u64p, _u64p, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(Scalar), _u64p]),
     "plx_datagen_lineitem_q1": (C.c_int, [C.c_int64, C.c_uint64, _u64p]),
     "plx_datagen_lineitem_q1_host": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "plx_datagen_orders_lineitem": (C.c_int, [C.c_int64, C.c_uint64, _u64p, _u64p]),

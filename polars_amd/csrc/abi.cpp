@@ -573,6 +573,21 @@ int plx_join_indices(plx_join_how how, plx_column left_key, plx_column right_key
   PLX_CATCH
 }
 
+int plx_join_asof_indices(int32_t strategy_and_flags, const plx_column* left_by, const plx_column* right_by, int32_t n_by, plx_column left_on, plx_column right_on,
+                          const plx_scalar* tolerance, plx_column* out_right_idx) {
+  PLX_TRY
+  PLX_REQUIRE(out_right_idx, PLX_ERR_INVALID, "join_asof_indices: null output");
+  PLX_REQUIRE(n_by >= 0 && (n_by == 0 || (left_by && right_by)), PLX_ERR_INVALID, "join_asof_indices: n_by must be >= 0, with both by arrays given when it is not 0");
+  PLX_REQUIRE(n_by <= 7, PLX_ERR_UNSUPPORTED, "join_asof_indices: " + std::to_string(n_by) + " by parts; an as-of join takes 0..7 by parts on this path");
+  std::vector<ColumnPtr> lby, rby;
+  for (int i = 0; i < n_by; i++) { lby.push_back(get_column(left_by[i])); rby.push_back(get_column(right_by[i])); }
+  std::string d;
+  ColumnPtr ri = asof::match(strategy_and_flags, lby, rby, get_column(left_on), get_column(right_on), tolerance, &d);
+  t_plan_desc = d;
+  *out_right_idx = register_column(ri);
+  PLX_CATCH
+}
+
 int plx_sort_indices(const plx_column* by, int32_t n_by, const uint8_t* descending, const uint8_t* nulls_last, int64_t limit, plx_column* out_idx) {
   PLX_TRY
   PLX_REQUIRE(by && n_by > 0 && out_idx, PLX_ERR_INVALID, "sort_indices: need at least one key column");

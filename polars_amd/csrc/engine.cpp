@@ -2,6 +2,8 @@
 // pipeline compiler and the executors.  See engine.hpp for the reference mapping.
 #include "engine.hpp"
 
+#include "asof.hpp"
+
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -129,6 +131,25 @@ Plan import_plan(const plx_ir* ir, int n_ir, const plx_aexpr* ae, int n_ae, uint
       PLX_REQUIRE(n.how >= PLX_JOIN_INNER && n.how <= PLX_JOIN_RIGHT, PLX_ERR_INVALID, "join: how outside 0..5 (plx_join_how)");
       n.coalesce = ir[i].coalesce;
       PLX_REQUIRE(n.coalesce >= 0 && n.coalesce <= 2, PLX_ERR_INVALID, "join: coalesce outside 0..2 (0 = the join kind's default, 1 = coalesce, 2 = keep both key columns)");
+    }
+    if (n.kind == PLX_IR_JOIN_ASOF) {
+      // everything that can be refused without a device is refused here
+      PLX_REQUIRE(asof::how_ok(n.how), PLX_ERR_INVALID, "join_asof: strategy " + std::to_string(n.how) + " in the how slot is no plx_asof_strategy (0 = backward, 1 = forward, 2 = nearest), optionally OR'd with PLX_ASOF_STRICT (4)");
+      PLX_REQUIRE(n.input >= 0 && n.input_right >= 0, PLX_ERR_INVALID, "join_asof needs two inputs");
+      PLX_REQUIRE(!n.keys.empty() && n.keys.size() == n.keys_right.size(), PLX_ERR_INVALID,
+                  "join_asof: " + std::to_string(n.keys.size()) + " left keys against " + std::to_string(n.keys_right.size()) + " right keys (the by parts, then `on`: at least one, the same number on both sides)");
+      PLX_REQUIRE((int)n.keys.size() <= asof::kMaxWords, PLX_ERR_UNSUPPORTED,
+                  "join_asof: " + std::to_string(n.keys.size()) + " keys; an as-of join takes `on` and 0.." + std::to_string(asof::kMaxBy) + " by parts on this path");
+      PLX_REQUIRE(n.maintain_order == 0, PLX_ERR_INVALID, "join_asof: maintain_order must be 0 (the result is always in left row order), got " + std::to_string(n.maintain_order));
+      n.coalesce = ir[i].coalesce;
+      PLX_REQUIRE(n.coalesce >= 0 && n.coalesce <= 2, PLX_ERR_INVALID, "join_asof: coalesce outside 0..2 (0 = the default, 1 = coalesce, 2 = keep both key columns)");
+      if (n.predicate != -1) {
+        PLX_REQUIRE(n.predicate >= 0 && n.predicate < n_ae && p.ae[n.predicate].kind == PLX_AE_LITERAL && !p.ae[n.predicate].is_null, PLX_ERR_INVALID,
+                    "join_asof: the tolerance (the predicate slot) must be the index of a non-null literal node, or -1");
+        const AE& t = p.ae[n.predicate];
+        const bool negative = dtype_is_float(t.dtype) ? !((t.dtype == PLX_F32 ? (double)t.lit.f32 : t.lit.f64) >= 0.0) : dtype_is_signed(t.dtype) && t.lit.i < 0;
+        PLX_REQUIRE(!negative, PLX_ERR_INVALID, "join_asof: the tolerance must be a number >= 0, got " + (dtype_is_float(t.dtype) ? std::to_string(t.dtype == PLX_F32 ? (double)t.lit.f32 : t.lit.f64) : std::to_string((long long)t.lit.i)));
+      }
     }
     if (n.kind == PLX_IR_DISTINCT) {
       PLX_REQUIRE(distinct::keep_ok(n.how), PLX_ERR_INVALID, "distinct: keep " + std::to_string(n.how) + " in the how slot is no plx_unique_keep (0 = any, 1 = first, 2 = last, 3 = none)");
@@ -3773,6 +3794,55 @@ static FramePtr exec_join(Plan& plan, const IRN& n) {
   return out;
 }
 
+// PLX_IR_JOIN_ASOF: the keys evaluated as exec_join does, one index column from asof::match, the frame by the column rules of a left join.  The left columns are the
+// input's own: every left row appears once, in its place.
+static FramePtr exec_join_asof(Plan& plan, const IRN& n) {
+  FramePtr left = exec_node(plan, n.input);
+  FramePtr right = exec_node(plan, n.input_right);
+  std::vector<ColumnPtr> lby, rby;
+  ColumnPtr lon, ron;
+  for (size_t j = 0; j < n.keys.size(); j++) {
+    ColumnPtr a = broadcast(eval(plan, n.keys[j], *left, nullptr), left->height);
+    ColumnPtr b = broadcast(eval(plan, n.keys_right[j], *right, nullptr), right->height);
+    if (j + 1 == n.keys.size()) { lon = a; ron = b; } else { lby.push_back(a); rby.push_back(b); }
+  }
+  flush_node_notes(plan);
+  plx_scalar tol{};
+  const plx_scalar* tolerance = nullptr;
+  if (n.predicate >= 0) {
+    const AE& t = plan.ae[n.predicate];
+    const bool on_float = asof::dtype_is_float(lon->dtype);
+    PLX_REQUIRE(on_float == dtype_is_float(t.dtype), PLX_ERR_INVALID,
+                std::string("join_asof: a ") + dtype_name(t.dtype) + " tolerance against `on` of dtype " + dtype_name(lon->dtype) + "; the tolerance is a literal of the `on` dtype's family");
+    if (on_float) tol.f64 = t.dtype == PLX_F32 ? (double)t.lit.f32 : t.lit.f64; else tol.u = t.lit.u;
+    tolerance = &tol;
+  }
+  std::string d;
+  ColumnPtr ri = asof::match(n.how, lby, rby, lon, ron, tolerance, &d);
+  const bool coalesce = n.coalesce != 2;      // plx_ir.coalesce: the default of an as-of join is a left join's
+  std::set<std::string> merged;               // the right columns of the key pairs made of two plain columns
+  for (size_t j = 0; coalesce && j < n.keys.size(); j++) {
+    const AE* lkx = plain_column(plan, n.keys[j]);
+    const AE* rkx = plain_column(plan, n.keys_right[j]);
+    if (lkx && rkx) merged.insert(rkx->name);
+  }
+  auto out = std::make_shared<Frame>();
+  out->height = left->height;
+  out->names = left->names;
+  out->cols = left->cols;
+  size_t gathered = 0;
+  for (size_t i = 0; i < right->cols.size(); i++) {
+    if (merged.count(right->names[i])) continue;
+    std::string name = right->names[i];
+    if (out->find(name) >= 0) name += n.suffix;
+    out->names.push_back(name);
+    out->cols.push_back(ops::gather(right->cols[i], ri));
+    gathered++;
+  }
+  plan.desc += "JoinAsof{" + d + ", gather x" + std::to_string(gathered) + "}; ";
+  return out;
+}
+
 // IR::Sort (+ a Slice directly above it: only the first offset+len rows of the order are produced, top-k)
 static FramePtr exec_sort(Plan& plan, const IRN& n, int64_t limit) {
   FramePtr in = exec_node(plan, n.input);
@@ -3936,6 +4006,7 @@ static FramePtr exec_node(Plan& plan, int node_id) {
     case PLX_IR_SORT: return exec_sort(plan, n, -1);
     case PLX_IR_SLICE: return exec_slice(plan, n);
     case PLX_IR_DISTINCT: return exec_distinct(plan, n);
+    case PLX_IR_JOIN_ASOF: return exec_join_asof(plan, n);
     default: fail(PLX_ERR_UNSUPPORTED, "IR node kind " + std::to_string(n.kind) + " is outside the hot path (run it on the CPU engine)");
   }
 }

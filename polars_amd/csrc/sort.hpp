@@ -136,4 +136,16 @@ ColumnPtr shift_column(const cumulative::ScanOrder& order, const Segments& segs,
 bool tile_route_for(int64_t w);
 ColumnPtr rolling_column(const cumulative::ScanOrder& order, const Segments& segs, const ColumnPtr& value, int op, const Params& p, std::string* route);
 }  // namespace rolling
+
+// ---- join_asof (kernels_asof.hip; asof.hpp holds the arithmetic and the contract) ----
+namespace asof {
+// The matched right row of every left row: PLX_U32, len(left_on) rows in left order, a validity bitmap only when some row is unmatched.  how: a plx_asof_strategy,
+// OR'd with PLX_ASOF_STRICT; left_by / right_by: 0..7 parts, part j of one dtype on both sides; tolerance: null, or .u for an integer `on`, .f64 for a float one.
+// The right rows with a null key part are compacted away, the rest checked for order and sorted (sort::sort_indices by the parts then `on`) only when that fails;
+// then one encode launch and one search launch.  Empty sides launch nothing.  *desc = "asof[backward, by=2, right=in order, rows=N x M, samples=S]" |
+// "asof[..., right=sorted: <sort description>, dropped null keys=K, ...]" | "asof[empty]"; PLX_ASOF_ROUTE=global in the environment (read per call) searches
+// without the LDS sample stage: samples=0.
+ColumnPtr match(int how, const std::vector<ColumnPtr>& left_by, const std::vector<ColumnPtr>& right_by, const ColumnPtr& left_on, const ColumnPtr& right_on, const plx_scalar* tolerance,
+                std::string* desc);
+}  // namespace asof
 }  // namespace plx

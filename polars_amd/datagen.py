@@ -420,3 +420,14 @@ def frame_from_torch(pl, cols, names):
     """Wrap device tensors as a DataFrame without copying (plx_column_from_device)."""
     lt = logical_dtypes(pl)
     return pl.DataFrame([pl.Series.from_torch(n, cols[n], dtype=lt.get(n)) for n in names])
+
+
+def trades_quotes_native(pl, n_trades: int, n_quotes: int, seed: int = 10, n_syms: int = 100, span_us: int = 60_000_000):
+    """(trades, quotes) for queries.quote_before_trade from the library's generator, on the device: sym Int32 in [0, n_syms), ts Datetime("us") uniform over
+    `span_us` microseconds from 2024-01-01, price Float64 in [90, 110).  Rows come in no order on either side."""
+    t0 = us(2024, 1, 1)
+    def side(n, stream):
+        return pl.DataFrame([uniform_native(pl, "sym", pl.Int64, n, seed, stream, 0, n_syms).cast(pl.Int32).rename("sym"),
+                             uniform_native(pl, "ts", pl.Datetime, n, seed, stream + 1, t0, t0 + span_us),
+                             uniform_native(pl, "price", pl.Float64, n, seed, stream + 2, 9000, 11000, 0.01)])
+    return side(n_trades, 0), side(n_quotes, 3)          # (the generator's streams: 0..7)

@@ -871,6 +871,14 @@ class DataFrame:
              coalesce: Optional[bool] = None) -> "DataFrame":
         return self.lazy().join(other.lazy(), on=on, how=how, left_on=left_on, right_on=right_on, suffix=suffix, maintain_order=maintain_order, coalesce=coalesce).collect()
 
+    def join_asof(self, other: "DataFrame", *, on=None, left_on=None, right_on=None, by=None, by_left=None, by_right=None, strategy: str = "backward",
+                  suffix: str = "_right", tolerance=None, allow_exact_matches: bool = True, coalesce: Optional[bool] = None, check_sortedness: bool = True,
+                  allow_parallel: bool = True, force_parallel: bool = False) -> "DataFrame":
+        """As-of join: LazyFrame.join_asof states the contract."""
+        return self.lazy().join_asof(other.lazy(), on=on, left_on=left_on, right_on=right_on, by=by, by_left=by_left, by_right=by_right, strategy=strategy, suffix=suffix,
+                                     tolerance=tolerance, allow_exact_matches=allow_exact_matches, coalesce=coalesce, check_sortedness=check_sortedness,
+                                     allow_parallel=allow_parallel, force_parallel=force_parallel).collect()
+
     def sort(self, by, *more_by, descending=False, nulls_last=False, maintain_order: bool = False) -> "DataFrame":
         return self.lazy().sort(by, *more_by, descending=descending, nulls_last=nulls_last, maintain_order=maintain_order).collect()
 
@@ -1038,6 +1046,65 @@ class LazyFrame:
         lo, ro = _as_exprs([left_on]), _as_exprs([right_on])
         return LazyFrame(P.Node("join", left=self._node, right=other._node, left_on=lo, right_on=ro, how=how, suffix=suffix, maintain_order=maintain_order, coalesce=coalesce))
 
+    def join_asof(self, other: "LazyFrame", *, on=None, left_on=None, right_on=None, by=None, by_left=None, by_right=None, strategy: str = "backward",
+                  suffix: str = "_right", tolerance=None, allow_exact_matches: bool = True, coalesce: Optional[bool] = None, check_sortedness: bool = True,
+                  allow_parallel: bool = True, force_parallel: bool = False) -> "LazyFrame":
+        """As-of join (py-polars join_asof; the contract is stated at plx_join_asof_indices in include/polars_amd.h, and is the maintainers' reading of the reference).
+        Shape: one row per left row, in the left frame's row order; the left columns are the input's own; each right column is gathered at the matched right row,
+        null where there is none.
+        Groups: the candidates of a left row are the right rows whose `by` parts (0..7, integer / float / Boolean / Date / Datetime; Categorical parts are refused by
+        name) all equal the left row's, with the sort's equality (NaN == NaN, -0 == +0).  A null in any `by` part, or a null `on`, on either side makes that row match
+        nothing; a left row whose group has no right rows gets null.
+        Order: the candidates of a group are taken in (`on`, right row order) order.  Neither side needs to be sorted: the right side is checked for order on the
+        device and sorted only when that fails, every left row is searched on its own; on sorted inputs the result is the reference's.  That is why
+        `check_sortedness`, `allow_parallel` and `force_parallel` have nothing to do here: they are accepted (bools only) and change nothing.
+        strategy: "backward" = the last candidate with on_r <= on_l; "forward" = the first candidate with on_r >= on_l; "nearest" = the candidate at the smallest
+        distance, among several at that distance the last in candidate order (an equidistant pair goes to the forward value, a duplicated forward value to its
+        last row, an exact match to the last of its duplicates).  allow_exact_matches=False makes every comparison strict, for "nearest" as well.
+        tolerance: None, or t >= 0: an int in the column's own unit for an integer / Date / Datetime `on` (those two also take a datetime.timedelta, converted
+        exactly), a float for a float `on`; strings such as "2h" are refused.  The match found without the tolerance is kept only if its distance is at most t: no
+        fallback to another candidate.  Integer distances are exact in 64 unsigned bits; float distances are |a - b| in f64, equal values are distance 0, a NaN
+        distance is within no tolerance and loses against any number under "nearest".
+        `on`: any integer, Float32 / Float64, Date or Datetime (both sides of one unit; integers of different width meet in their supertype); not Boolean, not
+        Categorical.  Columns: the rules of a left join -- plain right `on` / `by` key columns are dropped unless coalesce=False, which keeps them (under `suffix`
+        where names clash); key expressions that are not plain columns never merge."""
+        for name, flag in (("check_sortedness", check_sortedness), ("allow_parallel", allow_parallel), ("force_parallel", force_parallel), ("allow_exact_matches", allow_exact_matches)):
+            if not isinstance(flag, bool):
+                raise ValueError(f"join_asof: {name} must be a bool, got {flag!r}")
+        if coalesce is not None and not isinstance(coalesce, bool):
+            raise ValueError(f"coalesce must be None, True or False, got {coalesce!r}")
+        if not isinstance(strategy, str) or strategy not in F.ASOF_STRATEGIES:
+            raise ValueError(f"strategy must be one of {list(F.ASOF_STRATEGIES)}, got {strategy!r}")
+        if on is not None:
+            if left_on is not None or right_on is not None:
+                raise ValueError(f"join_asof: `on` ({on!r}) given together with `left_on` / `right_on` ({left_on!r} / {right_on!r}): give one or the other")
+            left_on = right_on = on
+        if left_on is None or right_on is None:
+            raise ValueError(f"join_asof: needs `on`, or both `left_on` and `right_on` (got left_on={left_on!r}, right_on={right_on!r})")
+        if by is not None:
+            if by_left is not None or by_right is not None:
+                raise ValueError(f"join_asof: `by` ({by!r}) given together with `by_left` / `by_right` ({by_left!r} / {by_right!r}): give one or the other")
+            by_left = by_right = by
+        bl, br = _as_exprs([[] if by_left is None else by_left]), _as_exprs([[] if by_right is None else by_right])
+        if len(bl) != len(br):
+            raise ValueError(f"join_asof: the length of `by_left` ({len(bl)}) does not match the length of `by_right` ({len(br)})")
+        if len(bl) > F.ASOF_MAX_BY:
+            raise ValueError(f"join_asof: {len(bl)} by parts; an as-of join takes 0..{F.ASOF_MAX_BY} by parts")
+        lo, ro = _as_exprs([left_on]), _as_exprs([right_on])
+        if len(lo) != 1 or len(ro) != 1:
+            raise ValueError(f"join_asof: `on` is one column or expression per side, got {len(lo)} and {len(ro)}")
+        if tolerance is not None:
+            import math
+            if isinstance(tolerance, str):
+                raise ValueError(f"join_asof: tolerance={tolerance!r}: duration strings are not on this path; give an int in the column's own unit, a datetime.timedelta (Date / Datetime) or a float")
+            if isinstance(tolerance, float) and math.isnan(tolerance):
+                raise ValueError(f"join_asof: tolerance={tolerance!r} must be a number >= 0")
+            import datetime as _dt
+            if tolerance < (_dt.timedelta(0) if isinstance(tolerance, _dt.timedelta) else 0):
+                raise ValueError(f"join_asof: tolerance={tolerance!r} is negative")
+        return LazyFrame(P.Node("join_asof", left=self._node, right=other._node, left_on=bl + lo, right_on=br + ro, how="left", strategy=strategy, strict=not allow_exact_matches,
+                                tolerance=tolerance, suffix=suffix, coalesce=coalesce))
+
     def sort(self, by, *more_by, descending=False, nulls_last=False, maintain_order: bool = False) -> "LazyFrame":
         """LazyFrame.sort (py-polars lazyframe/frame.py sort): `descending` / `nulls_last` are one flag or one per key.
         The GPU sort is always stable, which satisfies maintain_order either way."""
@@ -1167,6 +1234,7 @@ class LazyFrame:
         from . import io as _io
         lines = [F.last_plan()] if F._lib is not None and F.last_plan() else []
         lines += P.describe_join_orders(self._node)
+        lines += P.describe_asof_joins(self._node)
         lines += P.describe_distincts(self._node)
         lines += P.describe_windows(self._node)
         lines += P.describe_cumulatives(self._node)

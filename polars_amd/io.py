@@ -768,7 +768,7 @@ def output_names(n: P.Node) -> List[str]:
         return names + [x for x in (P.expr_output_name(e) for e in n.exprs) if x not in names]
     if k == "group_by":
         return [P.expr_output_name(e) for e in n.keys] + [P.expr_output_name(e) for e in n.aggs]
-    if k == "join":
+    if k in ("join", "join_asof"):          # (a join_asof node carries how = "left": its columns follow a left join's rules)
         return list(P.join_schema(n.how, getattr(n, "coalesce", None), n.left_on, n.right_on, dict.fromkeys(output_names(n.left)), dict.fromkeys(output_names(n.right)), n.suffix))
     raise TypeError(k)
 
@@ -875,7 +875,7 @@ def push_down(node: P.Node, needed: Optional[Set[str]] = None, preds: Optional[L
     if k == "unique":          # the subset is read whatever the plan above keeps; no subset: every column decides
         push_down(node.input, None if (needed is None or node.subset is None) else needed | set(node.subset), None)
         return
-    if k == "join":
+    if k in ("join", "join_asof"):
         lnames, rnames = output_names(node.left), output_names(node.right)
         lk, rk = set(), set()
         for e in node.left_on:

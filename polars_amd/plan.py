@@ -58,6 +58,63 @@ def join_schema(how: str, coalesce, left_on, right_on, ls: Schema, rs: Schema, s
     return out
 
 
+def _is_temporal(dt) -> bool:
+    return dt == T.Date or isinstance(dt, T.DatetimeType)
+
+
+def asof_tolerance_literal(tolerance: Any, on_dt: T.DataType) -> Tuple[Any, T.DataType]:
+    """The tolerance of a join_asof as the literal of its PLX_IR_JOIN_ASOF node: (value, literal dtype) in the `on` dtype's family.  Integer and temporal `on`: an
+    int in the column's own unit (Int64, UInt64 for an unsigned `on`); Date / Datetime also take a datetime.timedelta, converted exactly (one that is no whole number
+    of the unit is refused); float `on`: a float (Float64).  Negative, NaN and duration strings ("2h") are ValueErrors naming the value."""
+    import datetime as _dt
+    import math
+    import numbers
+    if isinstance(tolerance, str):
+        raise ValueError(f"join_asof: tolerance={tolerance!r}: duration strings are not on this path; give an int in the column's own unit, a datetime.timedelta (Date / Datetime) or a float")
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (numbers.Real, _dt.timedelta)):
+        raise ValueError(f"join_asof: tolerance={tolerance!r} is neither a number nor a datetime.timedelta")
+    if isinstance(tolerance, _dt.timedelta):
+        if not _is_temporal(on_dt):
+            raise ValueError(f"join_asof: tolerance={tolerance!r}: a timedelta needs a Date or Datetime `on`, this one is {on_dt}")
+        us = (tolerance.days * 86_400 + tolerance.seconds) * 1_000_000 + tolerance.microseconds
+        if us < 0:
+            raise ValueError(f"join_asof: tolerance={tolerance!r} is negative")
+        num, den = (us, 86_400_000_000) if on_dt == T.Date else (us * on_dt.ticks_per_second(), 1_000_000)
+        if num % den:
+            raise ValueError(f"join_asof: tolerance={tolerance!r} is no whole number of the unit of `on` ({'days' if on_dt == T.Date else on_dt.time_unit})")
+        return num // den, T.Int64
+    if on_dt.is_float():
+        f = float(tolerance)
+        if math.isnan(f) or f < 0:
+            raise ValueError(f"join_asof: tolerance={tolerance!r} must be a number >= 0")
+        return f, T.Float64
+    if not isinstance(tolerance, numbers.Integral):
+        if isinstance(tolerance, float) and (math.isnan(tolerance) or tolerance < 0):
+            raise ValueError(f"join_asof: tolerance={tolerance!r} must be a number >= 0")
+        raise ValueError(f"join_asof: tolerance={tolerance!r}: `on` is {on_dt}, so the tolerance is an int in the column's own unit" + (" or a datetime.timedelta" if _is_temporal(on_dt) else ""))
+    v = int(tolerance)
+    if v < 0:
+        raise ValueError(f"join_asof: tolerance={tolerance!r} is negative")
+    lit_dt = T.UInt64 if on_dt.name.startswith("UInt") else T.Int64
+    if v > (2 ** 64 - 1 if lit_dt == T.UInt64 else 2 ** 63 - 1):
+        raise ValueError(f"join_asof: tolerance={tolerance!r} does not fit the {lit_dt} literal of the plan node")
+    return v, lit_dt
+
+
+def describe_asof_joins(node: Node) -> List[str]:
+    """One line per join_asof under `node` (LazyFrame.explain): the JoinAsof node as it is lowered."""
+    out: List[str] = []
+    for attr in ("input", "left", "right"):
+        child = getattr(node, attr, None)
+        if isinstance(child, Node):
+            out += describe_asof_joins(child)
+    if node.kind == "join_asof":
+        by = ", ".join(f"{a!r} = {b!r}" for a, b in zip(node.left_on[:-1], node.right_on[:-1]))
+        out.append(f"JoinAsof[strategy={node.strategy}{' strict' if node.strict else ''}, by=[{by}], on={node.left_on[-1]!r} / {node.right_on[-1]!r}, "
+                   f"tolerance={node.tolerance!r}, order=left rows]")
+    return out
+
+
 def describe_distincts(node: Node) -> List[str]:
     """One line per unique() under `node` (LazyFrame.explain): the Distinct node as it is lowered."""
     out: List[str] = []
@@ -718,6 +775,45 @@ class Lowering:
             coalesce = getattr(n, "coalesce", None)
             out_schema = join_schema(n.how, coalesce, n.left_on, n.right_on, ls, rs, n.suffix)
             return push(kind=F.IR_JOIN, input=li, input_right=ri, keys=lk, keys_right=rk, how=how, suffix=n.suffix, maintain_order=order, coalesce=JOIN_COALESCE[coalesce]), out_schema
+        if k == "join_asof":
+            # keys / keys_right: the by parts first, `on` last; the Datetime-unit and supertype rules of a join; Categorical by parts and a Boolean / Categorical `on` refused
+            li, ls = self.lower_node(n.left)
+            ri, rs = self.lower_node(n.right)
+            if n.strategy not in F.ASOF_STRATEGIES:
+                raise ValueError(f"strategy must be one of {list(F.ASOF_STRATEGIES)}, got {n.strategy!r}")
+            if len(n.left_on) - 1 > F.ASOF_MAX_BY:
+                raise ValueError(f"join_asof: {len(n.left_on) - 1} by parts; an as-of join takes 0..{F.ASOF_MAX_BY}")
+            lk, rk, on_dt = [], [], None
+            for j, (a, b) in enumerate(zip(n.left_on, n.right_on)):
+                is_on = j == len(n.left_on) - 1
+                what = "`on`" if is_on else f"by part {j} ({a!r} = {b!r})"
+                ai, adt = self.lower_expr(a, ls)
+                bi, bdt = self.lower_expr(b, rs)
+                for dt in (adt, bdt):
+                    if isinstance(dt, T.Categorical):
+                        raise TypeError(f"join_asof: {what} is Categorical: " + ("`on` may be an integer, a float, a Date or a Datetime" if is_on else
+                                        "Categorical by parts are not on this path yet (the two dictionaries would have to be reconciled); join on the codes of one shared dictionary, or on an integer key"))
+                    if is_on and dt == T.Boolean:
+                        raise TypeError("join_asof: `on` is Boolean: `on` may be an integer, a float, a Date or a Datetime")
+                if isinstance(adt, T.DatetimeType) and isinstance(bdt, T.DatetimeType) and adt.time_unit != bdt.time_unit:
+                    raise TypeError(f"join keys Datetime[{adt.time_unit}] and Datetime[{bdt.time_unit}]: casts between time units are not on this path")
+                if _is_temporal(adt) != _is_temporal(bdt) or (_is_temporal(adt) and isinstance(adt, T.DatetimeType) != isinstance(bdt, T.DatetimeType)):
+                    raise TypeError(f"join_asof: {what} is {adt} on the left and {bdt} on the right")
+                st = adt
+                if adt.physical != bdt.physical:
+                    st = T.supertype(adt, bdt)
+                    ai = self._cast(ai, adt, st)
+                    bi = self._cast(bi, bdt, st)
+                lk.append(ai)
+                rk.append(bi)
+                on_dt = st
+            tol = -1
+            if n.tolerance is not None:
+                value, lit_dt = asof_tolerance_literal(n.tolerance, on_dt)
+                tol = self._lit_node(value, lit_dt)
+            out_schema = join_schema("left", n.coalesce, n.left_on, n.right_on, ls, rs, n.suffix)
+            return push(kind=F.IR_JOIN_ASOF, input=li, input_right=ri, keys=lk, keys_right=rk, how=F.ASOF_STRATEGIES[n.strategy] | (F.ASOF_STRICT if n.strict else 0),
+                        predicate=tol, suffix=n.suffix, coalesce=JOIN_COALESCE[n.coalesce]), out_schema
         if k == "sort":
             inp, schema = self.lower_node(n.input)
             keys = [self.lower_expr(e, schema)[0] for e in n.by]

@@ -234,3 +234,14 @@ def q14_promo(lineitem, part, prefix="PROMO"):
     rev = c("l_extendedprice") * (1 - c("l_discount"))
     j = lineitem.join(part, left_on="l_partkey", right_on="p_partkey")
     return j.select(E.when(c("p_type").str.starts_with(prefix)).then(rev).otherwise(0.0).sum().alias("promo_revenue"), rev.sum().alias("revenue"))
+
+
+def quote_before_trade(trades, quotes, tolerance=None):
+    """Every trade with the last quote of its symbol at or before it, at most `tolerance` (default one second) old, then per symbol how many trades found a quote
+    and what they paid over it: join_asof(by="sym", on="ts", tolerance=...) -> group_by("sym").  trades / quotes: sym, ts (Datetime), price; neither side needs to
+    be sorted."""
+    c = E.col
+    tol = dt.timedelta(seconds=1) if tolerance is None else tolerance
+    j = trades.join_asof(quotes, by="sym", on="ts", tolerance=tol)
+    return j.group_by("sym").agg(E.len().alias("trades"), c("price_right").count().alias("quoted"), (c("price") - c("price_right")).mean().alias("mean_over_quote"),
+                                 c("price_right").max().alias("max_quote"))
